@@ -45,6 +45,50 @@ PEAK_BF16_TFLOPS = 2500.0   # MI355X dense bf16 MFMA peak (/opt/skills/guides/MI
 # measured on).  bench.py does not read counters itself: when the sources have changed since the passes were taken, the numbers would
 # describe another build, and the fields are reported as null (with the reason) instead of silently going stale.
 ROOT = os.path.dirname(os.path.abspath(__file__))
+DUMP_BYTES = 64 << 20         # --dump-outputs: at most this much in all
+DUMP_SAMPLE = 2 << 20         # a tensor larger than this many elements is dumped as a fixed, seeded sample of this size
+
+
+def region_sizes(steps, regions):
+    """--steps timed steps in all, split into at most --regions back-to-back regions of near-equal length."""
+    n = max(1, min(regions, steps))
+    return [steps // n + (1 if r < steps % n else 0) for r in range(n)]
+
+
+def dump_sample(t, seed):
+    """t flattened; if longer than DUMP_SAMPLE, the elements at DUMP_SAMPLE indices drawn (sorted, no repeats) by numpy's seeded
+    generator: the same positions for the same seed and length in every run and build."""
+    t = t.detach().reshape(-1)
+    if t.numel() <= DUMP_SAMPLE:
+        return t
+    idx = np.sort(np.random.default_rng(seed).choice(t.numel(), DUMP_SAMPLE, replace=False))
+    return t[torch.from_numpy(idx).to(t.device)]
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: {name: tensor} -> dirname/<name>.npy, float64 kept as float64, everything else as float32."""
+    out = {}
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach().cpu()
+        out[name] = t.numpy() if t.dtype == torch.float64 else t.float().numpy()
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_BYTES}-byte budget")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+
+
+def train_step_outputs(loss, eng):
+    """What a caller of the training step receives: the loss, and per trained arena the gradients of the step and the weights after its
+    optimizer update (samples of them when large)."""
+    out = {"loss": loss.reshape(1)}
+    if eng is not None:
+        for k, a in enumerate(eng.arenas()):
+            name = "mapper" if k == 0 else "gpt2"
+            out[f"{name}_grads"] = dump_sample(a.grads(), 100 + k)
+            out[f"{name}_weights"] = dump_sample(a.w32, 200 + k)
+    return out
 
 
 def kernel_source_hash():
@@ -256,21 +300,22 @@ def decode_bench(args, device):
     prefix = torch.randn(S, L, 1024, device=device) * 0.5
     for _ in range(max(1, args.warmup)):
         generate_beam_tokens(model, prefix, beam, entry, 1.0, 50256)
-    # `regions` timed regions of exactly `steps` decodes each (box-to-box and run-to-run spread of this number exceeds most decode changes:
-    # the median region is reported, min / max beside it)
-    regions = max(1, int(getattr(args, "regions", 3) or 3))
-    each, gen = [], 0
-    for _ in range(regions):
+    # `steps` timed decodes in all, split into up to `regions` timed regions (box-to-box and run-to-run spread of this number exceeds most
+    # decode changes: the median region's time per decode is reported, min / max beside it)
+    sizes = region_sizes(args.steps, max(1, int(getattr(args, "regions", 3) or 3)))
+    regions = len(sizes)
+    each = []
+    for k in sizes:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        g_ = 0
-        for _ in range(args.steps):
+        for _ in range(k):
             toks, scores, lens = generate_beam_tokens(model, prefix, beam, entry, 1.0, 50256)
             best = scores.argmax(dim=1)
-            g_ += int(lens.gather(1, best[:, None]).sum())
+            gen = int(lens.gather(1, best[:, None]).sum())      # tokens of one decode (every decode runs the same inputs)
         torch.cuda.synchronize()
-        each.append(time.perf_counter() - t0)
-        gen = g_
+        each.append((time.perf_counter() - t0) / k)
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, {"tokens": toks.double(), "scores": scores, "seq_lengths": lens})
     dt = sorted(each)[len(each) // 2]
     steps_per_decode = toks.shape[2]
     wbytes = 2.0 * (lm.engine.arena.n - (lm.engine.dims["NPOS"] * 1024))     # bf16 weights read once per decode step
@@ -282,15 +327,15 @@ def decode_bench(args, device):
     rows_distinct = decode_distinct_rows(model, prefix, beam, entry)
     kvbytes = 2.0 * 24 * rows_distinct * 1024 * 2
     tr = pmc_constant("decode_bytes_per_position") if S == 64 else {"bytes": None, "source": None, "stale": "offline pass is for 64 prefixes"}
-    per_pos_s = dt / args.steps / steps_per_decode
+    per_pos_s = dt / steps_per_decode
     return {"metric": "decode tok/s (beam=5, GPT-2-medium, KV cache)", "value": round(gen / dt, 1), "unit": "tokens/s", "n_gpus": 1,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt * 1e3, 2), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
             "config": {"workload": "BASELINE configs[4]: beam=5 decode, GPT-2-medium random init, 64 prefixes x 10 rows, 67 new tokens",
                        "prefixes": S, "beam": beam, "entry_length": entry, "generated_steps": steps_per_decode},
             "beam_tokens_per_s": round(gen * beam / dt, 1),
-            "timed_regions": {"regions": regions, "decodes_per_region": args.steps, "statistic": "median region",
-                              "ms_per_batch_each": [round(e / args.steps * 1e3, 2) for e in each],
+            "timed_regions": {"regions": regions, "decodes_per_region": sizes, "statistic": "median region",
+                              "ms_per_batch_each": [round(e * 1e3, 2) for e in each],
                               "tokens_per_s_min": round(gen / max(each), 1), "tokens_per_s_max": round(gen / min(each), 1)},
             "roofline": {"bound": "hbm", "kernel": "whole decode step (weights once per generated position + the distinct KV rows of every beam group)",
                          "achieved": round((wbytes + kvbytes) / per_pos_s / 1e9, 1), "peak": 8000.0, "unit": "GB/s",
@@ -366,6 +411,8 @@ def sample_bench(args, device):
         n += int(toks.shape[0] * toks.shape[1])
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, {"tokens": toks.double(), "stop_pos": stop_pos.double()})
     return {"metric": "sampling decode tok/s (nucleus top_p=0.8, GPT-2-medium, KV cache)", "value": round(n / dt, 1), "unit": "tokens/s",
             "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
@@ -381,24 +428,28 @@ def mapper_bench(args, device):
         c["B"] = args.batch
     me, ge, eng = init_engines(c, device)
     B = c["B"]
-    emb = torch.randn(B, c["E"], device=device)
-    dout = torch.randn(B, c["L"], c["D"], device=device) * 1e-3
+    gen = torch.Generator(device=device).manual_seed(1234)
+    emb = torch.randn(B, c["E"], generator=gen, device=device)
+    dout = torch.randn(B, c["L"], c["D"], generator=gen, device=device) * 1e-3
 
     def it():
         me.arena.grads().zero_()
-        me.forward(emb, save=True)
+        out = me.forward(emb, save=True)
         me.backward(dout)
+        return out
 
     for _ in range(max(1, args.warmup)):
         it()
     torch.cuda.synchronize()
     each = []
-    for _ in range(max(1, int(getattr(args, "regions", 3) or 3))):      # median of the timed regions, min / max beside it
+    for k in region_sizes(args.steps, max(1, int(getattr(args, "regions", 3) or 3))):   # median of the timed regions, min / max beside it
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            it()
+        for _ in range(k):
+            prefix = it()
         torch.cuda.synchronize()
-        each.append((time.perf_counter() - t0) / args.steps)
+        each.append((time.perf_counter() - t0) / k)
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, {"prefix": dump_sample(prefix, 300), "mapper_grads": dump_sample(me.arena.grads(), 100)})
     dt = sorted(each)[len(each) // 2]
     tf = 3 * mapper_flops_fwd(c) * B / dt / 1e12
     return {"metric": "mapping-transformer fwd+bwd (batch 256)", "value": round(B / dt, 1), "unit": "samples/s", "n_gpus": 1, "steps": args.steps,
@@ -522,7 +573,15 @@ def e2e_bench(args, device, max_tokens=None):
     from clipcap_amd.train import add_training_args, train
     c = dict(CONFIGS["2"])
     B = args.batch or c["B"]
-    rows = max(204800, (args.steps + 60) * B) // (4 * B) * (4 * B)
+    if args.steps > 0:
+        # --mode e2e: exactly --steps timed steps after a warm-up of up to 50 (the four shards hold whole batches: steps in all % 4 == 0)
+        warm = min(50, max(1, args.steps // 4))
+        warm += -(args.steps + warm) % 4
+        rows = (args.steps + warm) * B
+    else:
+        # the default line's sub-benchmark: one epoch over >= 200 k rows, timed after 50 steps
+        rows = max(204800, 60 * B) // (4 * B) * (4 * B)
+        warm = None
     out = {}
     with tempfile.TemporaryDirectory(prefix="clipcap_e2e_") as tmp:
         t0 = time.perf_counter()
@@ -541,7 +600,8 @@ def e2e_bench(args, device, max_tokens=None):
             "--reader-max-piece-size", "50", "--device", str(device.index or 0)])
         a.max_token_length = max_tokens
         n_steps = rows // B
-        warm = min(50, n_steps // 4)
+        if warm is None:
+            warm = min(50, n_steps // 4)
         st = {}
 
         def hook(step, model):
@@ -614,11 +674,11 @@ def main():
     ap.add_argument("--mode", default="train", choices=["train", "decode", "mapper", "sample", "e2e"])
     ap.add_argument("--reader-parallel-pieces", type=int, default=10, help="--mode e2e: background reader workers (0 = read and tokenise on the training thread)")
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps in all (split over --regions)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--regions", type=int, default=5,
-                    help="the timed region of exactly --steps steps is run this many times back to back (each bracketed by barrier + synchronize, "
-                         "max over ranks); ms_per_step / value are the MEDIAN region, min / max are reported beside it")
+                    help="the --steps timed steps are split into this many back-to-back regions of near-equal length (each bracketed by barrier + "
+                         "synchronize, max over ranks); ms_per_step / value are the MEDIAN region's, min / max are reported beside it")
     ap.add_argument("--config", default="2", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch override")
     ap.add_argument("--site", default="lmhead_fwd", help="single GEMM call site timed for the roofline_lmhead object")
@@ -641,15 +701,22 @@ def main():
                     help="no GPU: every rank walks THIS file's control flow (warm-up, timed regions, max-over-ranks, the no-all-reduce pass, the "
                          "event-bracketed passes, process-group teardown, rank 0's sub-benches and CPU baseline) with a stub workload over gloo — "
                          "what tests/test_ddp_gloo.py runs at 8 ranks to show that no rank is left waiting in a collective")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, "
+                         "seeded samples of large tensors, <= 64 MB in all); the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.mode == "e2e":
+        ap.error("--dump-outputs is not supported with --mode e2e")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # launched bare (`python bench.py --gpus 8`): start the N ranks ourselves exactly as the driver's torchrun line does, and never
         # print a 1-rank line for an N-GPU request
         import socket
         import subprocess
-        have = torch.cuda.device_count()
-        if have < args.gpus and "CC_BENCH_DEVICE" not in os.environ and not args.dry_run:
+        have = torch.cuda.device_count() if not args.dry_run else args.gpus      # (a dry run never opens the GPU)
+        if have < args.gpus and "CC_BENCH_DEVICE" not in os.environ:
             sys.exit(f"bench.py: --gpus {args.gpus} requested but {have} GPU(s) visible; refusing to report a smaller run")
         with socket.socket() as sock:
             sock.bind(("127.0.0.1", 0))
@@ -693,7 +760,7 @@ def main():
     if args.grad_wire == "auto":      # clipcap_amd.train.train.grad_wire_dtype: fp32 in the fp32-parity mode and for a full finetune
         args.grad_wire = "fp32" if (c["train_lm"] or args.precision == "32") else "bf16"
 
-    total_steps = args.steps * args.regions + args.warmup
+    total_steps = args.steps + args.warmup
     base_lr, warm = 2e-5, 2
     comm = None
     if dry:
@@ -708,8 +775,9 @@ def main():
             return torch.tensor(1.0)
 
         def sync():
+            # a CPU all-reduce as the barrier: barrier() probes for an accelerator, which would open the GPU in every rank of a dry run
             if world > 1:
-                torch.distributed.barrier()
+                torch.distributed.all_reduce(torch.zeros(1))
 
         def profile(n_steps, site, per_step, first_step):
             for i in range(first_step, first_step + n_steps):
@@ -768,17 +836,20 @@ def main():
     for i in range(args.warmup):
         loss = one_step(i)
     nxt = args.warmup
-    region_s = []
-    for _ in range(max(1, args.regions)):
-        # one timed region: EXACTLY --steps steps between barrier + synchronize on both sides, max over ranks
+    sizes = region_sizes(args.steps, args.regions)
+    region_ms = []
+    for k in sizes:
+        # one timed region: k of the --steps timed steps between barrier + synchronize on both sides, max over ranks
         sync()
         t0 = time.perf_counter()
-        for i in range(nxt, nxt + args.steps):
+        for i in range(nxt, nxt + k):
             loss = one_step(i)
         sync()
-        region_s.append(max_over_ranks(time.perf_counter() - t0))
-        nxt += args.steps
-    dt = sorted(region_s)[len(region_s) // 2]
+        region_ms.append(max_over_ranks(time.perf_counter() - t0) / k * 1e3)
+        nxt += k
+    ms_per_step = sorted(region_ms)[len(region_ms) // 2]
+    if args.dump_outputs and rank == 0:     # the last timed step's outputs, before any untimed step below changes the arenas
+        dump_outputs(args.dump_outputs, train_step_outputs(loss, eng))
     exposed_ms = None
     if world > 1:
         # the same steps with the gradient all-reduce left out (timing only): the difference is the all-reduce time that backward
@@ -789,9 +860,8 @@ def main():
         for i in range(nxt, nxt + k2):
             one_step(i, reduce=False)
         sync()
-        exposed_ms = max(0.0, dt / args.steps - max_over_ranks((time.perf_counter() - t1) / k2)) * 1e3
+        exposed_ms = max(0.0, ms_per_step - max_over_ranks((time.perf_counter() - t1) / k2) * 1e3)
         nxt += k2
-    ms_per_step = dt / args.steps * 1e3
     T, D, Mc, M = c["L"] + cap, c["D"], B * cap, B * (c["L"] + cap)
     S = c["P"] + c["L"]
     roof = {}
@@ -850,9 +920,9 @@ def main():
         sys.stderr.flush()
     if rank != 0:
         return
-    value = B * world * args.steps / dt
-    step_tflops = step_flops(c) * B * world * args.steps / dt / 1e12
-    exec_tflops = executed_step_flops(c) * B * world * args.steps / dt / 1e12
+    value = B * world / (ms_per_step * 1e-3)
+    step_tflops = step_flops(c) * B * world / (ms_per_step * 1e-3) / 1e12
+    exec_tflops = executed_step_flops(c) * B * world / (ms_per_step * 1e-3) / 1e12
     out = {
         "metric": "train samples/sec (512-d prefix, 40-tok caption)", "value": round(value, 2), "unit": "samples/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
@@ -860,9 +930,9 @@ def main():
         "config": {"workload": f"BASELINE configs[{int(args.config) - 1}]: {c['name']}", "per_gpu_batch": B, "global_batch": B * world,
                    "caption_tokens": cap, "encoder_dim": c["E"], "train_language_model": c["train_lm"],
                    "parallelism": f"dp{world}", "final_loss": round(float(loss.item()), 4)},
-        "timed_regions": {"regions": len(region_s), "steps_per_region": args.steps, "statistic": "median region (ms_per_step, value)",
-                          "ms_per_step_each": [round(r / args.steps * 1e3, 3) for r in region_s],
-                          "ms_per_step_min": round(min(region_s) / args.steps * 1e3, 3), "ms_per_step_max": round(max(region_s) / args.steps * 1e3, 3)},
+        "timed_regions": {"regions": len(sizes), "steps_per_region": sizes, "statistic": "median region (ms_per_step, value)",
+                          "ms_per_step_each": [round(r, 3) for r in region_ms],
+                          "ms_per_step_min": round(min(region_ms), 3), "ms_per_step_max": round(max(region_ms), 3)},
         "step_algorithmic_tflops": round(step_tflops, 1),
         "step_executed_tflops": round(exec_tflops, 1),
         "step_frac_of_bf16_peak": round(step_tflops / (PEAK_BF16_TFLOPS * world), 4),
@@ -892,7 +962,7 @@ def main():
         # north_star sub-targets in the same line: mapping-transformer fwd+bwd alone (target >= 40 % of the bf16 peak at batch 256), the
         # same at 4x / 16x the batch (is the limiter the problem size or the kernels?), and KV-cached beam decode (BASELINE configs[4])
         key = args.config if args.config in ("2", "3", "4") else "2"
-        sub = argparse.Namespace(config=key, batch=0, steps=50, warmup=5, regions=3)
+        sub = argparse.Namespace(config=key, batch=0, steps=150, warmup=5, regions=3)
         mb = mapper_bench(sub, device)
         out["mapper"] = {"ms_fwd_bwd": mb["ms_per_step"], "ms_fwd_bwd_min": mb["ms_per_step_min"], "ms_fwd_bwd_max": mb["ms_per_step_max"], "samples_per_s": mb["value"], "tflops": mb["roofline"]["achieved"],
                          "frac_of_bf16_peak": mb["roofline"]["frac"], "target_frac": 0.40, "batch": CONFIGS[key]["B"], "batch_sweep": []}
@@ -904,7 +974,7 @@ def main():
             torch.cuda.empty_cache()
         del mb
         torch.cuda.empty_cache()
-        db = decode_bench(argparse.Namespace(batch=0, steps=3, warmup=1, regions=3), device)
+        db = decode_bench(argparse.Namespace(batch=0, steps=9, warmup=1, regions=3), device)
         out["decode"] = {"metric": db["metric"], "tokens_per_s": db["value"], "beam_tokens_per_s": db["beam_tokens_per_s"],
                          "ms_per_batch": db["ms_per_step"], "timed_regions": db["timed_regions"], "config": db["config"]["workload"],
                          "roofline": db["roofline"]}

@@ -129,6 +129,7 @@ struct MapperWS {
     act_t *gdx[MAX_LAYERS], *gdxb[MAX_LAYERS], *gdh[MAX_LAYERS], *gdqkv[MAX_LAYERS];
     bool own_grads;     // every layer has its own copies (else they alias the single dx16 / dx16b / dh16 / dqkv16 buffers and weight gradients flush per layer)
     float* wg_scratch;
+    float* red;         // partial sums of the cross-block reductions (kernels.h red_set_scratch)
     float* adelta;
     uint16_t* gimg;    // bf16x3 build: the [hi | hi | lo] image of the output gradient both GEMMs of a layer step read
     char* x3;          // bf16x3 build: operand-image scratch of the GEMM in flight (gemm_api.h)
@@ -188,12 +189,14 @@ void mapper_carve(const cc_mapper_cfg* c, int B, int save, void* ws, MapperWS& w
             w.gdqkv[l] = own ? cv.take<act_t>(M * 3 * D) : w.dqkv16;
         }
         w.wg_scratch = cv.take<float>(WGRAD_SCRATCH_BYTES / sizeof(float));
+        w.red = cv.take<float>(RED_SCRATCH_FLOATS);
         w.adelta = cv.take<float>((size_t)B * c->H * S);
         // bf16x3: an output gradient is the operand of TWO GEMMs in the same image form (its layer's weight gradient and input gradient):
         // split once into this buffer, read twice (the widest is d qkv)
         w.gimg = kX3 ? reinterpret_cast<uint16_t*>(cv.take<char>(x3_img(M, std::max<size_t>(3 * (size_t)D, c->Hm)))) : nullptr;
     } else {
         w.dx32 = nullptr; w.dx16 = w.dx16b = w.dh16 = w.dxn16 = w.datt16 = w.dqkv16 = w.dlin16 = nullptr; w.wg_scratch = nullptr; w.adelta = nullptr;
+        w.red = nullptr;
         w.gimg = nullptr;
         for (int l = 0; l < c->N; l++) w.gdx[l] = w.gdxb[l] = w.gdh[l] = w.gdqkv[l] = nullptr;
         w.own_grads = false;
@@ -271,6 +274,7 @@ struct Gpt2WS {
     float* dx32;
     act_t *dx16, *dx16b, *dhf16, *du16, *dxn16, *datt16, *dqkv16;
     float* wg_scratch;
+    float* red;        // partial sums of the cross-block reductions (kernels.h red_set_scratch)
     float* adelta;
     char* x3;          // bf16x3 build: operand-image scratch
     size_t x3_bytes;
@@ -326,9 +330,10 @@ void gpt2_carve(const cc_gpt2_cfg* c, int B, int T, int cap, int mode, void* ws,
         w.datt16 = cv.take<act_t>(M * D);
         w.dqkv16 = cv.take<act_t>(M * 3 * D * ((kX3 && !full) ? 3 : 2) / 2);
         w.wg_scratch = full ? cv.take<float>(WGRAD_SCRATCH_BYTES / sizeof(float)) : nullptr;
+        w.red = full ? cv.take<float>(RED_SCRATCH_FLOATS) : nullptr;      // only a full finetune reduces parameter gradients across blocks
         w.adelta = cv.take<float>((size_t)B * c->H * T);
     } else {
-        w.wg_scratch = nullptr; w.adelta = nullptr;
+        w.wg_scratch = nullptr; w.adelta = nullptr; w.red = nullptr;
         w.logits16 = nullptr; w.pmax = w.psum = w.tgt_logit = w.lse_row = w.row_loss = nullptr;
         w.cref = w.lmfac = nullptr; w.hfs16 = nullptr;
         w.dx32 = nullptr; w.dx16 = w.dx16b = w.dhf16 = w.du16 = w.dxn16 = w.datt16 = w.dqkv16 = nullptr;
@@ -450,6 +455,7 @@ int CC_API(cc_mapper_fwd)(const cc_mapper_cfg* c, int32_t B, const float* w32, c
     MapperWS w;
     mapper_carve(c, B, save, ws, w);
     X3_SCRATCH(w);
+    red_set_scratch(w.red);
     const int D = c->D, PP = c->W * c->P, S = PP + c->L, M = B * S, H = c->H, hd = D / H, Hm = c->Hm;
     const int PD = c->P * D;
     // linear (mapper.py:123): [B*W, E] x [P*D, E]^T + b -> rows 0..PP-1 of every sample of x[0]
@@ -503,6 +509,7 @@ int CC_API(cc_mapper_bwd_range)(const cc_mapper_cfg* c, int32_t B, const float* 
     MapperWS w;
     mapper_carve(c, B, 1, ws, w);
     X3_SCRATCH(w);
+    red_set_scratch(w.red);
     const int D = c->D, PP = c->W * c->P, S = PP + c->L, M = B * S, H = c->H, hd = D / H, Hm = c->Hm;
     const int PD = c->P * D;
     const uint16_t* w16t = W16(w16, o.total);   // transposed weight copies: dgrad GEMMs are NT
@@ -761,6 +768,7 @@ int CC_API(cc_gpt2_fwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const floa
     Gpt2WS w;
     gpt2_carve(c, s->B, s->T, s->T - s->L, s->mode, ws, w);
     X3_SCRATCH(w);
+    red_set_scratch(w.red);
     const int D = c->D, M = s->B * s->T, H = c->H, hd = D / H;
     const uint16_t* w16t = W16(w16, o.total);   // Conv1D weights transposed to [out,in]: every forward GEMM is NT
     for (int l = 0; l < c->NL; l++) {
@@ -828,6 +836,7 @@ int CC_API(cc_gpt2_logits)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const f
     Gpt2WS w;
     gpt2_carve(c, s->B, s->T, s->T - s->L, s->mode, ws, w);
     X3_SCRATCH(w);
+    red_set_scratch(w.red);
     const int D = c->D, M = s->B * s->T;
     CC_TRY(ln_fwd(w.x[c->NL], D, nullptr, w32 + o.lnf_w, w32 + o.lnf_b, w.hf16, nullptr, w.meanf, w.rstdf, M, D, st));
     return gemm_f32out(0, 0, w.hf16, D, W16(w16, o.wte), D, M, Ns, D, logits, (int)ldl, nullptr, 0, 1.0f, 1, st);
@@ -843,6 +852,7 @@ int CC_API(cc_lmhead_ce_fwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const
     const int cap = s->T - s->L;
     gpt2_carve(c, s->B, s->T, cap, s->mode, ws, w);
     X3_SCRATCH(w);
+    red_set_scratch(w.red);
     const int D = c->D, Mc = s->B * cap, npart = c->Vp / 64;
     if (cap != s->cap) return CC_ERR_SHAPE;  // the loss consumes every token column (model.py:108-109)
     if (hipMemsetAsync(stats, 0, 2 * sizeof(float), st) != hipSuccess) return CC_ERR_LAUNCH;
@@ -871,6 +881,7 @@ int CC_API(cc_lmhead_ce_bwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const
     const int cap = s->T - s->L;
     gpt2_carve(c, s->B, s->T, cap, s->mode, ws, w);
     X3_SCRATCH(w);
+    red_set_scratch(w.red);
     const int D = c->D, Mc = s->B * cap, M = s->B * s->T;
     const bool full = s->mode == 2;
     // exponential form: logits16 holds E = exp(logit - cref); d logits = r E - w onehot is never written — the row factors go into the
@@ -935,6 +946,7 @@ int CC_API(cc_gpt2_logits_bwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, con
     Gpt2WS w;
     gpt2_carve(c, s->B, s->T, s->T, s->mode, ws, w);      // L == 0: the loss-side buffers are sized for all B*T rows
     X3_SCRATCH(w);
+    red_set_scratch(w.red);
     const int D = c->D, M = s->B * s->T;
     const bool full = s->mode == 2;
     CC_TRY(f32_to_op16_pad(dlogits, ldl, c->V, w.logits16, c->Vp, M, st));
@@ -969,6 +981,7 @@ int CC_API(cc_gpt2_bwd_range)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, cons
     Gpt2WS w;
     gpt2_carve(c, s->B, s->T, s->T - s->L, s->mode, ws, w);
     X3_SCRATCH(w);
+    red_set_scratch(w.red);
     const int D = c->D, M = s->B * s->T, H = c->H, hd = D / H, D3 = 3 * D, D4 = 4 * D;
     const bool full = s->mode == 2;
     WgradBatch wb;          // full finetune: a layer's four weight gradients as one grouped launch + one slab reduce

@@ -14,6 +14,11 @@ int wire_unpack(const unsigned short* src, float* dst, size_t n, hipStream_t st)
 int slice_f32_to_bf16(const float* src, size_t src_stride, act_t* dst, size_t dst_stride, int len, int B, hipStream_t st);
 int broadcast_rows(float* dst, size_t dst_stride, const float* src, int len, int B, hipStream_t st);
 int add_rows(float* dst, size_t dst_stride, const float* add, int len, int B, hipStream_t st);
+// Reductions across blocks (batch_sum, ln_bwd's parameter gradients, colsum_bf16*) write per-block partials into the call's reduction
+// scratch and fold them in a fixed order, so a gradient is the same bit for bit from run to run (fp32 atomics are not).  Every C-ABI
+// entry that reaches them sets the scratch first (RED_SCRATCH_FLOATS floats of its workspace); without it they return CC_ERR_STATE.
+constexpr size_t RED_SCRATCH_FLOATS = size_t(1) << 20;
+void red_set_scratch(float* base);
 int batch_sum(const float* src, size_t src_stride, float* dst, int len, int B, hipStream_t st);
 int copy_rows(const float* src, size_t src_stride, float* dst, size_t dst_stride, int len, int B, hipStream_t st);
 

@@ -126,11 +126,56 @@ int add_rows(float* dst, size_t dst_stride, const float* add, int len, int B, hi
     return CC_OK;
 }
 
+// ---- deterministic cross-block reductions (kernels.h): per-block partials in the call's scratch, folded in a fixed order ----
+namespace {
+thread_local float* g_red = nullptr;
+}  // namespace
+void red_set_scratch(float* base) { g_red = base; }
+static float* red_scratch(size_t floats) { return floats <= RED_SCRATCH_FLOATS ? g_red : nullptr; }
+
+// partials part[y][s][j] (y < gridDim.y groups of S slices x n columns): out[y * k + j / m][j % m] += sum over s of part[y][s][j], the
+// slices summed in one fixed order: per chunk of 256 slices, lane g (of 16) of a column loads s = g, g + 16, ..., g + 240 at once and adds
+// them as a fixed tree; the 16 lane sums are then added in lane order.
+struct FoldOut { float* p[32]; int m; int k; };
+__global__ __launch_bounds__(1024) void k_fold_partials(const float* __restrict__ part, int S, int n, FoldOut o) {
+    __shared__ float red[16][64];
+    const int t = threadIdx.x & 63, g = threadIdx.x >> 6, j = blockIdx.x * 64 + t;
+    const float* __restrict__ src = part + (size_t)blockIdx.y * S * n;
+    float acc = 0.f;
+    if (j < n) {
+        for (int k0 = 0; k0 < S; k0 += 256) {
+            float v[16];
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const int k = k0 + g + 16 * i;
+                v[i] = k < S ? src[(size_t)k * n + j] : 0.f;
+            }
+#pragma unroll
+            for (int w = 8; w >= 1; w >>= 1)
+#pragma unroll
+                for (int i = 0; i < w; i++) v[i] += v[i + w];
+            acc += v[0];
+        }
+    }
+    red[g][t] = acc;
+    __syncthreads();
+    if (g == 0 && j < n) {
+        float s = 0.f;
+#pragma unroll
+        for (int q = 0; q < 16; q++) s += red[q][t];
+        o.p[blockIdx.y * o.k + j / o.m][j % o.m] += s;
+    }
+}
+static int fold_partials(const float* part, int S, int n, int groups, const FoldOut& o, hipStream_t st) {
+    hipLaunchKernelGGL(k_fold_partials, dim3((n + 63) / 64, groups), dim3(1024), 0, st, part, S, n, o);
+    return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
+}
+
 // dst[i] += sum_b src[b*src_stride + i]   (gradient of a broadcast block).  Grid = column blocks x batch slices: each thread sums its
-// slice of the batch with 4 independent loads in flight, one fp32 atomic per (column, slice) folds the slices (a single thread per
-// column walking all B rows took 58 us for 256 x 7680 floats: 30 blocks, one load in flight each).
+// slice of the batch with 4 independent loads in flight; the slices' partial sums are folded in a fixed order by k_fold_partials (a
+// single thread per column walking all B rows took 58 us for 256 x 7680 floats: 30 blocks, one load in flight each).
 __global__ __launch_bounds__(256) void k_batch_sum(const float* __restrict__ src, size_t src_stride, float* __restrict__ dst, int len, int B,
-                                                    int per) {
+                                                    int per, float* __restrict__ part) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= len) return;
     const int b0 = blockIdx.y * per, b1 = min(B, b0 + per);
@@ -145,7 +190,7 @@ __global__ __launch_bounds__(256) void k_batch_sum(const float* __restrict__ src
     for (; b < b1; b++) s0 += src[(size_t)b * src_stride + i];
     const float s = (s0 + s1) + (s2 + s3);
     if (gridDim.y == 1) dst[i] += s;
-    else __hip_atomic_fetch_add(dst + i, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else part[(size_t)blockIdx.y * len + i] = s;
 }
 int batch_sum(const float* src, size_t src_stride, float* dst, int len, int B, hipStream_t st) {
     if (!len || B <= 0) return CC_OK;
@@ -153,8 +198,13 @@ int batch_sum(const float* src, size_t src_stride, float* dst, int len, int B, h
     int slices = std::max(1, std::min(B / 8, 1024 / colb));        // ~1k blocks, at least 8 rows per slice
     const int per = (B + slices - 1) / slices;
     slices = (B + per - 1) / per;
-    hipLaunchKernelGGL(k_batch_sum, dim3(colb, slices), dim3(256), 0, st, src, src_stride, dst, len, B, per);
-    return CC_OK;
+    float* part = slices > 1 ? red_scratch((size_t)slices * len) : nullptr;
+    if (slices > 1 && !part) return CC_ERR_STATE;
+    hipLaunchKernelGGL(k_batch_sum, dim3(colb, slices), dim3(256), 0, st, src, src_stride, dst, len, B, per, part);
+    if (slices == 1) return CC_OK;
+    FoldOut o{};
+    o.p[0] = dst; o.m = len; o.k = 1;
+    return fold_partials(part, slices, len, 1, o, st);
 }
 
 // dst[b*dst_stride + i] = src[b*src_stride + i]  fp32 strided copy (len % 4 == 0)
@@ -349,8 +399,8 @@ int ln_fwd(const float* x, int ldx, const int* row_map, const float* gamma, cons
 }
 
 // LayerNorm backward.  dy(bf16)[r]; x[map(r)]; mean/rstd[r].  dx_out[map(r)] = (dres ? dres[map(r)] : 0) + dLN ; also a
-// bf16 copy of dx_out for the next dgrad GEMM.  Optional dgamma/dbeta (atomic fp32 accumulation, one atomic per
-// column per block) and, with them, dcol[c] += sum_r dx16[r][c] — the bias gradient of the Linear whose output gradient dx16 is
+// bf16 copy of dx_out for the next dgrad GEMM.  Optional dgamma/dbeta (one partial sum per column per block into `part`, folded
+// in a fixed order by k_fold_partials) and, with them, dcol[c] += sum_r dx16[r][c] — the bias gradient of the Linear whose output gradient dx16 is
 // (column sums of the 16-bit values, exactly what k_colsum_bf16 on dx16 gives): one launch less per bias.
 // Each wave walks rows  row = blockIdx*4 + wave + k*gridDim*4.
 template <int NV, bool DG, int NW>   // NV as in k_ln_fwd; DG: accumulate dgamma / dbeta; NW waves per block
@@ -359,7 +409,7 @@ __global__ __launch_bounds__(NW * 64) void k_ln_bwd(const act_t* __restrict__ dy
                                                 const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                 const float* __restrict__ dres, float* __restrict__ dx32,
                                                 act_t* __restrict__ dx16, float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                float* __restrict__ dcol, int rows, int D, Drop dmask, int img) {
+                                                float* __restrict__ dcol, int rows, int D, Drop dmask, int img, float* __restrict__ part) {
     // img (bf16x3 build, ldx == D): dx16 receives the [hi | hi | lo] operand image of the input-gradient GEMM that reads it
     extern __shared__ __attribute__((aligned(16))) float ln_red[];  // [2][NW][D] when dgamma
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -466,6 +516,7 @@ __global__ __launch_bounds__(NW * 64) void k_ln_bwd(const act_t* __restrict__ dy
     if constexpr (DG) {
         float* rg = ln_red;
         float* rb = ln_red + NW * D;
+        float* pp = part + (size_t)blockIdx.x * (dcol ? 3 : 2) * D;      // this block's partials: [dgamma | dbeta | dcol]
 #pragma unroll
         for (int it = 0; it < NV; it++) {
             const int c = lane * 4 + it * 256;
@@ -479,8 +530,8 @@ __global__ __launch_bounds__(NW * 64) void k_ln_bwd(const act_t* __restrict__ dy
             float sg = 0.f, sb = 0.f;
 #pragma unroll
             for (int w = 0; w < NW; w++) { sg += rg[w * D + c]; sb += rb[w * D + c]; }
-            __hip_atomic_fetch_add(dgamma + c, sg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(dbeta + c, sb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            pp[c] = sg;
+            pp[D + c] = sb;
         }
         if (dcol) {                          // third reduction through the same buffer
             __syncthreads();
@@ -494,7 +545,7 @@ __global__ __launch_bounds__(NW * 64) void k_ln_bwd(const act_t* __restrict__ dy
                 float sc = 0.f;
 #pragma unroll
                 for (int w = 0; w < NW; w++) sc += rg[w * D + c];
-                __hip_atomic_fetch_add(dcol + c, sc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                pp[2 * D + c] = sc;
             }
         }
     }
@@ -505,11 +556,14 @@ int ln_bwd(const act_t* dy, const float* x, int ldx, const int* row_map, const f
     if (D > LN_MAXV * 256 || (D & 3) || (ldx & 3) || (dcol && (!dgamma || !dx16 || row_map)) || (dmask.thresh && (row_map || ldx != D)))
         return CC_ERR_SHAPE;
     if (rows <= 0) return CC_OK;
-    // with parameter gradients every block ends with 2*D fp32 atomics: keep the block count low (one per CU) so that the
-    // atomic tail (measured: it dominated at 1024 blocks) stays ~0.4 M atomics per launch, and give those blocks 8 waves
+    // with parameter gradients every block ends with 2*D (3*D with dcol) partial sums that k_fold_partials folds in a fixed order: keep
+    // the block count low (one per CU) so that the partials stay small, and give those blocks 8 waves
     const int nw = (dgamma && (size_t)16 * D * sizeof(float) <= 65536) ? 8 : 4;      // 8-wave reduction buffer within the 64 KiB default
     static const int dg_grid = []() { const char* e = cc_lab_env("CC_LNBWD_GRID"); return e ? atoi(e) : 256; }();   // tuning knob
-    const int grid = std::min((rows + nw - 1) / nw, dgamma ? dg_grid : 8192);
+    const int nvec = dcol ? 3 : 2;
+    const int grid = std::min((rows + nw - 1) / nw, dgamma ? std::max(1, std::min(dg_grid, (int)(RED_SCRATCH_FLOATS / ((size_t)nvec * D)))) : 8192);
+    float* part = dgamma ? red_scratch((size_t)grid * nvec * D) : nullptr;
+    if (dgamma && !part) return CC_ERR_STATE;
     const size_t sh = dgamma ? (size_t)2 * nw * D * sizeof(float) : 0;
     int img = 0;
 #if CC_OP == 2
@@ -518,19 +572,22 @@ int ln_bwd(const act_t* dy, const float* x, int ldx, const int* row_map, const f
         img = 1;
     }
 #endif
-#define LN_BWD(NV, DG, NW) hipLaunchKernelGGL((k_ln_bwd<NV, DG, NW>), dim3(grid), dim3(NW * 64), sh, st, dy, x, ldx, row_map, mean, rstd, gamma, dres, dx32, dx16, dgamma, dbeta, dcol, rows, D, dmask, img)
+#define LN_BWD(NV, DG, NW) hipLaunchKernelGGL((k_ln_bwd<NV, DG, NW>), dim3(grid), dim3(NW * 64), sh, st, dy, x, ldx, row_map, mean, rstd, gamma, dres, dx32, dx16, dgamma, dbeta, dcol, rows, D, dmask, img, part)
 #define LN_BWD_D(DG, NW) { if (D <= 256) LN_BWD(1, DG, NW); else if (D <= 512) LN_BWD(2, DG, NW); else if (D <= 768) LN_BWD(3, DG, NW); else if (D <= 1024) LN_BWD(4, DG, NW); else LN_BWD(LN_MAXV, DG, NW); }
     if (dgamma && nw == 8) LN_BWD_D(true, 8) else if (dgamma) LN_BWD_D(true, 4) else LN_BWD_D(false, 4)
 #undef LN_BWD_D
 #undef LN_BWD
-    return CC_OK;
+    if (!dgamma) return CC_OK;
+    FoldOut o{};
+    o.p[0] = dgamma; o.p[1] = dbeta; o.p[2] = dcol; o.m = D; o.k = nvec;
+    return fold_partials(part, grid, nvec * D, 1, o, st);
 }
 
 // ------------------------------------------------------------------------------------------------------------
 // Column sums of a bf16 matrix (bias gradients): out[n] += sum_m X[m][n].  Block = 64 columns x a row slice.
 // ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_colsum_bf16(const act_t* __restrict__ X, int ld, int M, int N, float* __restrict__ out,
-                                                     int rows_per_slice) {
+                                                     int rows_per_slice, float* __restrict__ part) {
     __shared__ float red[32][65];
     const int cg = threadIdx.x & 7, rl = threadIdx.x >> 3;
     const int col = blockIdx.x * 64 + cg * 8;
@@ -552,12 +609,15 @@ __global__ __launch_bounds__(256) void k_colsum_bf16(const act_t* __restrict__ X
 #pragma unroll
         for (int r = 0; r < 32; r++) s += red[r][threadIdx.x];
         const int c = blockIdx.x * 64 + threadIdx.x;
-        if (c < N) __hip_atomic_fetch_add(out + c, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (c < N) {
+            if (gridDim.y == 1) out[c] += s;
+            else part[(size_t)blockIdx.y * N + c] = s;         // folded in a fixed order by k_fold_partials
+        }
     }
 }
 // the same column sums for up to 32 equally shaped matrices in one launch (blockIdx.z = matrix): the mapper backward's per-layer
 // fc1.bias gradients, deferred to the end of the call together with the weight gradients (round 5)
-__global__ __launch_bounds__(256) void k_colsum_bf16_multi(ColsumBatch b, int ld, int M, int N, int rows_per_slice) {
+__global__ __launch_bounds__(256) void k_colsum_bf16_multi(ColsumBatch b, int ld, int M, int N, int rows_per_slice, float* __restrict__ part) {
     __shared__ float red[32][65];
     const act_t* __restrict__ X = b.X[blockIdx.z];
     float* __restrict__ out = b.out[blockIdx.z];
@@ -581,7 +641,10 @@ __global__ __launch_bounds__(256) void k_colsum_bf16_multi(ColsumBatch b, int ld
 #pragma unroll
         for (int r = 0; r < 32; r++) s += red[r][threadIdx.x];
         const int c = blockIdx.x * 64 + threadIdx.x;
-        if (c < N) __hip_atomic_fetch_add(out + c, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (c < N) {
+            if (gridDim.y == 1) out[c] += s;
+            else part[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * N + c] = s;
+        }
     }
 }
 int colsum_bf16_multi(const ColsumBatch& b, int ld, int M, int N, hipStream_t st) {
@@ -591,8 +654,15 @@ int colsum_bf16_multi(const ColsumBatch& b, int ld, int M, int N, hipStream_t st
     int slices = std::max(1, std::min((M + 255) / 256, std::max(1, 1024 / (cb * b.n))));
     const int rps = ((M + slices - 1) / slices + 31) / 32 * 32;
     slices = (M + rps - 1) / rps;
-    hipLaunchKernelGGL(k_colsum_bf16_multi, dim3(cb, slices, b.n), dim3(256), 0, st, b, ld, M, N, rps);
-    return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
+    float* part = slices > 1 ? red_scratch((size_t)b.n * slices * N) : nullptr;
+    if (slices > 1 && !part) return CC_ERR_STATE;
+    hipLaunchKernelGGL(k_colsum_bf16_multi, dim3(cb, slices, b.n), dim3(256), 0, st, b, ld, M, N, rps, part);
+    if (hipGetLastError() != hipSuccess) return CC_ERR_LAUNCH;
+    if (slices == 1) return CC_OK;
+    FoldOut o{};
+    for (int i = 0; i < b.n; i++) o.p[i] = b.out[i];
+    o.m = N; o.k = 1;
+    return fold_partials(part, slices, N, b.n, o, st);
 }
 int colsum_bf16(const act_t* X, int ld, int M, int N, float* out, hipStream_t st) {
     if ((N & 7) || (ld & 7)) return CC_ERR_SHAPE;
@@ -601,8 +671,13 @@ int colsum_bf16(const act_t* X, int ld, int M, int N, float* out, hipStream_t st
     int slices = std::max(1, std::min((M + 255) / 256, 1024 / cb));
     const int rps = ((M + slices - 1) / slices + 31) / 32 * 32;
     slices = (M + rps - 1) / rps;
-    hipLaunchKernelGGL(k_colsum_bf16, dim3(cb, slices), dim3(256), 0, st, X, ld, M, N, out, rps);
-    return CC_OK;
+    float* part = slices > 1 ? red_scratch((size_t)slices * N) : nullptr;
+    if (slices > 1 && !part) return CC_ERR_STATE;
+    hipLaunchKernelGGL(k_colsum_bf16, dim3(cb, slices), dim3(256), 0, st, X, ld, M, N, out, rps, part);
+    if (slices == 1) return CC_OK;
+    FoldOut o{};
+    o.p[0] = out; o.m = N; o.k = 1;
+    return fold_partials(part, slices, N, 1, o, st);
 }
 
 // ------------------------------------------------------------------------------------------------------------
