@@ -124,6 +124,11 @@ SIGNATURES = {
     "cc_layernorm_fwd": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "cc_attention_fwd": (_I, [_I, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "cc_attention_bwd": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "cc_red_scratch_floats": (_L, []),
+    "cc_layernorm_bwd": (_I, [_I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
+    "cc_colsum_bf16": (_I, [_I, _P, _I, _I, _I, _P, _P, _P]),
+    "cc_colsum_multi": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "cc_batch_sum": (_I, [_P, _L, _P, _I, _I, _P, _P]),
     "cc_comm_unique_id": (_I, [_P]),
     "cc_comm_create": (_I, [C.POINTER(_P), _I, _I, _P]),
     "cc_allreduce_bucket": (_I, [_P, _P, _L, _I, _P]),

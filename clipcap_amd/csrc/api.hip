@@ -1142,6 +1142,51 @@ int CC_API(cc_layernorm_fwd)(const float* x, const float* gamma, const float* be
     return ln_fwd(x, D, nullptr, gamma, beta, reinterpret_cast<act_t*>(y), nullptr, mean, rstd, rows, D, S_(stream));
 }
 
+// ---- reduction hooks: the scratch is this call's only; it is cleared on return so that no later call can find a pointer into a buffer
+// the caller may since have freed
+namespace {
+struct RedScope {
+    explicit RedScope(float* p) { red_set_scratch(p); }
+    ~RedScope() { red_set_scratch(nullptr); }
+};
+}  // namespace
+
+int64_t CC_API(cc_red_scratch_floats)(void) { return (int64_t)RED_SCRATCH_FLOATS; }
+
+int CC_API(cc_layernorm_bwd)(const uint16_t* dy, const float* x, int32_t ldx, const int32_t* row_map, const float* mean, const float* rstd,
+                     const float* gamma, const float* dres, float* dx32, uint16_t* dx16, float* dgamma, float* dbeta, float* dcol, int32_t rows,
+                     int32_t D, float* red_ws, void* stream) {
+    // (bf16x3: dx16 would be fp32, or a 3-wide operand image when a GEMM asked for one: no bare hook)
+    if (!dy || !x || !mean || !rstd || !gamma || !dx32 || !dgamma != !dbeta || kX3) return CC_ERR_ARG;
+    RedScope rs(red_ws);
+    return ln_bwd(reinterpret_cast<const act_t*>(dy), x, ldx, row_map, mean, rstd, gamma, dres, dx32, reinterpret_cast<act_t*>(dx16), dgamma,
+                  dbeta, rows, D, S_(stream), dcol);
+}
+
+int CC_API(cc_colsum_bf16)(const uint16_t* X, int32_t ld, int32_t M, int32_t N, float* out, float* red_ws, void* stream) {
+    if (!X || !out || kX3) return CC_ERR_ARG;
+    RedScope rs(red_ws);
+    return colsum_bf16(reinterpret_cast<const act_t*>(X), ld, M, N, out, S_(stream));
+}
+
+int CC_API(cc_colsum_multi)(const uint16_t* const* X_host, float* const* out_host, int32_t n, int32_t ld, int32_t M, int32_t N, float* red_ws,
+                    void* stream) {
+    if (!X_host || !out_host || n < 0 || n > 32 || kX3) return CC_ERR_ARG;
+    ColsumBatch b;
+    for (int i = 0; i < n; i++) {
+        if (!X_host[i] || !out_host[i]) return CC_ERR_ARG;
+        b.add(reinterpret_cast<const act_t*>(X_host[i]), out_host[i]);
+    }
+    RedScope rs(red_ws);
+    return colsum_bf16_multi(b, ld, M, N, S_(stream));
+}
+
+int CC_API(cc_batch_sum)(const float* src, int64_t src_stride, float* dst, int32_t len, int32_t B, float* red_ws, void* stream) {
+    if (!src || !dst || len < 0 || src_stride < len) return CC_ERR_ARG;
+    RedScope rs(red_ws);
+    return batch_sum(src, (size_t)src_stride, dst, len, B, S_(stream));
+}
+
 int CC_API(cc_attention_fwd)(const uint16_t* qkv, int32_t B, int32_t S, int32_t H, int32_t hd, int32_t causal, uint16_t* out, float* lse, void* stream) {
     if (!qkv || !out) return CC_ERR_ARG;
     return attn_fwd(reinterpret_cast<const act_t*>(qkv), B, S, H, hd, causal != 0, reinterpret_cast<act_t*>(out), lse, S_(stream));

@@ -390,6 +390,25 @@ int cc_attention_fwd(int32_t op_dtype, const uint16_t* qkv, int32_t B, int32_t S
 /* o = forward output and delta_ws = fp32 scratch [B*H*S] select the MFMA kernels (hd 64/96/128); NULL -> LDS/VALU kernel */
 int cc_attention_bwd(int32_t op_dtype, const uint16_t* qkv, const uint16_t* dout, const uint16_t* o, const float* lse, float* delta_ws, int32_t B, int32_t S,
                      int32_t H, int32_t hd, int32_t causal, uint16_t* dqkv, void* stream);
+/* The cross-block reductions of the backward passes, one call each (the training step reaches them only inside cc_mapper_bwd*,
+ * cc_gpt2_bwd* and cc_lmhead_ce_bwd).  Test hooks: the product path never calls them.  Every gradient output is ACCUMULATED (+=).
+ * red_ws = device scratch of cc_red_scratch_floats() floats for the per-block partial sums, used by this call only; a shape whose
+ * sum spans several blocks returns CC_ERR_STATE without it and writes nothing.  bf16 / fp16 operands only (CC_OP_BF16X3: CC_ERR_ARG).
+ * cc_layernorm_bwd: LayerNorm backward of `rows` rows of width D.  dy [rows][D] 16-bit, mean / rstd [rows]; x, dres, dx32 fp32 and dx16
+ * 16-bit rows of stride ldx, row r of them at row_map[r] (row_map NULL: at r).  dx32 = dres (nullable) + d LayerNorm input; dx16
+ * (nullable) = its 16-bit copy; dgamma / dbeta [D] (both or neither) += the parameter gradients; dcol [D] (nullable, needs dgamma and
+ * dx16, no row_map) += the column sums of the 16-bit dx16 values. */
+int64_t cc_red_scratch_floats(void);
+int cc_layernorm_bwd(int32_t op_dtype, const uint16_t* dy, const float* x, int32_t ldx, const int32_t* row_map, const float* mean,
+                     const float* rstd, const float* gamma, const float* dres, float* dx32, uint16_t* dx16, float* dgamma, float* dbeta,
+                     float* dcol, int32_t rows, int32_t D, float* red_ws, void* stream);
+/* out[n] += sum over m of X[m][n]  (X 16-bit [M][ld], N % 8 == 0, ld % 8 == 0) */
+int cc_colsum_bf16(int32_t op_dtype, const uint16_t* X, int32_t ld, int32_t M, int32_t N, float* out, float* red_ws, void* stream);
+/* the same for n <= 32 equally shaped matrices in one launch (n > 32: CC_ERR_ARG); X_host[i] / out_host[i] = host arrays of device pointers */
+int cc_colsum_multi(int32_t op_dtype, const uint16_t* const* X_host, float* const* out_host, int32_t n, int32_t ld, int32_t M, int32_t N,
+                    float* red_ws, void* stream);
+/* dst[i] += sum over b < B of src[b * src_stride + i], i < len  (fp32) */
+int cc_batch_sum(const float* src, int64_t src_stride, float* dst, int32_t len, int32_t B, float* red_ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Measurement aid for bench.py's roofline line: brackets every launch of ONE GEMM call site — or, with CC_SITE_ALL_GEMMS, every
