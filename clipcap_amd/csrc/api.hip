@@ -275,6 +275,7 @@ struct Gpt2WS {
     act_t *dx16, *dx16b, *dhf16, *du16, *dxn16, *datt16, *dqkv16;
     float* wg_scratch;
     float* red;        // partial sums of the cross-block reductions (kernels.h red_set_scratch)
+    void* scat;        // full finetune: scratch of the token-indexed scatters into d wte (kernels.h scatter_rows), for the B*cap caption rows
     float* adelta;
     char* x3;          // bf16x3 build: operand-image scratch
     size_t x3_bytes;
@@ -331,9 +332,10 @@ void gpt2_carve(const cc_gpt2_cfg* c, int B, int T, int cap, int mode, void* ws,
         w.dqkv16 = cv.take<act_t>(M * 3 * D * ((kX3 && !full) ? 3 : 2) / 2);
         w.wg_scratch = full ? cv.take<float>(WGRAD_SCRATCH_BYTES / sizeof(float)) : nullptr;
         w.red = full ? cv.take<float>(RED_SCRATCH_FLOATS) : nullptr;      // only a full finetune reduces parameter gradients across blocks
+        w.scat = full ? cv.take<char>(scatter_ws_bytes((int)Mc, (int)D)) : nullptr;
         w.adelta = cv.take<float>((size_t)B * c->H * T);
     } else {
-        w.wg_scratch = nullptr; w.adelta = nullptr; w.red = nullptr;
+        w.wg_scratch = nullptr; w.adelta = nullptr; w.red = nullptr; w.scat = nullptr;
         w.logits16 = nullptr; w.pmax = w.psum = w.tgt_logit = w.lse_row = w.row_loss = nullptr;
         w.cref = w.lmfac = nullptr; w.hfs16 = nullptr;
         w.dx32 = nullptr; w.dx16 = w.dx16b = w.dhf16 = w.du16 = w.dxn16 = w.datt16 = w.dqkv16 = nullptr;
@@ -920,7 +922,9 @@ int CC_API(cc_lmhead_ce_bwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const
         if (ef) {
             CC_TRY(lm_scale_rows(w.hf16, w.lmfac, w.hfs16, D, Mc, st));
             CC_TRY(gemm_wgrad(w.logits16, c->Vp, w.hfs16, D, c->Vp, D, Mc, g32 + o.wte, D, w.wg_scratch, st));
-            CC_TRY(lm_wgrad_onehot(w.hf16, w.lmfac, w.target, g32 + o.wte, D, Mc, st));
+            ScatterSrc oh;          // the one-hot term: d wte[target] -= w hf, rows with w == 0 left out
+            oh.ids32 = w.target; oh.act = w.hf16; oh.fac = w.lmfac;
+            CC_TRY(scatter_rows(oh, Mc, D, c->Vp, g32 + o.wte, w.scat, st));
         } else {
             CC_TRY(gemm_wgrad(w.logits16, c->Vp, w.hf16, D, c->Vp, D, Mc, g32 + o.wte, D, w.wg_scratch, st));
         }
@@ -1062,8 +1066,16 @@ int CC_API(cc_gpt2_bwd_range)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, cons
     if (l_lo > 0) return CC_OK;
     CC_TRY(dropout_f32(w.dx32, (size_t)M * D, make_drop(s->p_embd, s->drop_seed, DROP_EMBD, 0), st));   // d(inputs + wpe)
     if (s->L > 0) CC_TRY(copy_rows(w.dx32, (size_t)s->T * D, dprefix, (size_t)s->L * D, s->L * D, s->B, st));
-    if (full)
-        CC_TRY(embed_bwd(w.dx32, reinterpret_cast<const long long*>(tokens), s->cap, g32 + o.wte, g32 + o.wpe, s->B, s->L, s->T, D, st));
+    if (full) {     // d wte[max(tok, 0)] += d x0[b, L + c] (the caption rows, fixed-order scatter);  d wpe[t] += sum_b d x0[b, t]
+        if (tokens) {
+            ScatterSrc e;
+            e.ids64 = reinterpret_cast<const long long*>(tokens);
+            e.ids_ld = s->cap;
+            e.f32 = w.dx32 + (size_t)s->L * D; e.rpb = s->T - s->L; e.bstride = (size_t)s->T * D;
+            CC_TRY(scatter_rows(e, s->B * (s->T - s->L), D, c->Vp, g32 + o.wte, w.scat, st));
+        }
+        CC_TRY(batch_sum(w.dx32, (size_t)s->T * D, g32 + o.wpe, s->T * D, s->B, st));
+    }
     return CC_OK;
 }
 

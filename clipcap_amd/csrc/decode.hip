@@ -448,7 +448,8 @@ __global__ void k_embed_tokens(const float* __restrict__ wte, const int* __restr
     }
 }
 
-// Gradient of the gather: dwte[tok[r], :] += dout[r, :] (fp32 atomics; rows that share an id accumulate).  Ids clamped like the forward's.
+// Gradient of the gather: dwte[tok[r], :] += dout[r, :] (fp32 atomics; rows that share an id accumulate in arrival order: the
+// non-deterministic form, kept for cc_embed_tokens_bwd; cc_embed_tokens_bwd_ws runs kernels.h scatter_rows).  Ids clamped like the forward's.
 __global__ void k_embed_tokens_bwd(const float* __restrict__ dout, const int* __restrict__ tok, float* __restrict__ dwte, int R, int D, int rows) {
     const size_t total = (size_t)R * D;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -1436,6 +1437,18 @@ int CC_API(cc_embed_tokens_bwd)(const cc_gpt2_cfg* c, int32_t R, const float* do
     const size_t total = (size_t)R * c->D;
     hipLaunchKernelGGL(k_embed_tokens_bwd, dim3((int)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, S_(stream), dout, tokens, dwte, R, c->D, c->Vp);
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
+}
+
+int CC_API(cc_embed_tokens_bwd_ws)(const cc_gpt2_cfg* c, int32_t R, const float* dout, const int32_t* tokens, float* dwte, void* ws, void* stream) {
+    if (!cfg_ok(c) || R <= 0 || !dout || !tokens || !dwte) return CC_ERR_ARG;
+    ScatterSrc e;
+    e.ids32 = tokens; e.f32 = dout; e.rpb = 1; e.bstride = (size_t)c->D;
+    return scatter_rows(e, R, c->D, c->Vp, dwte, ws, S_(stream));
+}
+
+int64_t CC_API(cc_embed_tokens_bwd_ws_bytes)(const cc_gpt2_cfg* c, int32_t R) {
+    if (!cfg_ok(c) || R <= 0) return CC_ERR_ARG;
+    return (int64_t)scatter_ws_bytes(R, c->D);
 }
 
 int CC_API(cc_beam_advance)(const cc_gpt2_cfg* c, int32_t R, int32_t beam, const float* w32, const int32_t* next_tokens, const int32_t* src_rows,

@@ -57,7 +57,30 @@ int dropout_mask_u8(unsigned char* out, size_t n, Drop drop, hipStream_t st);   
 int embed_concat(const float* prefix, const long long* tokens, int cap, const float* wte, const float* wpe, float* x0, int B, int L,
                  int T, int D, int pos0, hipStream_t st);
 int f32_to_op16_pad(const float* src, long long lds, int V, act_t* dst, int ldd, int M, hipStream_t st);
-int embed_bwd(const float* dx0, const long long* tokens, int cap, float* dwte, float* dwpe, int B, int L, int T, int D, hipStream_t st);
+// Deterministic token-indexed scatter-add (no atomics): dst[id(r)][:] += value(r)[:] for rows r < R, bit for bit the same from run to
+// run.  Row values: f32 set: value(r)[d] = f32[(r / rpb) * bstride + (r % rpb) * D + d];  act set: value(r)[d] = fl(-fac[2r+1] * act[r*D+d])
+// (the one-hot term of the exponential-form lm_head), rows with fac[2r+1] == 0 left out of every list.  Ids from ids32 or ids64,
+// id(r) = min(max(ids[(r / rpb) * ids_ld + r % rpb], 0), Vp - 1).  The order, exactly (a float32 emulation reproduces it bit for bit):
+//   * the list of id i = its rows in ascending row order; its k-th chunk = list entries [k*SCATTER_CHUNK, (k+1)*SCATTER_CHUNK);
+//   * a chunk's sum, per column: s = value(first row); s = s + value(next row) for each further row in list order (fp32, no fused
+//     multiply-add with the products above);
+//   * a list of one chunk: dst[i] = dst[i] + s_0;  of nk > 1 chunks: t = s_0; t = t + s_k for k = 1 .. nk-1; dst[i] = dst[i] + t.
+// Ids without rows are untouched.  ws: scatter_ws_bytes(R, D) bytes of device scratch for this call (the inverted index and the chunk
+// partials, rebuilt by every call; nothing survives it); without it, CC_ERR_STATE.  D % 4 == 0.
+constexpr int SCATTER_CHUNK = 512;
+constexpr unsigned SC_SKIP = 0xffffffffu;       // id field of a left-out row's key: sorted after every list, summed by none
+struct ScatterSrc {
+    const int* ids32 = nullptr;
+    const long long* ids64 = nullptr;
+    const float* f32 = nullptr;
+    size_t bstride = 0;
+    int rpb = 1;
+    size_t ids_ld = 1;
+    const act_t* act = nullptr;
+    const float* fac = nullptr;
+};
+size_t scatter_ws_bytes(int R, int D);
+int scatter_rows(const ScatterSrc& s, int R, int D, int Vp, float* dst, void* ws, hipStream_t st);
 
 int ce_rows(const float* pmax, const float* psum, int npart, const int* target, const float* tgt_logit, float* lse, float* row_loss,
             float* stats, int M, hipStream_t st);
@@ -72,12 +95,11 @@ int ce_targets(const long long* tokens, int* target, int* row_map, int B, int ca
 //   lm_tgt_ref   cref[m] = hf[m] . wte[target[m]]  (16-bit operands, fp32 accumulate): the reference shift of row m
 //   lm_rowfac    fac[m] = {r, w}: w = (target[m] != 0) * loss_scale / max(denom, 1), r = exp(cref[m] - lse[m]) * w
 //   lm_dgrad_fix dhf[m][:] = r dhf[m][:] - w wte[target[m]][:]  (the path whose GEMM has no finishing pass of its own)
-//   lm_scale_rows out[m][:] = r hf[m][:] (weight-gradient operand);  lm_wgrad_onehot dwte[target[m]][:] -= w hf[m][:]
+//   lm_scale_rows out[m][:] = r hf[m][:] (weight-gradient operand);  the one-hot term dwte[target[m]][:] -= w hf[m][:] is scatter_rows' act form
 int lm_tgt_ref(const act_t* hf, const op16_t* wte, int D, const int* target, float* cref, int M, hipStream_t st);
 int lm_rowfac(const float* cref, const float* lse, const int* target, const float* denom, const float* loss_scale, float* fac, int M, hipStream_t st);
 int lm_dgrad_fix(act_t* dhf, const float* fac, const int* target, const op16_t* wte, int D, int M, hipStream_t st);
 int lm_scale_rows(const act_t* hf, const float* fac, act_t* out, int D, int M, hipStream_t st);
-int lm_wgrad_onehot(const act_t* hf, const float* fac, const int* target, float* dwte, int D, int M, hipStream_t st);
 
 int adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, float wd, int step, float gscale,
           const float* loss_scale, const float* found_inf, hipStream_t st, op16_t* w16 = nullptr);   // w16: also store the 16-bit copy of the updated parameters

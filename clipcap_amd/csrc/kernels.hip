@@ -2826,22 +2826,6 @@ int embed_concat(const float* prefix, const long long* tokens, int cap, const fl
     return CC_OK;
 }
 
-// Embedding-gradient scatter (full finetune): dwte[tok[b,c],:] += dx0[b,L+c,:] ; dwpe[t,:] += sum_b dx0[b,t,:]
-__global__ void k_embed_bwd(const float* __restrict__ dx0, const long long* __restrict__ tokens, int cap, float* __restrict__ dwte,
-                            float* __restrict__ dwpe, int B, int L, int T, int D) {
-    const size_t total = (size_t)B * T * D;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int d = (int)(i % D);
-        const int t = (int)((i / D) % T), b = (int)(i / ((size_t)D * T));
-        const float g = dx0[i];
-        __hip_atomic_fetch_add(dwpe + (size_t)t * D + d, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (t >= L && tokens) {
-            long long id = tokens[(size_t)b * cap + (t - L)];
-            if (id < 0) id = 0;
-            __hip_atomic_fetch_add(dwte + (size_t)id * D + d, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
 // dst[r][c] = op16(src[r][c]) for c < V, 0 for V <= c < ldd (gradient of caller-visible fp32 logits -> the GEMM operand layout)
 __global__ __launch_bounds__(256) void k_f32_to_op16_pad(const float* __restrict__ src, long long lds, int V, act_t* __restrict__ dst, int ldd,
                                                          int M) {
@@ -2858,12 +2842,232 @@ int f32_to_op16_pad(const float* src, long long lds, int V, act_t* dst, int ldd,
     hipLaunchKernelGGL(k_f32_to_op16_pad, dim3((int)std::min<size_t>((total + 255) / 256, 8192)), dim3(256), 0, st, src, lds, V, dst, ldd, M);
     return CC_OK;
 }
-int embed_bwd(const float* dx0, const long long* tokens, int cap, float* dwte, float* dwpe, int B, int L, int T, int D, hipStream_t st) {
-    const size_t total = (size_t)B * T * D;
-    if (!total) return CC_OK;
-    hipLaunchKernelGGL(k_embed_bwd, dim3((int)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, st, dx0, tokens, cap, dwte,
-                       dwpe, B, L, T, D);
-    return CC_OK;
+// ---- deterministic token-indexed scatter-add (kernels.h scatter_rows, where the order is specified) ----
+// Index: k_sc_sort_tile sorts the keys (id << 32 | row) of SC_TILE rows per workgroup in LDS (bitonic); k_sc_rank gives every key its place
+// in the whole sorted array, the number of keys below it summed over the tiles (binary searches in LDS; the keys are unique), and the
+// start and length of its id's list the same way; k_sc_compact (one workgroup) lists the chunk heads and the multi-chunk lists.  Sum:
+// k_sc_sum, one wave per (chunk, 256 columns), each lane walking its 4 columns down the chunk in list order; k_sc_fold adds a multi-chunk
+// list's partials in chunk order onto its row.  No atomics: every output element and every partial has exactly one writer.
+namespace {
+constexpr int SC_TILE = 2048;        // keys per LDS tile of the index sort
+typedef unsigned long long sc_key;
+struct ScatterWS {
+    sc_key *tkeys, *skeys;
+    int2* info;       // per sorted position: {start, length} of its id's list
+    int *heads, *mstarts, *cnt;
+    float* part;
+    size_t bytes;
+};
+ScatterWS sc_carve(void* ws, int R, int D) {
+    ScatterWS w{};
+    char* base = static_cast<char*>(ws);
+    size_t off = 0;
+    auto take = [&](size_t n) { off = (off + 255) & ~size_t(255); char* r = base ? base + off : nullptr; off += n; return r; };
+    w.tkeys = reinterpret_cast<sc_key*>(take((size_t)R * sizeof(sc_key)));
+    w.skeys = reinterpret_cast<sc_key*>(take((size_t)R * sizeof(sc_key)));
+    w.info = reinterpret_cast<int2*>(take((size_t)R * sizeof(int2)));
+    w.heads = reinterpret_cast<int*>(take((size_t)R * sizeof(int)));
+    w.mstarts = reinterpret_cast<int*>(take((size_t)(R / (SCATTER_CHUNK + 1) + 1) * sizeof(int)));
+    w.cnt = reinterpret_cast<int*>(take(4 * sizeof(int)));
+    // a list of n > CHUNK rows starting at sorted position s owns partial slots 2s/CHUNK + k, k < ceil(n/CHUNK): disjoint between lists
+    // (floor(2(s+n)/C) >= floor(2s/C) + floor(2n/C) >= floor(2s/C) + ceil(n/C)) and below 2R/CHUNK
+    w.part = reinterpret_cast<float*>(take((size_t)(2 * (size_t)R / SCATTER_CHUNK) * D * sizeof(float)));
+    w.bytes = (off + 255) & ~size_t(255);
+    return w;
+}
+
+template <bool ACT>
+__device__ __forceinline__ void sc_row(const ScatterSrc& s, unsigned r, int D, int d0, float (&v)[4]) {
+#pragma clang fp contract(off)
+    if (ACT) {
+        const float w = -s.fac[2 * (size_t)r + 1];
+        const act_t* h = s.act + (size_t)r * D + d0;
+#pragma unroll
+        for (int e = 0; e < 4; e++) v[e] = w * act2f(h[e]);
+    } else {
+        const float* f = s.f32 + (size_t)(r / s.rpb) * s.bstride + (size_t)(r % s.rpb) * D + d0;
+#pragma unroll
+        for (int e = 0; e < 4; e++) v[e] = f[e];
+    }
+}
+
+__global__ __launch_bounds__(1024) void k_sc_sort_tile(ScatterSrc s, int R, int Vp, int n, sc_key* __restrict__ tkeys) {
+    __shared__ sc_key k[SC_TILE];
+    const int base = blockIdx.x * SC_TILE;
+    for (int i = threadIdx.x; i < n; i += 1024) {
+        const int r = base + i;
+        sc_key key = ~0ull;                                  // padding: above every real key, never stored
+        if (r < R) {
+            const size_t ir = (size_t)(r / s.rpb) * s.ids_ld + r % s.rpb;
+            long long id = s.ids64 ? s.ids64[ir] : (long long)s.ids32[ir];
+            id = id < 0 ? 0 : (id >= Vp ? Vp - 1 : id);
+            unsigned hi = (unsigned)id;
+            if (s.fac && s.fac[2 * (size_t)r + 1] == 0.f) hi = SC_SKIP;
+            key = (sc_key)hi << 32 | (unsigned)r;
+        }
+        k[i] = key;
+    }
+    __syncthreads();
+    for (int size = 2; size <= n; size <<= 1)
+        for (int j = size >> 1; j > 0; j >>= 1) {
+            for (int i = threadIdx.x; i < n; i += 1024) {
+                const int p = i ^ j;
+                if (p > i) {
+                    const sc_key a = k[i], b = k[p];
+                    if ((a > b) == ((i & size) == 0)) { k[i] = b; k[p] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    for (int i = threadIdx.x; i < n && base + i < R; i += 1024) tkeys[base + i] = k[i];
+}
+
+__global__ __launch_bounds__(256) void k_sc_rank(const sc_key* __restrict__ tkeys, int R, sc_key* __restrict__ skeys, int2* __restrict__ info) {
+    __shared__ sc_key t[SC_TILE];
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    const sc_key key = p < R ? tkeys[p] : ~0ull;
+    const unsigned hi = (unsigned)(key >> 32);
+    const sc_key lo_key = (sc_key)hi << 32, hi_key = hi == SC_SKIP ? ~0ull : (sc_key)(hi + 1) << 32;
+    int pos = 0, ls = 0, le = 0;
+    for (int base = 0; base < R; base += SC_TILE) {
+        const int n = min(SC_TILE, R - base);
+        __syncthreads();
+        for (int i = threadIdx.x; i < n; i += 256) t[i] = tkeys[base + i];
+        __syncthreads();
+        int a = 0, b = 0, c = 0;                             // counts of tile keys below key / lo_key / hi_key, three searches in step
+        for (int step = SC_TILE; step > 0; step >>= 1) {
+            if (a + step <= n && t[a + step - 1] < key) a += step;
+            if (b + step <= n && t[b + step - 1] < lo_key) b += step;
+            if (c + step <= n && t[c + step - 1] < hi_key) c += step;
+        }
+        pos += a; ls += b; le += c;
+    }
+    if (p >= R) return;
+    skeys[pos] = key;
+    info[pos] = make_int2(ls, hi == SC_SKIP ? 0 : le - ls);
+}
+
+// one workgroup: thread i takes sorted positions [i*span, (i+1)*span); counts, an exclusive scan of the counts, then the lists in order
+__global__ __launch_bounds__(1024) void k_sc_compact(const sc_key* __restrict__ skeys, const int2* __restrict__ info, int R, int* __restrict__ heads,
+                                                     int* __restrict__ mstarts, int* __restrict__ cnt) {
+    __shared__ int sh[1024], sm[1024];
+    const int tid = threadIdx.x, span = (R + 1023) / 1024, a = min(R, tid * span), b = min(R, a + span);
+    int nh = 0, nm = 0;
+    for (int p = a; p < b; p++) {
+        const int2 li = info[p];
+        const int off = p - li.x;
+        if ((unsigned)(skeys[p] >> 32) == SC_SKIP || off % SCATTER_CHUNK) continue;
+        nh++;
+        nm += off == 0 && li.y > SCATTER_CHUNK;
+    }
+    sh[tid] = nh; sm[tid] = nm;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const int x = tid >= d ? sh[tid - d] : 0, y = tid >= d ? sm[tid - d] : 0;
+        __syncthreads();
+        sh[tid] += x; sm[tid] += y;
+        __syncthreads();
+    }
+    int oh = sh[tid] - nh, om = sm[tid] - nm;
+    if (tid == 1023) { cnt[0] = sh[tid]; cnt[1] = sm[tid]; }
+    for (int p = a; p < b; p++) {
+        const int2 li = info[p];
+        const int off = p - li.x;
+        if ((unsigned)(skeys[p] >> 32) == SC_SKIP || off % SCATTER_CHUNK) continue;
+        heads[oh++] = p;
+        if (off == 0 && li.y > SCATTER_CHUNK) mstarts[om++] = p;
+    }
+}
+
+template <bool ACT>
+__global__ __launch_bounds__(256) void k_sc_sum(ScatterSrc s, const sc_key* __restrict__ skeys, const int2* __restrict__ info,
+                                                const int* __restrict__ heads, const int* __restrict__ cnt, int D, int ncb,
+                                                float* __restrict__ dst, float* __restrict__ part) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int items = cnt[0] * ncb;
+    for (int it = blockIdx.x * 4 + (threadIdx.x >> 6); it < items; it += gridDim.x * 4) {
+        const int h = it / ncb, d0 = (it % ncb) * 256 + lane * 4;
+        const int p = heads[h];
+        const int2 li = info[p];
+        const int end = min(p + SCATTER_CHUNK, li.x + li.y);
+        if (d0 >= D) continue;
+        float acc[4];
+        sc_row<ACT>(s, (unsigned)skeys[p], D, d0, acc);
+        int q = p + 1;
+        for (; q + 3 < end; q += 4) {                       // four rows' loads in flight, added in list order
+            float v0[4], v1[4], v2[4], v3[4];
+            sc_row<ACT>(s, (unsigned)skeys[q], D, d0, v0);
+            sc_row<ACT>(s, (unsigned)skeys[q + 1], D, d0, v1);
+            sc_row<ACT>(s, (unsigned)skeys[q + 2], D, d0, v2);
+            sc_row<ACT>(s, (unsigned)skeys[q + 3], D, d0, v3);
+#pragma unroll
+            for (int e = 0; e < 4; e++) acc[e] = (((acc[e] + v0[e]) + v1[e]) + v2[e]) + v3[e];
+        }
+        for (; q < end; q++) {
+            float v[4];
+            sc_row<ACT>(s, (unsigned)skeys[q], D, d0, v);
+#pragma unroll
+            for (int e = 0; e < 4; e++) acc[e] += v[e];
+        }
+        float* o;
+        if (li.y <= SCATTER_CHUNK) o = dst + (size_t)(skeys[p] >> 32) * D + d0;
+        else o = part + (size_t)(2 * (size_t)li.x / SCATTER_CHUNK + (p - li.x) / SCATTER_CHUNK) * D + d0;
+        if (li.y <= SCATTER_CHUNK) {
+#pragma unroll
+            for (int e = 0; e < 4; e++) o[e] = o[e] + acc[e];
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; e++) o[e] = acc[e];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_sc_fold(const sc_key* __restrict__ skeys, const int2* __restrict__ info, const int* __restrict__ mstarts,
+                                                 const int* __restrict__ cnt, int D, int ncb, const float* __restrict__ part, float* __restrict__ dst) {
+    const int lane = threadIdx.x & 63;
+    const int items = cnt[1] * ncb;
+    for (int it = blockIdx.x * 4 + (threadIdx.x >> 6); it < items; it += gridDim.x * 4) {
+        const int m = it / ncb, d0 = (it % ncb) * 256 + lane * 4;
+        if (d0 >= D) continue;
+        const int p = mstarts[m];
+        const int n = info[p].y, nk = (n + SCATTER_CHUNK - 1) / SCATTER_CHUNK;
+        const float* src = part + (size_t)(2 * (size_t)p / SCATTER_CHUNK) * D + d0;
+        float t[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++) t[e] = src[e];
+        for (int k = 1; k < nk; k++)
+#pragma unroll
+            for (int e = 0; e < 4; e++) t[e] += src[(size_t)k * D + e];
+        float* o = dst + (size_t)(skeys[p] >> 32) * D + d0;
+#pragma unroll
+        for (int e = 0; e < 4; e++) o[e] = o[e] + t[e];
+    }
+}
+}  // namespace
+
+size_t scatter_ws_bytes(int R, int D) { return R > 0 ? sc_carve(nullptr, R, D).bytes : 0; }
+
+int scatter_rows(const ScatterSrc& s, int R, int D, int Vp, float* dst, void* ws, hipStream_t st) {
+    if (R < 0 || D <= 0 || (D & 3) || Vp <= 0 || (!s.ids32 && !s.ids64) || (!s.f32 && !(s.act && s.fac)) || s.rpb <= 0) return CC_ERR_ARG;
+    if (R == 0) return CC_OK;
+    if (!ws) return CC_ERR_STATE;
+    const ScatterWS w = sc_carve(ws, R, D);
+    const int nt = (R + SC_TILE - 1) / SC_TILE;
+    int n = SC_TILE;
+    if (nt == 1) for (n = 1; n < R; n <<= 1) {}
+    hipLaunchKernelGGL(k_sc_sort_tile, dim3(nt), dim3(1024), 0, st, s, R, Vp, n, w.tkeys);
+    hipLaunchKernelGGL(k_sc_rank, dim3((R + 255) / 256), dim3(256), 0, st, w.tkeys, R, w.skeys, w.info);
+    hipLaunchKernelGGL(k_sc_compact, dim3(1), dim3(1024), 0, st, w.skeys, w.info, R, w.heads, w.mstarts, w.cnt);
+    const int ncb = (D + 255) / 256;
+    const int sum_blocks = (int)std::min<size_t>(((size_t)R * ncb + 3) / 4, 4096);
+    if (s.act) hipLaunchKernelGGL(k_sc_sum<true>, dim3(sum_blocks), dim3(256), 0, st, s, w.skeys, w.info, w.heads, w.cnt, D, ncb, dst, w.part);
+    else hipLaunchKernelGGL(k_sc_sum<false>, dim3(sum_blocks), dim3(256), 0, st, s, w.skeys, w.info, w.heads, w.cnt, D, ncb, dst, w.part);
+    if (R > SCATTER_CHUNK) {
+        const int fold_blocks = (int)std::min<size_t>(((size_t)(R / (SCATTER_CHUNK + 1) + 1) * ncb + 3) / 4, 1024);
+        hipLaunchKernelGGL(k_sc_fold, dim3(fold_blocks), dim3(256), 0, st, w.skeys, w.info, w.mstarts, w.cnt, D, ncb, w.part, dst);
+    }
+    return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -3031,7 +3235,7 @@ int lm_rowfac(const float* cref, const float* lse, const int* target, const floa
     hipLaunchKernelGGL(k_lm_rowfac, dim3((M + 255) / 256), dim3(256), 0, st, cref, lse, target, denom, loss_scale, fac, M);
     return CC_OK;
 }
-// MODE 0: dhf = r dhf - w wte[t];  1: out = r hf;  2: dwte[t] -= w hf (fp32 atomics: several rows may share a target)
+// MODE 0: dhf = r dhf - w wte[t];  1: out = r hf
 template <int MODE>
 __global__ __launch_bounds__(256) void k_lm_rows(act_t* __restrict__ io, const act_t* __restrict__ hf, const float* __restrict__ fac,
                                                  const int* __restrict__ target, const op16_t* __restrict__ wte, float* __restrict__ dwte, int D, int M) {
@@ -3052,17 +3256,11 @@ __global__ __launch_bounds__(256) void k_lm_rows(act_t* __restrict__ io, const a
 #pragma unroll
             for (int e = 0; e < 8; e++) v[e] = r * v[e] - w * b[e];
             act_st8(io + (size_t)row * D + c, v);
-        } else if (MODE == 1) {
+        } else {
             act_ld8(hf + (size_t)row * D + c, v);
 #pragma unroll
             for (int e = 0; e < 8; e++) v[e] *= r;
             act_st8(io + (size_t)row * D + c, v);
-        } else {
-            if (w == 0.f) continue;
-            act_ld8(hf + (size_t)row * D + c, v);
-            float* dst = dwte + (size_t)target[row] * D + c;
-#pragma unroll
-            for (int e = 0; e < 8; e++) __hip_atomic_fetch_add(dst + e, -w * v[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
@@ -3079,9 +3277,6 @@ int lm_dgrad_fix(act_t* dhf, const float* fac, const int* target, const op16_t* 
 }
 int lm_scale_rows(const act_t* hf, const float* fac, act_t* out, int D, int M, hipStream_t st) {
     return lm_rows_launch<1>(out, hf, fac, nullptr, nullptr, nullptr, D, M, st);
-}
-int lm_wgrad_onehot(const act_t* hf, const float* fac, const int* target, float* dwte, int D, int M, hipStream_t st) {
-    return lm_rows_launch<2>(nullptr, hf, fac, target, nullptr, dwte, D, M, st);
 }
 
 // Targets of the caption rows: target[b*cap + c] = max(tokens[b,c], 0) (model.py:103-104); row_map[b*cap+c] = b*T + L-1+c.

@@ -743,10 +743,20 @@ def embed_tokens(gpt2: "Gpt2Engine", tokens: torch.Tensor, out: torch.Tensor) ->
 
 def embed_tokens_bwd(gpt2: "Gpt2Engine", tokens: torch.Tensor, dout: torch.Tensor) -> torch.Tensor:
     """fp32 (V, D) gradient of ``embed_tokens`` with respect to wte: rows of ``dout`` (R, D) scattered by int32 ``tokens`` (R,), rows that
-    share an id accumulate (cc_embed_tokens_bwd; fp32 atomics, like torch's embedding backward on a GPU)."""
+    share an id accumulate in a fixed order, so the result is the same bit for bit from run to run (cc_embed_tokens_bwd_ws; no atomics).
+    Its index scratch is kept on the engine and grown when a larger R arrives."""
     D, V, Vp = gpt2.dims["D"], gpt2.dims["V"], gpt2.dims["Vp"]
+    L = _lib.lib()
+    R = tokens.numel()
     dw = torch.zeros(Vp, D, dtype=torch.float32, device=gpt2.arena.device)
-    check(_lib.lib().cc_embed_tokens_bwd(C.byref(gpt2.cfg), tokens.numel(), _p(dout), _p(tokens), _p(dw), _stream(gpt2.arena.device)), "cc_embed_tokens_bwd")
+    if R == 0:
+        return dw[:V]
+    need = L.cc_embed_tokens_bwd_ws_bytes(C.byref(gpt2.cfg), R)
+    check(need, "cc_embed_tokens_bwd_ws_bytes")
+    ws = getattr(gpt2, "_embed_bwd_ws", None)
+    if ws is None or ws.numel() < need or ws.device != dw.device:
+        ws = gpt2._embed_bwd_ws = torch.empty(need, dtype=torch.uint8, device=dw.device)
+    check(L.cc_embed_tokens_bwd_ws(C.byref(gpt2.cfg), R, _p(dout), _p(tokens), _p(dw), _p(ws), _stream(gpt2.arena.device)), "cc_embed_tokens_bwd_ws")
     return dw[:V]
 
 

@@ -53,8 +53,8 @@ class _LogitsFn(torch.autograd.Function):
 
 
 class _EmbedFn(torch.autograd.Function):
-    """wte[ids] with its gradient, both on the library's kernels (cc_embed_tokens / cc_embed_tokens_bwd): the autograd path of a full
-    finetune driven through Module.forward (reference model.py:44 ``get_input_embeddings()(tokens)``)."""
+    """wte[ids] with its gradient, both on the library's kernels (cc_embed_tokens / cc_embed_tokens_bwd_ws, a fixed-order scatter): the
+    autograd path of a full finetune driven through Module.forward (reference model.py:44 ``get_input_embeddings()(tokens)``)."""
 
     @staticmethod
     def forward(ctx, weight, ids, engine):

@@ -61,7 +61,8 @@ extern "C" {
  * would be written out of bounds, so clipcap_amd/_lib.py refuses a library whose version differs.  Entry points ADDED since 2:
  * cc_adamw_step_cast, cc_mapper_transpose_weights, cc_gpt2_transpose_weights, cc_comm_count, cc_decode_part_floats, cc_decode_fwd_p,
  * cc_beam_step_p; since 3: cc_decode_fwd_g, cc_decode_ws_check, cc_decode_mode, cc_grad_wire_pack, cc_grad_wire_unpack,
- * cc_sample_step_lp, cc_broadcast_bucket, cc_reduce_bucket, cc_embed_tokens_bwd; operand mode ADDED: CC_OP_BF16X3.  Round 6 (still 3): the default-off decode experiments
+ * cc_sample_step_lp, cc_broadcast_bucket, cc_reduce_bucket, cc_embed_tokens_bwd, cc_embed_tokens_bwd_ws,
+ * cc_embed_tokens_bwd_ws_bytes; operand mode ADDED: CC_OP_BF16X3.  Round 6 (still 3): the default-off decode experiments
  * (cc_decode_image*, cc_decode_xt_image*, cc_decode_fwd_x, cc_decode_ws_check, cc_decode_last_path) moved to include/clipcap_hip_lab.h —
  * the lab library exports them, the product library does not. */
 #define CC_ABI_VERSION 3
@@ -256,9 +257,17 @@ int cc_beam_step_p(int32_t S, int32_t beam, int32_t V, const float* logits, int6
 int64_t cc_beam_ws_bytes(int32_t S, int32_t beam, int32_t V);
 /* gathers wte rows for next tokens: out fp32 [R, D] (base.py:117) */
 int cc_embed_tokens(const cc_gpt2_cfg* cfg, int32_t R, const float* w32, const int32_t* tokens, float* out, void* stream);
-/* its gradient: dwte fp32 [Vp, D] += scatter of dout fp32 [R, D] by tokens (rows sharing an id accumulate; fp32 atomics) — what autograd runs
- * for `language_model.get_input_embeddings()(tokens)` in a full finetune driven through Module.forward (clipcap/model/model.py:44) */
+/* its gradient: dwte fp32 [Vp, D] += scatter of dout fp32 [R, D] by tokens (rows sharing an id accumulate).  The non-deterministic form:
+ * fp32 atomics, so rows that share an id add in arrival order.  cc_embed_tokens_bwd_ws is the reproducible one. */
 int cc_embed_tokens_bwd(const cc_gpt2_cfg* cfg, int32_t R, const float* dout, const int32_t* tokens, float* dwte, void* stream);
+/* the same gradient, bit for bit the same from run to run (no atomics) — what autograd runs for `language_model.get_input_embeddings()(tokens)`
+ * in a full finetune driven through Module.forward (clipcap/model/model.py:44).  Ids clamped to [0, Vp-1] like cc_embed_tokens'.  Order:
+ * the rows of one id in ascending row order, cut into chunks of 512 rows; each chunk summed in fp32 in that order, starting from its first
+ * row; a one-chunk id: dwte[id] = dwte[id] + sum; otherwise the chunk sums are added in chunk order, starting from the first, and
+ * dwte[id] = dwte[id] + that total.  ws: device scratch of cc_embed_tokens_bwd_ws_bytes(cfg, R) bytes, used by this call only
+ * (NULL: CC_ERR_STATE).  cfg->D % 4 == 0. */
+int cc_embed_tokens_bwd_ws(const cc_gpt2_cfg* cfg, int32_t R, const float* dout, const int32_t* tokens, float* dwte, void* ws, void* stream);
+int64_t cc_embed_tokens_bwd_ws_bytes(const cc_gpt2_cfg* cfg, int32_t R);
 /* Everything between two beam steps in one launch (base.py:104-117): row r continues row g = (r / beam) * beam + src_rows[r] of its beam
  * group (src_rows NULL: g = r).  x_out fp32 [R, D] = wte[next_tokens[r]] (w32 points at wte);  row_map_out[r][j] = row_map_in[g][j] for
  * j < pos, r for the positions still to come (tables int32 [R][ctx_max], see cc_decode_fwd; NULL = skip);  tokens_out[r][:step] =
