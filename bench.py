@@ -9,6 +9,10 @@ A "step" = one pass of the hot path over one batch of synthetic (embedding, capt
 mapper forward -> [prefix ; tokens] -> GPT-2 forward -> fused lm_head + cross-entropy -> backward through GPT-2 (dgrad;
 +wgrad when --config 3) -> mapper backward -> (N>1: RCCL all-reduce of the gradient arena) -> fused AdamW + LR schedule.
 Nothing is skipped inside the timed region.  Rank 0 prints ONE JSON line (see DESIGN.md §Measurement for every field).
+
+A plain run sets up, warms up, times the --steps steps, writes --dump-outputs and prints the headline line.  --full adds everything else
+the line can carry: the exposed all-reduce pass (N > 1), the event-bracketed roofline passes, the sub-benches (mapper, decode, configs[2] /
+[3], e2e input path, the other precisions) and the CPU baselines (--no-roofline-pass / --no-sub-benches / --no-cpu-baseline drop parts of it).
 """
 import argparse
 import ctypes as C
@@ -579,7 +583,7 @@ def e2e_bench(args, device, max_tokens=None):
         warm += -(args.steps + warm) % 4
         rows = (args.steps + warm) * B
     else:
-        # the default line's sub-benchmark: one epoch over >= 200 k rows, timed after 50 steps
+        # the --full line's sub-benchmark: one epoch over >= 200 k rows, timed after 50 steps
         rows = max(204800, 60 * B) // (4 * B) * (4 * B)
         warm = None
     out = {}
@@ -692,15 +696,19 @@ def main():
                          "auto = bf16 for frozen-LM bf16 / fp16 runs (41.7 M mapper gradients that only the short mapper backward can hide; "
                          "tests/test_ddp_gloo.py: 8e-3 on the gradients, loss trajectories equal to 2e-3 over 20 steps), fp32 for a full finetune "
                          "and for the fp32-parity mode (--precision 32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, also run the extras of the line: the N>1 pass without the gradient all-reduce "
+                         "(allreduce_exposed_ms), the event-bracketed roofline passes, the N=1 sub-benches and the CPU baselines (minutes); "
+                         "without it the run times the --steps steps and prints the headline line only")
     ap.add_argument("--no-roofline-pass", action="store_true",
-                    help="skip the 25 extra event-bracketed steps (use under rocprofv3 --pmc, where every dispatch is serialised)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sub-benches", action="store_true", help="skip the mapper / decode / configs[2,3] sub-objects of the default N=1 line")
+                    help="--full: skip the 25 extra event-bracketed steps (use under rocprofv3 --pmc, where every dispatch is serialised)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-sub-benches", action="store_true", help="--full: skip the mapper / decode / configs[2,3] sub-objects of the N=1 line")
     ap.add_argument("--no-dropout", action="store_true", help="configs 3/4: run the full finetune without GPT-2 dropout")
     ap.add_argument("--dry-run", action="store_true",
-                    help="no GPU: every rank walks THIS file's control flow (warm-up, timed regions, max-over-ranks, the no-all-reduce pass, the "
-                         "event-bracketed passes, process-group teardown, rank 0's sub-benches and CPU baseline) with a stub workload over gloo — "
-                         "what tests/test_ddp_gloo.py runs at 8 ranks to show that no rank is left waiting in a collective")
+                    help="no GPU: every rank walks THIS file's control flow (warm-up, timed regions, max-over-ranks, process-group teardown; "
+                         "with --full also the no-all-reduce pass, the event-bracketed passes, rank 0's sub-benches and CPU baseline) with a stub "
+                         "workload over gloo — what tests/test_ddp_gloo.py runs at 8 ranks to show that no rank is left waiting in a collective")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, "
                          "seeded samples of large tensors, <= 64 MB in all); the inputs are seeded, so two builds can be compared output for output")
@@ -851,7 +859,7 @@ def main():
     if args.dump_outputs and rank == 0:     # the last timed step's outputs, before any untimed step below changes the arenas
         dump_outputs(args.dump_outputs, train_step_outputs(loss, eng))
     exposed_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         # the same steps with the gradient all-reduce left out (timing only): the difference is the all-reduce time that backward
         # did not hide
         k2 = max(5, args.steps // 8)
@@ -865,7 +873,7 @@ def main():
     T, D, Mc, M = c["L"] + cap, c["D"], B * cap, B * (c["L"] + cap)
     S = c["P"] + c["L"]
     roof = {}
-    if not args.no_roofline_pass:   # every rank runs the profiled extra steps (their collectives must match); rank 0 reports
+    if args.full and not args.no_roofline_pass:   # every rank runs the profiled extra steps (their collectives must match); rank 0 reports
         # ---- roofline of the dominant kernel family: every MFMA GEMM launch of the step (forward, dgrad, wgrad, lm_head), bracketed
         # with HIP events on the launch stream during 5 extra steps; achieved = sum of 2MNK / sum of launch durations ----
         n_prof = 5
@@ -944,14 +952,19 @@ def main():
     if world > 1:
         out["rccl_ranks"] = rccl_ranks
         out["collective_backend"] = "rccl (C ABI cc_allreduce_bucket)" if comm is not None else ("rccl" if backend == "nccl" else backend)
-        out["allreduce_exposed_ms"] = round(exposed_ms, 3)
-        out["exposed_allreduce_ms"] = out["allreduce_exposed_ms"]      # (the name VERDICT r4 item 9 uses)
+        if exposed_ms is not None:                                      # --full
+            out["allreduce_exposed_ms"] = round(exposed_ms, 3)
+            out["exposed_allreduce_ms"] = out["allreduce_exposed_ms"]  # (the name VERDICT r4 item 9 uses)
         out["gradient_wire_dtype"] = args.grad_wire
         out["zero_stage"] = 0                                           # bench.py replicates the optimizer state (train() shards it under --deepspeed-strategy)
         out["allreduce_bytes_per_step_per_rank"] = int(sum(a.n for a in arenas) * (2 if args.grad_wire == "bf16" else 4))
         out["gradient_payload_bytes"] = int(sum(a.n for a in arenas) * (2 if args.grad_wire == "bf16" else 4))
         out["gradient_wire_dtype"] = args.grad_wire
     out.update(roof)
+    if not args.full:
+        # a plain run ends with its headline line: the extras below (minutes of sub-benches and CPU baselines) are --full's
+        print(json.dumps(out))
+        return
     if dry:
         # rank 0's single-rank extras, stubbed to a pause of the same order as the collectives' timeouts would need to survive
         time.sleep(float(os.environ.get("CC_BENCH_DRY_EXTRAS_S", "2.0")))

@@ -66,3 +66,27 @@ def test_dry_run_dump_outputs_and_exact_steps(tmp_path):
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "0"], env=env, capture_output=True, text=True,
                          timeout=300)
     assert bad.returncode != 0 and "--steps" in bad.stderr
+
+
+def test_plain_run_prints_the_headline_only_and_full_adds_the_extras():
+    """A plain run sets up, warms up, times its steps and prints the headline line.  What takes runs of its own (N > 1: the steps without
+    the all-reduce; the event-bracketed roofline steps) and rank 0's extras (sub-benches, CPU baselines) run only under --full."""
+    env = dict(os.environ, CC_BENCH_DRY_EXTRAS_S="0")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    lines = {}
+    for flags in ([], ["--full"]):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "5", "--warmup", "1",
+                              "--regions", "2"] + flags, env=env, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        js = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(js) == 1, out.stdout[-2000:]
+        lines[bool(flags)] = json.loads(js[0])
+    plain, full = lines[False], lines[True]
+    for j in (plain, full):
+        assert j["n_gpus"] == 2 and j["steps"] == 5 and j["warmup"] == 1 and j["timed_regions"]["steps_per_region"] == [3, 2]
+        assert j["unit"] == "samples/s" and j["higher_is_better"] is True and j["dtype"] == "bf16" and j["value"] > 0 and j["ms_per_step"] > 0
+    extras = {"allreduce_exposed_ms", "exposed_allreduce_ms", "roofline", "roofline_lmhead", "cpu_baseline"}
+    assert not extras & plain.keys(), sorted(extras & plain.keys())
+    assert extras <= full.keys(), sorted(extras - full.keys())
+    assert plain.keys() <= full.keys() and plain["metric"] == full["metric"]

@@ -172,7 +172,7 @@ def test_twenty_step_loss_trajectory_bf16_wire_follows_fp32_wire(tmp_path):
 
 def test_bench_eight_rank_dry_run_every_rank_leaves_before_rank_zero_extras():
     """no 8-GPU node exists for this build, so the first 8-rank run of bench.py must not be the first time its control flow
-    executes.  `bench.py --gpus 8 --dry-run` walks the real flow of that file (warm-up, timed regions with max-over-ranks, the
+    executes.  `bench.py --gpus 8 --dry-run --full` walks the real flow of that file (warm-up, timed regions with max-over-ranks, the
     no-all-reduce pass, both event-bracketed passes, teardown) over gloo with a stub step; rank 0 then spends seconds alone in its
     single-rank extras.  Every rank must have left the process group BEFORE that, the run must end cleanly and print ONE 8-rank line."""
     import json
@@ -183,7 +183,8 @@ def test_bench_eight_rank_dry_run_every_rank_leaves_before_rank_zero_extras():
     env.pop("RANK", None)
     env.pop("WORLD_SIZE", None)
     t0 = __import__("time").time()
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--dry-run", "--steps", "3", "--warmup", "1", "--regions", "3"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--dry-run", "--full", "--steps", "3", "--warmup", "1",
+                          "--regions", "3"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     left = __import__("re").findall(r"\[bench rank (\d+)\] left the process group", out.stderr)      # (ranks share the pipe: lines may run together)

@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-TRAIN="python $ROOT/bench.py --steps 8 --warmup 2 --regions 1 --no-cpu-baseline --no-sub-benches"
+TRAIN="python $ROOT/bench.py --steps 8 --warmup 2 --regions 1 --full --no-cpu-baseline --no-sub-benches"
 run_trace() {  # name, command...
     local name=$1; shift
     rm -rf $OUT/prof_$name
