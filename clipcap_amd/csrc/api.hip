@@ -65,11 +65,9 @@ inline const uint16_t* W16(const uint16_t* w16, int64_t off) { return w16 + (siz
 inline uint16_t* W16(uint16_t* w16, int64_t off) { return w16 + (size_t)PL * off; }
 // bf16x3: bytes of operand-image scratch for GEMMs whose largest A image is rows x depth (x3_operand rounds each image up to 256 B)
 inline size_t x3_img(size_t rows, size_t depth) { return ((rows * 3 * depth * sizeof(op16_t)) + 255) & ~size_t(255); }
-#if CC_OP == 2
-#define X3_SCRATCH(w) x3_set_scratch((w).x3, (w).x3_bytes)
-#else
-#define X3_SCRATCH(w) (void)0
-#endif
+// the Call of an entry point: its stream and the scratch of its carved workspace (MapperWS / Gpt2WS)
+template <class WS>
+inline Call call_of(hipStream_t st, const WS& w) { return Call{st, w.red, w.x3, w.x3_bytes}; }
 
 // ------------------------------------------------------------------------------------------------------------
 // mapper
@@ -129,7 +127,7 @@ struct MapperWS {
     act_t *gdx[MAX_LAYERS], *gdxb[MAX_LAYERS], *gdh[MAX_LAYERS], *gdqkv[MAX_LAYERS];
     bool own_grads;     // every layer has its own copies (else they alias the single dx16 / dx16b / dh16 / dqkv16 buffers and weight gradients flush per layer)
     float* wg_scratch;
-    float* red;         // partial sums of the cross-block reductions (kernels.h red_set_scratch)
+    float* red;         // partial sums of the cross-block reductions (kernels.h)
     float* adelta;
     uint16_t* gimg;    // bf16x3 build: the [hi | hi | lo] image of the output gradient both GEMMs of a layer step read
     char* x3;          // bf16x3 build: operand-image scratch of the GEMM in flight (gemm_api.h)
@@ -257,24 +255,49 @@ void gpt2_offsets(const cc_gpt2_cfg* c, Gpt2Off& o) {
     o.total = p;
 }
 
+// bf16x3, frozen LM: c_fc's forward epilogue and the gelu' input-gradient epilogue write the [hi | hi | lo] operand image of their consumer
+// GEMM directly instead of an fp32 activation that a split pass re-reads (CC_X3_IMG=0: A/B switch)
+static bool x3_img_on() {
+    static const bool on = []() { const char* e = cc_lab_env("CC_X3_IMG"); return !e || atoi(e) != 0; }();
+    return on;
+}
+// Exponential form of the lm_head outputs (gemm.hip.h EpiLMHead): the bf16 build's training path stores exp(logit - target logit) and
+// never materialises the softmax gradient.  fp16 lacks the exponent range, the bf16x3 build keeps fp32 logits.  CC_LM_EXPFORM=0: A/B switch.
+// bf16x3: the exponential form for frozen-LM runs (round 4) — E leaves the GEMM as the [hi | hi | lo] operand image of the input-gradient
+// GEMM (in the logits buffer, 1.5x), so neither fp32 logits nor the softmax-gradient pass over them exist; the full finetune keeps the
+// logit form (its tied weight gradient reads the fp32 gradient).
+static bool lm_exp_form(const cc_gpt2_shape* s) {
+    static const bool env = []() { const char* e = cc_lab_env("CC_LM_EXPFORM"); return !e || atoi(e) != 0; }();
+    if (CC_OP == 0) return env;
+    if (CC_OP == 2) return env && x3_img_on() && s->mode == 1;
+    return false;
+}
+// The logits buffer as cc_lmhead_ce_fwd fills it and cc_lmhead_ce_bwd reads it: in the bf16x3 exponential form E leaves the lm_head GEMM
+// as the operand image of the input-gradient GEMM.  cc_gpt2_logits_bwd fills the same buffer with plain values and passes the pointer.
+static Act lm_logits(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, act_t* logits16) { return Act(logits16, (kX3 && lm_exp_form(s)) ? c->Vp : 0); }
+
 struct Gpt2WS {
     float* x[MAX_LAYERS + 1];
     float* x1[MAX_LAYERS];
-    act_t *xn1[MAX_LAYERS], *xn2[MAX_LAYERS], *qkv[MAX_LAYERS], *att[MAX_LAYERS], *u[MAX_LAYERS], *hact[MAX_LAYERS];
+    act_t *qkv[MAX_LAYERS], *u[MAX_LAYERS];
+    // Act: buffers that hold, in the bf16x3 build, either fp32 activations or the operand image of the one GEMM that reads them; gpt2_carve
+    // decides which, and the handle says it to the buffer's producer and to its consumer alike
+    Act xn1[MAX_LAYERS], xn2[MAX_LAYERS], att[MAX_LAYERS], hact[MAX_LAYERS];
     float *lse[MAX_LAYERS], *mean1[MAX_LAYERS], *rstd1[MAX_LAYERS], *mean2[MAX_LAYERS], *rstd2[MAX_LAYERS];
     // lm head / loss
     act_t* hf16;       // [Mh, D]   ln_f output rows (Mh = max(B*cap, B*T) so the parity API can use it too)
     float *meanf, *rstdf;
     int *target, *row_map;
-    act_t* logits16;   // [B*cap, Vp]
+    act_t* logits16;   // [B*cap, Vp]  (what it holds depends on who filled it: lm_logits)
     float *pmax, *psum, *tgt_logit, *lse_row, *row_loss;
     float *cref, *lmfac;   // exponential form of the lm_head outputs (bf16 build): reference shift [Mc], row factors {r, w} [Mc][2]
     act_t* hfs16;          // full finetune: r * hf rows, the weight-gradient operand of the exponential form
     // backward
     float* dx32;
-    act_t *dx16, *dx16b, *dhf16, *du16, *dxn16, *datt16, *dqkv16;
+    Act dx16, dx16b, du16, dqkv16;
+    act_t *dhf16, *dxn16, *datt16;
     float* wg_scratch;
-    float* red;        // partial sums of the cross-block reductions (kernels.h red_set_scratch)
+    float* red;        // partial sums of the cross-block reductions (kernels.h)
     void* scat;        // full finetune: scratch of the token-indexed scatters into d wte (kernels.h scatter_rows), for the B*cap caption rows
     float* adelta;
     char* x3;          // bf16x3 build: operand-image scratch
@@ -282,10 +305,20 @@ struct Gpt2WS {
     size_t bytes;
 };
 
-void gpt2_carve(const cc_gpt2_cfg* c, int B, int T, int cap, int mode, void* ws, Gpt2WS& w) {
+// cap: caption rows per sample the loss-side buffers are sized for (s->T - s->L; cc_gpt2_logits_bwd: all s->T)
+void gpt2_carve(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, int cap, void* ws, Gpt2WS& w) {
     Carver cv(ws);
+    const int B = s->B, T = s->T, hd = c->D / c->H;
     const size_t M = (size_t)B * T, D = c->D, Mc = (size_t)B * cap;
-    const bool keep = mode >= 1, full = mode >= 2;
+    const bool keep = s->mode >= 1, full = s->mode >= 2;
+    // bf16x3: which buffers are operand images (width of the operand, 0 = fp32 activations).  Frozen LM: no weight gradient reads the
+    // normalised rows, the attention output, the MLP hidden or d u, so LayerNorm, attention and the c_fc / gelu' epilogues write what
+    // the next GEMM reads; without dropout that also holds for the 16-bit copies of the residual gradient and for d qkv.  Attention
+    // writes images only for the shapes its fp32-VALU pair serves (the backward then recomputes what it needs from qkv).
+    const bool img = kX3 && !full && x3_img_on();
+    const bool bimg = img && keep && s->p_resid == 0.f && s->p_attn == 0.f && s->p_embd == 0.f;
+    const int xw = img ? (int)D : 0, attw = (img && attn_fwd_can_image(T, hd)) ? (int)D : 0, hw = img ? 4 * (int)D : 0;
+    const int dxw = bimg ? (int)D : 0, dqw = (bimg && attn_bwd_can_image(T, hd)) ? 3 * (int)D : 0;
     const int nx = keep ? c->NL + 1 : 2;
     float* xb[MAX_LAYERS + 1];
     for (int i = 0; i < nx; i++) xb[i] = cv.take<float>(M * D);
@@ -300,10 +333,10 @@ void gpt2_carve(const cc_gpt2_cfg* c, int B, int T, int cap, int mode, void* ws,
         w.rstd1[l] = k0 ? cv.take<float>(M) : w.rstd1[0];
         w.mean2[l] = k0 ? cv.take<float>(M) : w.mean2[0];
         w.rstd2[l] = k0 ? cv.take<float>(M) : w.rstd2[0];
-        w.xn1[l] = f0 ? cv.take<act_t>(M * D * ((kX3 && !full) ? 3 : 2) / 2) : w.xn1[0];       // bf16x3, frozen LM: LayerNorm writes c_attn's / c_fc's operand image
-        w.xn2[l] = f0 ? cv.take<act_t>(M * D * ((kX3 && !full) ? 3 : 2) / 2) : w.xn2[0];
-        w.att[l] = k0 ? cv.take<act_t>(M * D * ((kX3 && !full) ? 3 : 2) / 2) : w.att[0];    // attention output: needed by the backward's delta = rowsum(dO*O) (bf16x3, frozen LM: attn.c_proj's operand image)
-        w.hact[l] = f0 ? cv.take<act_t>(M * 4 * D * ((kX3 && !full) ? 3 : 2) / 2) : w.hact[0];    // bf16x3, frozen LM: holds mlp.c_proj's operand IMAGE (6 B / element), written by c_fc's epilogue
+        w.xn1[l] = f0 ? Act(cv.take<act_t>(M * D * ((kX3 && !full) ? 3 : 2) / 2), xw) : w.xn1[0];       // bf16x3, frozen LM: LayerNorm writes c_attn's / c_fc's operand image
+        w.xn2[l] = f0 ? Act(cv.take<act_t>(M * D * ((kX3 && !full) ? 3 : 2) / 2), xw) : w.xn2[0];
+        w.att[l] = k0 ? Act(cv.take<act_t>(M * D * ((kX3 && !full) ? 3 : 2) / 2), attw) : w.att[0];    // attention output: needed by the backward's delta = rowsum(dO*O) (bf16x3, frozen LM: attn.c_proj's operand image)
+        w.hact[l] = f0 ? Act(cv.take<act_t>(M * 4 * D * ((kX3 && !full) ? 3 : 2) / 2), hw) : w.hact[0];    // bf16x3, frozen LM: holds mlp.c_proj's operand IMAGE (6 B / element), written by c_fc's epilogue
     }
     const size_t Mh = std::max(M, Mc);
     w.hf16 = cv.take<act_t>(Mh * D);
@@ -313,7 +346,7 @@ void gpt2_carve(const cc_gpt2_cfg* c, int B, int T, int cap, int mode, void* ws,
     w.row_map = cv.take<int>(Mh);
     if (keep) {
         const int npart = c->Vp / 64;
-        w.logits16 = cv.take<act_t>(Mc * c->Vp * ((kX3 && !full) ? 3 : 2) / 2);               // bf16x3, frozen LM: E as an operand image (lm_exp_form)
+        w.logits16 = cv.take<act_t>(Mc * c->Vp * ((kX3 && !full) ? 3 : 2) / 2);               // bf16x3, frozen LM: room for E as an operand image (lm_logits)
         w.pmax = cv.take<float>(Mc * npart);
         w.psum = cv.take<float>(Mc * npart);
         w.tgt_logit = cv.take<float>(Mc);
@@ -323,13 +356,13 @@ void gpt2_carve(const cc_gpt2_cfg* c, int B, int T, int cap, int mode, void* ws,
         w.lmfac = cv.take<float>(2 * Mc);
         w.hfs16 = full ? cv.take<act_t>(Mc * D) : nullptr;
         w.dx32 = cv.take<float>(M * D);
-        w.dx16 = cv.take<act_t>(M * D * ((kX3 && !full) ? 3 : 2) / 2);                            // bf16x3, frozen LM: operand images written by their producers (LayerNorm backward, attention backward)
-        w.dx16b = full ? cv.take<act_t>(M * D) : w.dx16;    // full finetune: second copy so a layer's weight gradients can run grouped
+        w.dx16 = Act(cv.take<act_t>(M * D * ((kX3 && !full) ? 3 : 2) / 2), dxw);                  // bf16x3, frozen LM: operand images written by their producers (LayerNorm backward, attention backward)
+        w.dx16b = full ? Act(cv.take<act_t>(M * D)) : w.dx16;    // full finetune: second copy so a layer's weight gradients can run grouped
         w.dhf16 = cv.take<act_t>(Mc * D);
-        w.du16 = cv.take<act_t>(M * 4 * D * ((kX3 && !full) ? 3 : 2) / 2);                       // likewise: c_fc's input-gradient operand image, written by the gelu' epilogue
+        w.du16 = Act(cv.take<act_t>(M * 4 * D * ((kX3 && !full) ? 3 : 2) / 2), hw);              // likewise: c_fc's input-gradient operand image, written by the gelu' epilogue
         w.dxn16 = cv.take<act_t>(M * D);
         w.datt16 = cv.take<act_t>(M * D);
-        w.dqkv16 = cv.take<act_t>(M * 3 * D * ((kX3 && !full) ? 3 : 2) / 2);
+        w.dqkv16 = Act(cv.take<act_t>(M * 3 * D * ((kX3 && !full) ? 3 : 2) / 2), dqw);
         w.wg_scratch = full ? cv.take<float>(WGRAD_SCRATCH_BYTES / sizeof(float)) : nullptr;
         w.red = full ? cv.take<float>(RED_SCRATCH_FLOATS) : nullptr;      // only a full finetune reduces parameter gradients across blocks
         w.scat = full ? cv.take<char>(scatter_ws_bytes((int)Mc, (int)D)) : nullptr;
@@ -338,7 +371,7 @@ void gpt2_carve(const cc_gpt2_cfg* c, int B, int T, int cap, int mode, void* ws,
         w.wg_scratch = nullptr; w.adelta = nullptr; w.red = nullptr; w.scat = nullptr;
         w.logits16 = nullptr; w.pmax = w.psum = w.tgt_logit = w.lse_row = w.row_loss = nullptr;
         w.cref = w.lmfac = nullptr; w.hfs16 = nullptr;
-        w.dx32 = nullptr; w.dx16 = w.dx16b = w.dhf16 = w.du16 = w.dxn16 = w.datt16 = w.dqkv16 = nullptr;
+        w.dx32 = nullptr; w.dx16 = w.dx16b = w.du16 = w.dqkv16 = Act(); w.dhf16 = w.dxn16 = w.datt16 = nullptr;
     }
     w.x3 = nullptr; w.x3_bytes = 0;
     if (kX3) {
@@ -456,16 +489,15 @@ int CC_API(cc_mapper_fwd)(const cc_mapper_cfg* c, int32_t B, const float* w32, c
     mapper_offsets(c, o);
     MapperWS w;
     mapper_carve(c, B, save, ws, w);
-    X3_SCRATCH(w);
-    red_set_scratch(w.red);
+    Call cx = call_of(st, w);
     const int D = c->D, PP = c->W * c->P, S = PP + c->L, M = B * S, H = c->H, hd = D / H, Hm = c->Hm;
     const int PD = c->P * D;
     // linear (mapper.py:123): [B*W, E] x [P*D, E]^T + b -> rows 0..PP-1 of every sample of x[0]
     CC_TRY(f32_to_act(emb, w.emb16, (size_t)B * c->W * c->E, st));
     if (c->W == 1) {
-        CC_TRY(gemm_f32out(0, 0, w.emb16, c->E, W16(w16, o.lin_w), c->E, B, PD, c->E, w.x[0], S * D, w32 + o.lin_b, 0, 1.0f, 1, st));
+        CC_TRY(gemm_f32out(0, 0, w.emb16, c->E, W16(w16, o.lin_w), c->E, B, PD, c->E, w.x[0], S * D, w32 + o.lin_b, 0, 1.0f, 1, cx));
     } else {
-        CC_TRY(gemm_f32out(0, 0, w.emb16, c->E, W16(w16, o.lin_w), c->E, B * c->W, PD, c->E, w.lin_tmp, PD, w32 + o.lin_b, 0, 1.0f, 1, st));
+        CC_TRY(gemm_f32out(0, 0, w.emb16, c->E, W16(w16, o.lin_w), c->E, B * c->W, PD, c->E, w.lin_tmp, PD, w32 + o.lin_b, 0, 1.0f, 1, cx));
         CC_TRY(copy_rows(w.lin_tmp, (size_t)PP * D, w.x[0], (size_t)S * D, PP * D, B, st));
         if (o.pos >= 0) CC_TRY(add_rows(w.x[0], (size_t)S * D, w32 + o.pos, PP * D, B, st));
     }
@@ -475,13 +507,13 @@ int CC_API(cc_mapper_fwd)(const cc_mapper_cfg* c, int32_t B, const float* w32, c
         const auto& y = o.layer[l];
         // x1 = x + project(attn(LN1 x))  (mapper.py:108, attention.py:17-43)
         CC_TRY(ln_fwd(w.x[l], D, nullptr, w32 + y.n1w, w32 + y.n1b, w.xn1[l], nullptr, w.mean1[l], w.rstd1[l], M, D, st));
-        CC_TIMED(CC_SITE_MAPPER_QKV_FWD, st, gemm_bf16out(0, 0, w.xn1[l], D, W16(w16, y.wq), D, M, 3 * D, D, w.qkv[l], 3 * D, nullptr, 0, nullptr, st));
+        CC_TIMED(CC_SITE_MAPPER_QKV_FWD, st, gemm_bf16out(0, 0, w.xn1[l], D, W16(w16, y.wq), D, M, 3 * D, D, w.qkv[l], 3 * D, nullptr, 0, nullptr, cx));
         CC_TRY(attn_fwd(w.qkv[l], B, S, H, hd, false, w.att[l], w.lse[l], st));
-        CC_TRY(gemm_resid(0, 0, w.att[l], D, W16(w16, y.wp), D, M, D, D, w.x1[l], w.x[l], D, w32 + y.bp, st));
+        CC_TRY(gemm_resid(0, 0, w.att[l], D, W16(w16, y.wp), D, M, D, D, w.x1[l], w.x[l], D, w32 + y.bp, cx));
         // x = x1 + fc2(relu(fc1(LN2 x1)))  (mapper.py:109, :82-88)
         CC_TRY(ln_fwd(w.x1[l], D, nullptr, w32 + y.n2w, w32 + y.n2b, w.xn2[l], nullptr, w.mean2[l], w.rstd2[l], M, D, st));
-        CC_TIMED(CC_SITE_MAPPER_FC1_FWD, st, gemm_bf16out(0, 0, w.xn2[l], D, W16(w16, y.w1), D, M, Hm, D, w.h[l], Hm, w32 + y.b1, 1, nullptr, st));
-        CC_TRY(gemm_resid(0, 0, w.h[l], Hm, W16(w16, y.w2), Hm, M, D, Hm, w.x[l + 1], w.x1[l], D, w32 + y.b2, st));
+        CC_TIMED(CC_SITE_MAPPER_FC1_FWD, st, gemm_bf16out(0, 0, w.xn2[l], D, W16(w16, y.w1), D, M, Hm, D, w.h[l], Hm, w32 + y.b1, 1, nullptr, cx));
+        CC_TRY(gemm_resid(0, 0, w.h[l], Hm, W16(w16, y.w2), Hm, M, D, Hm, w.x[l + 1], w.x1[l], D, w32 + y.b2, cx));
     }
     // out = rows [PP:] (mapper.py:128)
     CC_TRY(copy_rows(w.x[c->N] + (size_t)PP * D, (size_t)S * D, out, (size_t)c->L * D, c->L * D, B, st));
@@ -510,8 +542,7 @@ int CC_API(cc_mapper_bwd_range)(const cc_mapper_cfg* c, int32_t B, const float* 
     mapper_offsets(c, o);
     MapperWS w;
     mapper_carve(c, B, 1, ws, w);
-    X3_SCRATCH(w);
-    red_set_scratch(w.red);
+    Call cx = call_of(st, w);
     const int D = c->D, PP = c->W * c->P, S = PP + c->L, M = B * S, H = c->H, hd = D / H, Hm = c->Hm;
     const int PD = c->P * D;
     const uint16_t* w16t = W16(w16, o.total);   // transposed weight copies: dgrad GEMMs are NT
@@ -538,19 +569,17 @@ int CC_API(cc_mapper_bwd_range)(const cc_mapper_cfg* c, int32_t B, const float* 
     if (defer_all) { wb.direct = true; wb.cap = 4 * (l_hi - l_lo); }
     ColsumBatch cs;
     // bf16x3: `G2(t, width)` = the tensor as both of its GEMMs take it — split ONCE into w.gimg ([hi | hi | lo], the form of the weight
-    // gradient's first operand and of the input gradient's A operand alike); every use re-arms the one-shot image hint
+    // gradient's first operand and of the input gradient's A operand alike)
 #if CC_OP == 2
     static const bool share = []() { const char* e = cc_lab_env("CC_X3_SHARE"); return !e || atoi(e) != 0; }();
     int g2rc = CC_OK;
-    auto G2 = [&](const act_t* t, int width) -> const act_t* {
+    auto G2 = [&](const act_t* t, int width) -> ActIn {
         if (!share) return t;
         g2rc = x3_split_rows(t, (size_t)width, w.gimg, M, width, 0, st);
-        return reinterpret_cast<const act_t*>(w.gimg);
+        return ActIn(reinterpret_cast<const act_t*>(w.gimg), width);
     };
-    auto USE = [&](const act_t* img) -> const act_t* { if (share) x3_expect_image(img); return img; };
 #else
-    auto G2 = [&](const act_t* t, int) -> const act_t* { return t; };
-    auto USE = [&](const act_t* img) -> const act_t* { return img; };
+    auto G2 = [&](const act_t* t, int) -> ActIn { return t; };
     const int g2rc = CC_OK;
 #endif
     for (int l = l_hi - 1; l >= l_lo; l--) {
@@ -563,77 +592,57 @@ int CC_API(cc_mapper_bwd_range)(const cc_mapper_cfg* c, int32_t B, const float* 
         // must NOT land in a buffer a deferred weight gradient still has to read: it goes to the attention-gradient scratch, dead by then
         act_t* dx16_below = l > 0 ? w.gdx[l - 1] : w.datt16;
         // fc2: y = h W2^T + b2
-        const act_t* gx = G2(dx16, D);
+        const ActIn gx = G2(dx16, D);
         CC_TRY(g2rc);
-        CC_TIMED(CC_SITE_MAPPER_WGRAD_FC2, st, gemm_wgrad(USE(gx), D, w.h[l], Hm, D, Hm, M, g32 + y.w2, Hm, w.wg_scratch, st, &wb));
+        CC_TIMED(CC_SITE_MAPPER_WGRAD_FC2, st, gemm_wgrad(gx, D, w.h[l], Hm, D, Hm, M, g32 + y.w2, Hm, w.wg_scratch, cx, &wb));
         // fc2.bias gradient = column sums of dx16: for every layer but the top one the LN1 backward of the layer above produced
         // them together with dx16 (ln_bwd dcol); the top layer's dx16 comes from the seed
-        if (l == c->N - 1) CC_TRY(colsum_bf16(dx16, D, M, D, g32 + y.b2, st));
-        CC_TRY(gemm_dact(0, 0, USE(gx), D, W16(w16t, y.w2), D, M, Hm, D, dh16, Hm, w.h[l], 1, st));          // W2^T [Hm, D]
+        if (l == c->N - 1) CC_TRY(colsum_bf16(dx16, D, M, D, g32 + y.b2, cx));
+        CC_TRY(gemm_dact(0, 0, gx, D, W16(w16t, y.w2), D, M, Hm, D, dh16, Hm, w.h[l], 1, cx));          // W2^T [Hm, D]
         // fc1
-        const act_t* gh = G2(dh16, Hm);
+        const ActIn gh = G2(dh16, Hm);
         CC_TRY(g2rc);
-        CC_TRY(gemm_wgrad(USE(gh), Hm, w.xn2[l], D, Hm, D, M, g32 + y.w1, D, w.wg_scratch, st, &wb));
+        CC_TRY(gemm_wgrad(gh, Hm, w.xn2[l], D, Hm, D, M, g32 + y.w1, D, w.wg_scratch, cx, &wb));
         if (defer_all) cs.add(dh16, g32 + y.b1);                  // fc1.bias gradient: with the deferred weight gradients, one launch for all layers
-        else CC_TRY(colsum_bf16(dh16, Hm, M, Hm, g32 + y.b1, st));
-        CC_TRY(gemm_bf16out(0, 0, USE(gh), Hm, W16(w16t, y.w1), Hm, M, D, Hm, w.dxn16, D, nullptr, 0, nullptr, st));   // W1^T [D, Hm]
+        else CC_TRY(colsum_bf16(dh16, Hm, M, Hm, g32 + y.b1, cx));
+        CC_TRY(gemm_bf16out(0, 0, gh, Hm, W16(w16t, y.w1), Hm, M, D, Hm, w.dxn16, D, nullptr, 0, nullptr, cx));   // W1^T [D, Hm]
         CC_TRY(ln_bwd(w.dxn16, w.x1[l], D, nullptr, w.mean2[l], w.rstd2[l], w32 + y.n2w, w.dx32, w.dx32, dx16b, g32 + y.n2w,
-                      g32 + y.n2b, M, D, st, g32 + y.bp));         // + project.bias gradient (column sums of dx16b)
+                      g32 + y.n2b, M, D, cx, g32 + y.bp));         // + project.bias gradient (column sums of dx16b)
         // project
-        const act_t* gb = G2(dx16b, D);
+        const ActIn gb = G2(dx16b, D);
         CC_TRY(g2rc);
-        CC_TRY(gemm_wgrad(USE(gb), D, w.att[l], D, D, D, M, g32 + y.wp, D, w.wg_scratch, st, &wb));
-        CC_TRY(gemm_bf16out(0, 0, USE(gb), D, W16(w16t, y.wp), D, M, D, D, w.datt16, D, nullptr, 0, nullptr, st));     // Wp^T
+        CC_TRY(gemm_wgrad(gb, D, w.att[l], D, D, D, M, g32 + y.wp, D, w.wg_scratch, cx, &wb));
+        CC_TRY(gemm_bf16out(0, 0, gb, D, W16(w16t, y.wp), D, M, D, D, w.datt16, D, nullptr, 0, nullptr, cx));     // Wp^T
         CC_TRY(attn_bwd(w.qkv[l], w.datt16, w.att[l], w.lse[l], w.adelta, B, S, H, hd, false, dqkv16, st));
         // fused q/kv projection (to_queries.weight ++ to_keys_values.weight = [3D, D])
-        const act_t* gq = G2(dqkv16, 3 * D);
+        const ActIn gq = G2(dqkv16, 3 * D);
         CC_TRY(g2rc);
-        CC_TRY(gemm_wgrad(USE(gq), 3 * D, w.xn1[l], D, 3 * D, D, M, g32 + y.wq, D, w.wg_scratch, st, &wb));
-        CC_TRY(gemm_bf16out(0, 0, USE(gq), 3 * D, W16(w16t, y.wq), 3 * D, M, D, 3 * D, w.dxn16, D, nullptr, 0, nullptr, st));  // Wqkv^T [D, 3D]
+        CC_TRY(gemm_wgrad(gq, 3 * D, w.xn1[l], D, 3 * D, D, M, g32 + y.wq, D, w.wg_scratch, cx, &wb));
+        CC_TRY(gemm_bf16out(0, 0, gq, 3 * D, W16(w16t, y.wq), 3 * D, M, D, 3 * D, w.dxn16, D, nullptr, 0, nullptr, cx));  // Wqkv^T [D, 3D]
         // per-layer form: the deferred weight gradients read dx16, dh16, dx16b, dqkv16 — run them before the LN1 backward overwrites dx16
         // with the next layer's input gradient (with per-layer buffers nothing is overwritten and the flush waits for the end of the call)
         if (!defer_all) CC_TRY(wgrad_flush(wb, st));
         CC_TRY(ln_bwd(w.dxn16, w.x[l], D, nullptr, w.mean1[l], w.rstd1[l], w32 + y.n1w, w.dx32, w.dx32, dx16_below, g32 + y.n1w,
-                      g32 + y.n1b, M, D, st, l > 0 ? g32 + o.layer[l - 1].b2 : nullptr));   // + fc2.bias gradient of the layer below
+                      g32 + y.n1b, M, D, cx, l > 0 ? g32 + o.layer[l - 1].b2 : nullptr));   // + fc2.bias gradient of the layer below
     }
     CC_TRY(wgrad_flush(wb, st));
-    CC_TRY(colsum_bf16_multi(cs, Hm, M, Hm, st));
+    CC_TRY(colsum_bf16_multi(cs, Hm, M, Hm, cx));
     if (l_lo > 0) return CC_OK;
     // prefix_const, pos_embeddings, linear
-    CC_TRY(batch_sum(w.dx32 + (size_t)PP * D, (size_t)S * D, g32 + o.prefix, c->L * D, B, st));
-    if (o.pos >= 0) CC_TRY(batch_sum(w.dx32, (size_t)S * D, g32 + o.pos, PP * D, B, st));
+    CC_TRY(batch_sum(w.dx32 + (size_t)PP * D, (size_t)S * D, g32 + o.prefix, c->L * D, B, cx));
+    if (o.pos >= 0) CC_TRY(batch_sum(w.dx32, (size_t)S * D, g32 + o.pos, PP * D, B, cx));
     CC_TRY(slice_f32_to_bf16(w.dx32, (size_t)S * D, w.dlin16, (size_t)PP * D, PP * D, B, st));
-    CC_TRY(gemm_wgrad(w.dlin16, PD, w.emb16, c->E, PD, c->E, B * c->W, g32 + o.lin_w, c->E, w.wg_scratch, st));
-    CC_TRY(colsum_bf16(w.dlin16, PD, B * c->W, PD, g32 + o.lin_b, st));
+    CC_TRY(gemm_wgrad(w.dlin16, PD, w.emb16, c->E, PD, c->E, B * c->W, g32 + o.lin_w, c->E, w.wg_scratch, cx));
+    CC_TRY(colsum_bf16(w.dlin16, PD, B * c->W, PD, g32 + o.lin_b, cx));
     return CC_OK;
 }
 
 // ---------------------------------------------------------------- GPT-2 -----------------------------------------
 namespace {
-// Exponential form of the lm_head outputs (gemm.hip.h EpiLMHead): the bf16 build's training path stores exp(logit - target logit) and
-// never materialises the softmax gradient.  fp16 lacks the exponent range, the bf16x3 build keeps fp32 logits.  CC_LM_EXPFORM=0: A/B switch.
 // c_fc forward stores gelu_new'(u) where it used to store u (CC_GELU_GRAD_FWD=0: A/B switch; forward and backward read the same setting)
 static bool gelu_grad_fwd() {
     static const bool on = []() { const char* e = cc_lab_env("CC_GELU_GRAD_FWD"); return !e || atoi(e) != 0; }();
     return on;
-}
-// bf16x3, frozen LM: c_fc's forward epilogue and the gelu' input-gradient epilogue write the [hi | hi | lo] operand image of their consumer
-// GEMM directly instead of an fp32 activation that a split pass re-reads (CC_X3_IMG=0: A/B switch)
-static bool x3_img_on() {
-    static const bool on = []() { const char* e = cc_lab_env("CC_X3_IMG"); return !e || atoi(e) != 0; }();
-    return on;
-}
-#if CC_OP == 2
-static bool gpt2_bwd_images(const cc_gpt2_shape* s) { return s->mode == 1 && x3_img_on() && s->p_resid == 0.f && s->p_attn == 0.f && s->p_embd == 0.f; }
-#endif
-// bf16x3: the exponential form for frozen-LM runs (round 4) — E leaves the GEMM as the [hi | hi | lo] operand image of the input-gradient
-// GEMM (in the logits buffer, 1.5x), so neither fp32 logits nor the softmax-gradient pass over them exist; the full finetune keeps the
-// logit form (its tied weight gradient reads the fp32 gradient).
-static bool lm_exp_form(const cc_gpt2_shape* s) {
-    static const bool env = []() { const char* e = cc_lab_env("CC_LM_EXPFORM"); return !e || atoi(e) != 0; }();
-    if (CC_OP == 0) return env;
-    if (CC_OP == 2) return env && x3_img_on() && s->mode == 1;
-    return false;
 }
 static bool shape_ok(const cc_gpt2_cfg* c, const cc_gpt2_shape* s) {
     return s && s->B > 0 && s->T > 0 && s->L >= 0 && s->L <= s->T && s->cap >= s->T - s->L && s->mode >= 0 && s->mode <= 2 && s->T <= c->NPOS &&
@@ -666,7 +675,7 @@ int CC_API(cc_gpt2_param_offsets)(const cc_gpt2_cfg* cfg, int64_t* offs) {
 int64_t CC_API(cc_gpt2_ws_bytes)(const cc_gpt2_cfg* cfg, const cc_gpt2_shape* s) {
     if (!gpt2_cfg_ok(cfg) || !shape_ok(cfg, s)) return CC_ERR_SHAPE;
     Gpt2WS w;
-    gpt2_carve(cfg, s->B, s->T, s->T - s->L, s->mode, nullptr, w);
+    gpt2_carve(cfg, s, s->T - s->L, nullptr, w);
     return (int64_t)w.bytes;
 }
 
@@ -745,7 +754,7 @@ int CC_API(cc_gpt2_embed)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const fl
     Gpt2Off o;
     gpt2_offsets(c, o);
     Gpt2WS w;
-    gpt2_carve(c, s->B, s->T, s->T - s->L, s->mode, ws, w);
+    gpt2_carve(c, s, s->T - s->L, ws, w);
     CC_TRY(embed_concat(prefix, reinterpret_cast<const long long*>(tokens), s->cap, w32 + o.wte, w32 + o.wpe, w.x[0], s->B, s->L, s->T,
                         c->D, 0, S_(stream)));
     // embd dropout on inputs_embeds + position_embeds (hf GPT2Model.forward: self.drop)
@@ -758,7 +767,7 @@ int CC_API(cc_gpt2_embed_from)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, con
     Gpt2Off o;
     gpt2_offsets(c, o);
     Gpt2WS w;
-    gpt2_carve(c, s->B, s->T, s->T - s->L, s->mode, ws, w);
+    gpt2_carve(c, s, s->T - s->L, ws, w);
     return embed_concat(inputs_embeds, nullptr, 0, w32 + o.wte, w32 + o.wpe, w.x[0], s->B, s->T, s->T, c->D, 0, S_(stream));
 }
 
@@ -768,59 +777,35 @@ int CC_API(cc_gpt2_fwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const floa
     Gpt2Off o;
     gpt2_offsets(c, o);
     Gpt2WS w;
-    gpt2_carve(c, s->B, s->T, s->T - s->L, s->mode, ws, w);
-    X3_SCRATCH(w);
-    red_set_scratch(w.red);
+    gpt2_carve(c, s, s->T - s->L, ws, w);
+    Call cx = call_of(st, w);
     const int D = c->D, M = s->B * s->T, H = c->H, hd = D / H;
     const uint16_t* w16t = W16(w16, o.total);   // Conv1D weights transposed to [out,in]: every forward GEMM is NT
     for (int l = 0; l < c->NL; l++) {
         const auto& y = o.layer[l];
         // hf :262-310: x1 = x + c_proj(attn(c_attn(ln_1 x)))
-#if CC_OP == 2
-        const bool ximg = s->mode <= 1 && x3_img_on();          // no weight gradient reads the normalised rows: LayerNorm writes the GEMM operand image
-        if (ximg) x3_emit_image(w.xn1[l], D);
-#endif
         CC_TRY(ln_fwd(w.x[l], D, nullptr, w32 + y.l1w, w32 + y.l1b, w.xn1[l], nullptr, w.mean1[l], w.rstd1[l], M, D, st));
-#if CC_OP == 2
-        if (ximg) x3_expect_image(w.xn1[l]);
-#endif
-        CC_TRY(gemm_bf16out(0, 0, w.xn1[l], D, W16(w16t, y.aw), D, M, 3 * D, D, w.qkv[l], 3 * D, w32 + y.ab, 0, nullptr, st));
-#if CC_OP == 2
-        const bool aimg = ximg && attn_fwd_can_image(s->T, hd);      // the fp32-VALU attention pair: the backward recomputes what it needs from qkv
-        if (aimg) x3_emit_image(w.att[l], D);
-#endif
+        CC_TRY(gemm_bf16out(0, 0, w.xn1[l], D, W16(w16t, y.aw), D, M, 3 * D, D, w.qkv[l], 3 * D, w32 + y.ab, 0, nullptr, cx));
         CC_TRY(attn_fwd(w.qkv[l], s->B, s->T, H, hd, true, w.att[l], w.lse[l], st, make_drop(s->p_attn, s->drop_seed, DROP_ATTN, l)));
         {
             static const int tile_proj = env_tile("CC_TILE_PROJ");
             TileScope ts(tile_proj);
-#if CC_OP == 2
-            if (aimg) x3_expect_image(w.att[l]);
-#endif
-            CC_TRY(gemm_resid(0, 0, w.att[l], D, W16(w16t, y.pw), D, M, D, D, w.x1[l], w.x[l], D, w32 + y.pb, st,
+            CC_TRY(gemm_resid(0, 0, w.att[l], D, W16(w16t, y.pw), D, M, D, D, w.x1[l], w.x[l], D, w32 + y.pb, cx,
                               make_drop(s->p_resid, s->drop_seed, DROP_RESID_ATTN, l)));
         }
         // x = x1 + c_proj(gelu_new(c_fc(ln_2 x1)))   (hf :229-243)
-#if CC_OP == 2
-        if (ximg) x3_emit_image(w.xn2[l], D);
-#endif
         CC_TRY(ln_fwd(w.x1[l], D, nullptr, w32 + y.l2w, w32 + y.l2b, w.xn2[l], nullptr, w.mean2[l], w.rstd2[l], M, D, st));
         {
             static const int tile_fc = env_tile("CC_TILE_FC");
             TileScope ts(tile_fc);
             // act 3: the pre-activation slot receives gelu_new'(u) — one sigmoid serves both, and the backward's epilogue is a multiply
-#if CC_OP == 2
-            if (ximg) { x3_emit_image(w.hact[l], 4 * D); x3_expect_image(w.xn2[l]); }   // nobody but mlp.c_proj reads hact without a weight gradient: write its operand image directly
-#endif
             CC_TIMED(CC_SITE_GPT2_FC_FWD, st, gemm_bf16out(0, 0, w.xn2[l], D, W16(w16t, y.fw), D, M, 4 * D, D, w.hact[l], 4 * D, w32 + y.fb, (s->mode >= 1 && gelu_grad_fwd()) ? 3 : 2,
-                                                            s->mode >= 1 ? w.u[l] : nullptr, st));
+                                                            s->mode >= 1 ? w.u[l] : nullptr, cx));
         }
         {
             static const int tile_proj2 = env_tile("CC_TILE_PROJ2");
             TileScope ts(tile_proj2);
-#if CC_OP == 2
-            if (s->mode <= 1 && x3_img_on()) x3_expect_image(w.hact[l]);
-#endif
-            CC_TIMED(CC_SITE_GPT2_PROJ2_FWD, st, gemm_resid(0, 0, w.hact[l], 4 * D, W16(w16t, y.p2w), 4 * D, M, D, 4 * D, w.x[l + 1], w.x1[l], D, w32 + y.p2b, st,
+            CC_TIMED(CC_SITE_GPT2_PROJ2_FWD, st, gemm_resid(0, 0, w.hact[l], 4 * D, W16(w16t, y.p2w), 4 * D, M, D, 4 * D, w.x[l + 1], w.x1[l], D, w32 + y.p2b, cx,
                                                            make_drop(s->p_resid, s->drop_seed, DROP_RESID_MLP, l)));
         }
     }
@@ -836,12 +821,11 @@ int CC_API(cc_gpt2_logits)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const f
     Gpt2Off o;
     gpt2_offsets(c, o);
     Gpt2WS w;
-    gpt2_carve(c, s->B, s->T, s->T - s->L, s->mode, ws, w);
-    X3_SCRATCH(w);
-    red_set_scratch(w.red);
+    gpt2_carve(c, s, s->T - s->L, ws, w);
+    Call cx = call_of(st, w);
     const int D = c->D, M = s->B * s->T;
     CC_TRY(ln_fwd(w.x[c->NL], D, nullptr, w32 + o.lnf_w, w32 + o.lnf_b, w.hf16, nullptr, w.meanf, w.rstdf, M, D, st));
-    return gemm_f32out(0, 0, w.hf16, D, W16(w16, o.wte), D, M, Ns, D, logits, (int)ldl, nullptr, 0, 1.0f, 1, st);
+    return gemm_f32out(0, 0, w.hf16, D, W16(w16, o.wte), D, M, Ns, D, logits, (int)ldl, nullptr, 0, 1.0f, 1, cx);
 }
 
 int CC_API(cc_lmhead_ce_fwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const int64_t* tokens,
@@ -852,9 +836,8 @@ int CC_API(cc_lmhead_ce_fwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const
     gpt2_offsets(c, o);
     Gpt2WS w;
     const int cap = s->T - s->L;
-    gpt2_carve(c, s->B, s->T, cap, s->mode, ws, w);
-    X3_SCRATCH(w);
-    red_set_scratch(w.red);
+    gpt2_carve(c, s, cap, ws, w);
+    Call cx = call_of(st, w);
     const int D = c->D, Mc = s->B * cap, npart = c->Vp / 64;
     if (cap != s->cap) return CC_ERR_SHAPE;  // the loss consumes every token column (model.py:108-109)
     if (hipMemsetAsync(stats, 0, 2 * sizeof(float), st) != hipSuccess) return CC_ERR_LAUNCH;
@@ -864,10 +847,7 @@ int CC_API(cc_lmhead_ce_fwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const
     const bool ef = lm_exp_form(s);
     const op16_t* wte_rows = kX3 ? reinterpret_cast<const op16_t*>(w32 + o.wte) : W16(w16, o.wte);      // rows read elementwise: bf16x3 takes the fp32 master
     if (ef) CC_TRY(lm_tgt_ref(w.hf16, wte_rows, D, w.target, w.cref, Mc, st));
-#if CC_OP == 2
-    if (ef) x3_emit_image(w.logits16, c->Vp);
-#endif
-    CC_TIMED(CC_SITE_LMHEAD_FWD, st, gemm_lmhead(w.hf16, D, W16(w16, o.wte), D, Mc, c->Vp, c->V, D, w.logits16, c->Vp, w.pmax, w.psum, npart, w.target, w.tgt_logit, st,
+    CC_TIMED(CC_SITE_LMHEAD_FWD, st, gemm_lmhead(w.hf16, D, W16(w16, o.wte), D, Mc, c->Vp, c->V, D, lm_logits(c, s, w.logits16), c->Vp, w.pmax, w.psum, npart, w.target, w.tgt_logit, cx,
                                                  ef ? w.cref : nullptr));
     CC_TRY(ce_rows(w.pmax, w.psum, npart, w.target, ef ? w.cref : w.tgt_logit, w.lse_row, w.row_loss, stats, Mc, st));   // cref IS the target logit
     return CC_OK;
@@ -881,9 +861,8 @@ int CC_API(cc_lmhead_ce_bwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const
     gpt2_offsets(c, o);
     Gpt2WS w;
     const int cap = s->T - s->L;
-    gpt2_carve(c, s->B, s->T, cap, s->mode, ws, w);
-    X3_SCRATCH(w);
-    red_set_scratch(w.red);
+    gpt2_carve(c, s, cap, ws, w);
+    Call cx = call_of(st, w);
     const int D = c->D, Mc = s->B * cap, M = s->B * s->T;
     const bool full = s->mode == 2;
     // exponential form: logits16 holds E = exp(logit - cref); d logits = r E - w onehot is never written — the row factors go into the
@@ -891,52 +870,39 @@ int CC_API(cc_lmhead_ce_bwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const
     const bool ef = lm_exp_form(s);
     const LmFix fix{w.lmfac, w.target, kX3 ? reinterpret_cast<const op16_t*>(w32 + o.wte) : W16(w16, o.wte)};
     if (ef) CC_TRY(lm_rowfac(w.cref, w.lse_row, w.target, denom, loss_scale, w.lmfac, Mc, st));
-    const act_t* dlog = w.logits16;            // the A operand of the input-gradient GEMM
-#if CC_OP == 2
-    // frozen LM: nothing but that GEMM reads d logits -> the softmax-gradient pass writes its [hi | hi | lo] operand image straight into the
-    // call's operand scratch (sized for exactly this image, gpt2_carve) instead of fp32 values a split pass would re-read
-    op16_t* dimg = (!ef && !full && x3_img_on()) ? x3_scratch_block(x3_img(Mc, c->Vp)) : nullptr;
-    if (ef) dimg = reinterpret_cast<op16_t*>(w.logits16);        // exponential form: the forward GEMM wrote E there as the operand image
-    if (dimg) dlog = reinterpret_cast<const act_t*>(dimg);
+    const Act lg = lm_logits(c, s, w.logits16);
+    ActIn dlog = lg;                    // the A operand of the input-gradient GEMM (bf16x3 exponential form: E, written as its operand image)
+    // bf16x3, frozen LM: nothing but that GEMM reads d logits -> the softmax-gradient pass writes its [hi | hi | lo] operand image straight
+    // into the call's operand scratch (sized for exactly this image, gpt2_carve) instead of fp32 values a split pass would re-read
+    op16_t* dimg = (kX3 && !ef && !full && x3_img_on()) ? x3_scratch_block(cx, x3_img(Mc, c->Vp)) : nullptr;
+    if (dimg) dlog = ActIn(reinterpret_cast<const act_t*>(dimg), c->Vp);
     if (!ef) CC_TRY(ce_dlogits(w.logits16, c->Vp, c->V, w.target, w.lse_row, denom, loss_scale, Mc, st, dimg));
-#else
-    if (!ef) CC_TRY(ce_dlogits(w.logits16, c->Vp, c->V, w.target, w.lse_row, denom, loss_scale, Mc, st));
-#endif
     // d hf = dlogits · wte   ([Mc,Vp] x [Vp(k), D(n)])
     // K = Vp is deep and the output narrow: K slices over the idle CUs, slabs parked in du16 (free until the first layer's backward)
     const auto lm_dgrad = [&]() {
-#if CC_OP == 2
-        if (dimg) x3_expect_image(dlog);
-#endif
-        const int rc = gemm_nt_deepk(dlog, c->Vp, W16(w16, o.total + o.wte), c->Vp, Mc, D, c->Vp, w.dhf16, D, reinterpret_cast<float*>(w.du16),
-                                     (size_t)M * 4 * D * sizeof(act_t), st, ef ? &fix : nullptr);
+        const int rc = gemm_nt_deepk(dlog, c->Vp, W16(w16, o.total + o.wte), c->Vp, Mc, D, c->Vp, w.dhf16, D, reinterpret_cast<float*>(w.du16.p),
+                                     (size_t)M * 4 * D * sizeof(act_t), cx, ef ? &fix : nullptr);
         if (rc != CC_ERR_SHAPE) return rc;
-#if CC_OP == 2
-        if (dimg) x3_expect_image(dlog);
-#endif
-        const int rc2 = gemm_bf16out(0, 0, dlog, c->Vp, W16(w16, o.total + o.wte), c->Vp, Mc, D, c->Vp, w.dhf16, D, nullptr, 0, nullptr, st);
+        const int rc2 = gemm_bf16out(0, 0, dlog, c->Vp, W16(w16, o.total + o.wte), c->Vp, Mc, D, c->Vp, w.dhf16, D, nullptr, 0, nullptr, cx);
         return (rc2 != CC_OK || !ef) ? rc2 : lm_dgrad_fix(w.dhf16, w.lmfac, w.target, fix.wte, D, Mc, st);
     };
     CC_TIMED(CC_SITE_LMHEAD_DGRAD, st, lm_dgrad());
     if (full) {      // tied lm_head: d wte += dlogits^T hf  (= E^T (r hf) - onehot^T (w hf) in the exponential form)
         if (ef) {
             CC_TRY(lm_scale_rows(w.hf16, w.lmfac, w.hfs16, D, Mc, st));
-            CC_TRY(gemm_wgrad(w.logits16, c->Vp, w.hfs16, D, c->Vp, D, Mc, g32 + o.wte, D, w.wg_scratch, st));
+            CC_TRY(gemm_wgrad(lg, c->Vp, w.hfs16, D, c->Vp, D, Mc, g32 + o.wte, D, w.wg_scratch, cx));
             ScatterSrc oh;          // the one-hot term: d wte[target] -= w hf, rows with w == 0 left out
             oh.ids32 = w.target; oh.act = w.hf16; oh.fac = w.lmfac;
             CC_TRY(scatter_rows(oh, Mc, D, c->Vp, g32 + o.wte, w.scat, st));
         } else {
-            CC_TRY(gemm_wgrad(w.logits16, c->Vp, w.hf16, D, c->Vp, D, Mc, g32 + o.wte, D, w.wg_scratch, st));
+            CC_TRY(gemm_wgrad(lg, c->Vp, w.hf16, D, c->Vp, D, Mc, g32 + o.wte, D, w.wg_scratch, cx));
         }
     }
     if (hipMemsetAsync(w.dx32, 0, (size_t)M * D * sizeof(float), st) != hipSuccess) return CC_ERR_LAUNCH;
-    size_t dx16_bytes = (size_t)M * D * sizeof(act_t);
-#if CC_OP == 2
-    if (gpt2_bwd_images(s)) { dx16_bytes = (size_t)M * D * 3 * sizeof(op16_t); x3_emit_image(w.dx16, D); }     // the top layer's backward reads it as an operand image
-#endif
-    if (hipMemsetAsync(w.dx16, 0, dx16_bytes, st) != hipSuccess) return CC_ERR_LAUNCH;
+    const size_t dx16_bytes = (size_t)M * D * (w.dx16.img ? 3 * sizeof(op16_t) : sizeof(act_t));     // (an image where the top layer's backward reads one)
+    if (hipMemsetAsync(w.dx16.p, 0, dx16_bytes, st) != hipSuccess) return CC_ERR_LAUNCH;
     CC_TRY(ln_bwd(w.dhf16, w.x[c->NL], D, w.row_map, w.meanf, w.rstdf, w32 + o.lnf_w, nullptr, w.dx32, w.dx16, full ? g32 + o.lnf_w : nullptr,
-                  full ? g32 + o.lnf_b : nullptr, Mc, D, st));
+                  full ? g32 + o.lnf_b : nullptr, Mc, D, cx));
     return CC_OK;
 }
 
@@ -948,21 +914,17 @@ int CC_API(cc_gpt2_logits_bwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, con
     Gpt2Off o;
     gpt2_offsets(c, o);
     Gpt2WS w;
-    gpt2_carve(c, s->B, s->T, s->T, s->mode, ws, w);      // L == 0: the loss-side buffers are sized for all B*T rows
-    X3_SCRATCH(w);
-    red_set_scratch(w.red);
+    gpt2_carve(c, s, s->T, ws, w);      // L == 0: the loss-side buffers are sized for all B*T rows
+    Call cx = call_of(st, w);
     const int D = c->D, M = s->B * s->T;
     const bool full = s->mode == 2;
     CC_TRY(f32_to_op16_pad(dlogits, ldl, c->V, w.logits16, c->Vp, M, st));
     // d hf = dlogits · wte ([M,Vp] x [Vp(k), D(n)]); tied lm_head: d wte += dlogits^T hf (hf16 = the rows cc_gpt2_logits normalised)
-    CC_TRY(gemm_bf16out(0, 0, w.logits16, c->Vp, W16(w16, o.total + o.wte), c->Vp, M, D, c->Vp, w.dhf16, D, nullptr, 0, nullptr, st));
-    if (full) CC_TRY(gemm_wgrad(w.logits16, c->Vp, w.hf16, D, c->Vp, D, M, g32 + o.wte, D, w.wg_scratch, st));
+    CC_TRY(gemm_bf16out(0, 0, w.logits16, c->Vp, W16(w16, o.total + o.wte), c->Vp, M, D, c->Vp, w.dhf16, D, nullptr, 0, nullptr, cx));
+    if (full) CC_TRY(gemm_wgrad(w.logits16, c->Vp, w.hf16, D, c->Vp, D, M, g32 + o.wte, D, w.wg_scratch, cx));
     if (hipMemsetAsync(w.dx32, 0, (size_t)M * D * sizeof(float), st) != hipSuccess) return CC_ERR_LAUNCH;
-#if CC_OP == 2
-    if (gpt2_bwd_images(s)) x3_emit_image(w.dx16, D);
-#endif
     CC_TRY(ln_bwd(w.dhf16, w.x[c->NL], D, nullptr, w.meanf, w.rstdf, w32 + o.lnf_w, nullptr, w.dx32, w.dx16, full ? g32 + o.lnf_w : nullptr,
-                  full ? g32 + o.lnf_b : nullptr, M, D, st));
+                  full ? g32 + o.lnf_b : nullptr, M, D, cx));
     CC_TRY(CC_API(cc_gpt2_bwd_range)(c, s, w32, w16, ws, nullptr, nullptr, g32, c->NL, 0, stream));
     if (dx0 && hipMemcpyAsync(dx0, w.dx32, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return CC_ERR_LAUNCH;
     return CC_OK;
@@ -983,84 +945,56 @@ int CC_API(cc_gpt2_bwd_range)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, cons
     Gpt2Off o;
     gpt2_offsets(c, o);
     Gpt2WS w;
-    gpt2_carve(c, s->B, s->T, s->T - s->L, s->mode, ws, w);
-    X3_SCRATCH(w);
-    red_set_scratch(w.red);
+    gpt2_carve(c, s, s->T - s->L, ws, w);
+    Call cx = call_of(st, w);
     const int D = c->D, M = s->B * s->T, H = c->H, hd = D / H, D3 = 3 * D, D4 = 4 * D;
     const bool full = s->mode == 2;
     WgradBatch wb;          // full finetune: a layer's four weight gradients as one grouped launch + one slab reduce
     wb.defer = full;
     WgradBatch* wbp = full ? &wb : nullptr;
+    // the weight gradients and bias column sums below read these four as plain activations (.p)
+    if (full && (w.dx16.img || w.dx16b.img || w.du16.img || w.dqkv16.img)) return CC_ERR_STATE;
     // The 16-bit copy of the residual gradient that feeds a c_proj's backward GEMMs is the dropout-masked one, and the c_proj's bias
     // gradient is its column sum.  Both are produced by the LayerNorm backward that writes the copy (ln_bwd dmask / dcol) — except for
     // the top layer, whose copy comes from ln_f's row-mapped backward and is masked / summed by separate launches.
-#if CC_OP == 2
-    // frozen LM, no dropout: the 16-bit gradient copies are read by input-gradient GEMMs only -> their producers write operand images
-    const bool bimg = gpt2_bwd_images(s);
-#endif
     for (int l = l_hi - 1; l >= l_lo; l--) {
         const auto& y = o.layer[l];
         const bool top = l == c->NL - 1;
         // mlp.c_proj (Conv1D [4D, D]): y = hact W + b
-        if (top) CC_TRY(dropout_bf16(w.dx16, (size_t)M * D, make_drop(s->p_resid, s->drop_seed, DROP_RESID_MLP, l), st));
+        if (top) CC_TRY(dropout_bf16(w.dx16.p, (size_t)M * D, make_drop(s->p_resid, s->drop_seed, DROP_RESID_MLP, l), st));
         if (full) {
-            CC_TRY(gemm_wgrad(w.hact[l], D4, w.dx16, D, D4, D, M, g32 + y.p2w, D, w.wg_scratch, st, wbp));
-            if (top) CC_TRY(colsum_bf16(w.dx16, D, M, D, g32 + y.p2b, st));
+            CC_TRY(gemm_wgrad(w.hact[l], D4, w.dx16.p, D, D4, D, M, g32 + y.p2w, D, w.wg_scratch, cx, wbp));
+            if (top) CC_TRY(colsum_bf16(w.dx16.p, D, M, D, g32 + y.p2b, cx));
         }
         {
             static const int tile_dact = env_tile("CC_TILE_DACT");
             TileScope ts(tile_dact);
-#if CC_OP == 2
-            if (!full && x3_img_on()) x3_emit_image(w.du16, D4);                     // frozen LM: du is read by c_fc's input-gradient GEMM only
-#endif
-#if CC_OP == 2
-            if (bimg) x3_expect_image(w.dx16);                        // written as an image by the LayerNorm backward above it (or the lm_head's)
-#endif
-            CC_TRY(gemm_dact(0, 0, w.dx16, D, W16(w16, y.p2w), D, M, D4, D, w.du16, D4, w.u[l], gelu_grad_fwd() ? 3 : 2, st));
+            CC_TRY(gemm_dact(0, 0, w.dx16, D, W16(w16, y.p2w), D, M, D4, D, w.du16, D4, w.u[l], gelu_grad_fwd() ? 3 : 2, cx));
         }
         // mlp.c_fc (Conv1D [D, 4D])
         if (full) {
-            CC_TRY(gemm_wgrad(w.xn2[l], D, w.du16, D4, D, D4, M, g32 + y.fw, D4, w.wg_scratch, st, wbp));
-            CC_TRY(colsum_bf16(w.du16, D4, M, D4, g32 + y.fb, st));
+            CC_TRY(gemm_wgrad(w.xn2[l], D, w.du16.p, D4, D, D4, M, g32 + y.fw, D4, w.wg_scratch, cx, wbp));
+            CC_TRY(colsum_bf16(w.du16.p, D4, M, D4, g32 + y.fb, cx));
         }
-#if CC_OP == 2
-        if (!full && x3_img_on()) x3_expect_image(w.du16);
-#endif
-        CC_TIMED(CC_SITE_GPT2_FC_DGRAD, st, gemm_bf16out(0, 0, w.du16, D4, W16(w16, y.fw), D4, M, D, D4, w.dxn16, D, nullptr, 0, nullptr, st));
-#if CC_OP == 2
-        if (bimg) x3_emit_image(w.dx16b, D);
-#endif
+        CC_TIMED(CC_SITE_GPT2_FC_DGRAD, st, gemm_bf16out(0, 0, w.du16, D4, W16(w16, y.fw), D4, M, D, D4, w.dxn16, D, nullptr, 0, nullptr, cx));
         CC_TRY(ln_bwd(w.dxn16, w.x1[l], D, nullptr, w.mean2[l], w.rstd2[l], w32 + y.l2w, w.dx32, w.dx32, w.dx16b, full ? g32 + y.l2w : nullptr,
-                      full ? g32 + y.l2b : nullptr, M, D, st, full ? g32 + y.pb : nullptr,
+                      full ? g32 + y.l2b : nullptr, M, D, cx, full ? g32 + y.pb : nullptr,
                       make_drop(s->p_resid, s->drop_seed, DROP_RESID_ATTN, l)));
         // attn.c_proj (Conv1D [D, D])
-        if (full) CC_TRY(gemm_wgrad(w.att[l], D, w.dx16b, D, D, D, M, g32 + y.pw, D, w.wg_scratch, st, wbp));
-#if CC_OP == 2
-        if (bimg) x3_expect_image(w.dx16b);
-#endif
-        CC_TRY(gemm_bf16out(0, 0, w.dx16b, D, W16(w16, y.pw), D, M, D, D, w.datt16, D, nullptr, 0, nullptr, st));
-#if CC_OP == 2
-        const bool qimg = bimg && attn_bwd_can_image(s->T, hd);
-        if (qimg) x3_emit_image(w.dqkv16, D3);
-#endif
-        CC_TRY(attn_bwd(w.qkv[l], w.datt16, w.att[l], w.lse[l], w.adelta, s->B, s->T, H, hd, true, w.dqkv16, st,
+        if (full) CC_TRY(gemm_wgrad(w.att[l], D, w.dx16b.p, D, D, D, M, g32 + y.pw, D, w.wg_scratch, cx, wbp));
+        CC_TRY(gemm_bf16out(0, 0, w.dx16b, D, W16(w16, y.pw), D, M, D, D, w.datt16, D, nullptr, 0, nullptr, cx));
+        CC_TRY(attn_bwd(w.qkv[l], w.datt16, w.att[l].p, w.lse[l], w.adelta, s->B, s->T, H, hd, true, w.dqkv16, st,
                         make_drop(s->p_attn, s->drop_seed, DROP_ATTN, l)));
         // attn.c_attn (Conv1D [D, 3D])
         if (full) {
-            CC_TRY(gemm_wgrad(w.xn1[l], D, w.dqkv16, D3, D, D3, M, g32 + y.aw, D3, w.wg_scratch, st, wbp));
-            CC_TRY(colsum_bf16(w.dqkv16, D3, M, D3, g32 + y.ab, st));
+            CC_TRY(gemm_wgrad(w.xn1[l], D, w.dqkv16.p, D3, D, D3, M, g32 + y.aw, D3, w.wg_scratch, cx, wbp));
+            CC_TRY(colsum_bf16(w.dqkv16.p, D3, M, D3, g32 + y.ab, cx));
         }
-#if CC_OP == 2
-        if (qimg) x3_expect_image(w.dqkv16);
-#endif
-        CC_TRY(gemm_bf16out(0, 0, w.dqkv16, D3, W16(w16, y.aw), D3, M, D, D3, w.dxn16, D, nullptr, 0, nullptr, st));
+        CC_TRY(gemm_bf16out(0, 0, w.dqkv16, D3, W16(w16, y.aw), D3, M, D, D3, w.dxn16, D, nullptr, 0, nullptr, cx));
         // deferred weight gradients: dx16 (masked layer-input gradient), du16, dx16b, dqkv16 are all still intact here
         if (full) CC_TRY(wgrad_flush(wb, st));
-#if CC_OP == 2
-        if (bimg) x3_emit_image(w.dx16, D);
-#endif
         CC_TRY(ln_bwd(w.dxn16, w.x[l], D, nullptr, w.mean1[l], w.rstd1[l], w32 + y.l1w, w.dx32, w.dx32, w.dx16, full ? g32 + y.l1w : nullptr,
-                      full ? g32 + y.l1b : nullptr, M, D, st, (full && l > 0) ? g32 + o.layer[l - 1].p2b : nullptr,
+                      full ? g32 + y.l1b : nullptr, M, D, cx, (full && l > 0) ? g32 + o.layer[l - 1].p2b : nullptr,
                       l > 0 ? make_drop(s->p_resid, s->drop_seed, DROP_RESID_MLP, l - 1) : Drop()));
     }
     if (l_lo > 0) return CC_OK;
@@ -1074,7 +1008,7 @@ int CC_API(cc_gpt2_bwd_range)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, cons
             e.f32 = w.dx32 + (size_t)s->L * D; e.rpb = s->T - s->L; e.bstride = (size_t)s->T * D;
             CC_TRY(scatter_rows(e, s->B * (s->T - s->L), D, c->Vp, g32 + o.wte, w.scat, st));
         }
-        CC_TRY(batch_sum(w.dx32, (size_t)s->T * D, g32 + o.wpe, s->T * D, s->B, st));
+        CC_TRY(batch_sum(w.dx32, (size_t)s->T * D, g32 + o.wpe, s->T * D, s->B, cx));
     }
     return CC_OK;
 }
@@ -1121,7 +1055,8 @@ int CC_API(cc_loss_scale_update)(float* state, float* found_inf, float growth, f
 int CC_API(cc_gemm_op16_f32)(int32_t al, int32_t bl, const uint16_t* A, int32_t lda, const uint16_t* B, int32_t ldb, int32_t M, int32_t N, int32_t K,
                      float* C, int32_t ldc, const float* bias, int32_t ksplit, void* stream) {
     if (!A || !B || !C || kX3) return CC_ERR_ARG;      // (bf16x3 GEMMs need a workspace for their operand images: no bare hook)
-    return gemm_f32out(al, bl, reinterpret_cast<const act_t*>(A), lda, B, ldb, M, N, K, C, ldc, ksplit > 1 ? nullptr : bias, ksplit > 1 ? 2 : 0, 1.0f, ksplit, S_(stream));
+    Call cx{S_(stream)};
+    return gemm_f32out(al, bl, reinterpret_cast<const act_t*>(A), lda, B, ldb, M, N, K, C, ldc, ksplit > 1 ? nullptr : bias, ksplit > 1 ? 2 : 0, 1.0f, ksplit, cx);
 }
 
 int CC_API(cc_sample_step)(const float* logits, int32_t R, int32_t V, int32_t ld, float temperature, int32_t top_k, float top_p, int32_t mode,
@@ -1145,7 +1080,8 @@ int64_t CC_API(cc_wgrad_scratch_bytes)(void) { return (int64_t)WGRAD_SCRATCH_BYT
 int CC_API(cc_gemm_wgrad)(const uint16_t* X, int32_t ldx, const uint16_t* Y, int32_t ldy, int32_t Mw, int32_t Nw, int32_t K, float* dW, int32_t ldw,
                   float* scratch, void* stream) {
     if (!X || !Y || !dW || kX3) return CC_ERR_ARG;
-    return gemm_wgrad(reinterpret_cast<const act_t*>(X), ldx, reinterpret_cast<const act_t*>(Y), ldy, Mw, Nw, K, dW, ldw, scratch, S_(stream));
+    Call cx{S_(stream)};
+    return gemm_wgrad(reinterpret_cast<const act_t*>(X), ldx, reinterpret_cast<const act_t*>(Y), ldy, Mw, Nw, K, dW, ldw, scratch, cx);
 }
 
 int CC_API(cc_layernorm_fwd)(const float* x, const float* gamma, const float* beta, uint16_t* y, float* mean, float* rstd, int32_t rows, int32_t D,
@@ -1154,15 +1090,7 @@ int CC_API(cc_layernorm_fwd)(const float* x, const float* gamma, const float* be
     return ln_fwd(x, D, nullptr, gamma, beta, reinterpret_cast<act_t*>(y), nullptr, mean, rstd, rows, D, S_(stream));
 }
 
-// ---- reduction hooks: the scratch is this call's only; it is cleared on return so that no later call can find a pointer into a buffer
-// the caller may since have freed
-namespace {
-struct RedScope {
-    explicit RedScope(float* p) { red_set_scratch(p); }
-    ~RedScope() { red_set_scratch(nullptr); }
-};
-}  // namespace
-
+// ---- reduction hooks: red_ws is the call's reduction scratch
 int64_t CC_API(cc_red_scratch_floats)(void) { return (int64_t)RED_SCRATCH_FLOATS; }
 
 int CC_API(cc_layernorm_bwd)(const uint16_t* dy, const float* x, int32_t ldx, const int32_t* row_map, const float* mean, const float* rstd,
@@ -1170,15 +1098,15 @@ int CC_API(cc_layernorm_bwd)(const uint16_t* dy, const float* x, int32_t ldx, co
                      int32_t D, float* red_ws, void* stream) {
     // (bf16x3: dx16 would be fp32, or a 3-wide operand image when a GEMM asked for one: no bare hook)
     if (!dy || !x || !mean || !rstd || !gamma || !dx32 || !dgamma != !dbeta || kX3) return CC_ERR_ARG;
-    RedScope rs(red_ws);
+    Call cx{S_(stream), red_ws};
     return ln_bwd(reinterpret_cast<const act_t*>(dy), x, ldx, row_map, mean, rstd, gamma, dres, dx32, reinterpret_cast<act_t*>(dx16), dgamma,
-                  dbeta, rows, D, S_(stream), dcol);
+                  dbeta, rows, D, cx, dcol);
 }
 
 int CC_API(cc_colsum_bf16)(const uint16_t* X, int32_t ld, int32_t M, int32_t N, float* out, float* red_ws, void* stream) {
     if (!X || !out || kX3) return CC_ERR_ARG;
-    RedScope rs(red_ws);
-    return colsum_bf16(reinterpret_cast<const act_t*>(X), ld, M, N, out, S_(stream));
+    Call cx{S_(stream), red_ws};
+    return colsum_bf16(reinterpret_cast<const act_t*>(X), ld, M, N, out, cx);
 }
 
 int CC_API(cc_colsum_multi)(const uint16_t* const* X_host, float* const* out_host, int32_t n, int32_t ld, int32_t M, int32_t N, float* red_ws,
@@ -1189,14 +1117,14 @@ int CC_API(cc_colsum_multi)(const uint16_t* const* X_host, float* const* out_hos
         if (!X_host[i] || !out_host[i]) return CC_ERR_ARG;
         b.add(reinterpret_cast<const act_t*>(X_host[i]), out_host[i]);
     }
-    RedScope rs(red_ws);
-    return colsum_bf16_multi(b, ld, M, N, S_(stream));
+    Call cx{S_(stream), red_ws};
+    return colsum_bf16_multi(b, ld, M, N, cx);
 }
 
 int CC_API(cc_batch_sum)(const float* src, int64_t src_stride, float* dst, int32_t len, int32_t B, float* red_ws, void* stream) {
     if (!src || !dst || len < 0 || src_stride < len) return CC_ERR_ARG;
-    RedScope rs(red_ws);
-    return batch_sum(src, (size_t)src_stride, dst, len, B, S_(stream));
+    Call cx{S_(stream), red_ws};
+    return batch_sum(src, (size_t)src_stride, dst, len, B, cx);
 }
 
 int CC_API(cc_attention_fwd)(const uint16_t* qkv, int32_t B, int32_t S, int32_t H, int32_t hd, int32_t causal, uint16_t* out, float* lse, void* stream) {

@@ -55,6 +55,30 @@ typedef float act_t;
 constexpr bool kX3 = false;
 typedef op16_t act_t;
 #endif
+// What a C-ABI call hands the launchers that need scratch, where the others take its stream: built on the entry point's stack from the
+// workspace it carved, so no launcher can see another call's.
+struct Call {
+    hipStream_t st = nullptr;
+    float* red = nullptr;      // RED_SCRATCH_FLOATS floats for the fixed-order cross-block reductions (kernels.h); none -> CC_ERR_STATE there
+    char* x3 = nullptr;        // bf16x3: where the operand images of the GEMM being launched are split (gemm_api.h x3_operand)
+    size_t x3_bytes = 0;
+    size_t x3_used = 0;        //         fill mark: the images of one GEMM live there at a time
+};
+// An activation buffer and what it holds.  img = 0: act_t elements.  img = n (bf16x3 build only): the [hi | hi | lo] operand image, rows
+// of 3 n 16-bit elements, of the n-deep A operand of the GEMM that reads it.  Whoever owns the buffer decides once; its producer writes
+// what the handle says and its consumer reads what the handle says.  ActIn is the read-only view a GEMM wrapper takes as its A operand.
+struct Act {
+    act_t* p = nullptr;
+    int img = 0;
+    Act() = default;
+    Act(act_t* p_, int img_ = 0) : p(p_), img(img_) {}
+};
+struct ActIn {
+    const act_t* p;
+    int img;
+    ActIn(const act_t* p_, int img_ = 0) : p(p_), img(img_) {}
+    ActIn(const Act& a) : p(a.p), img(a.img) {}
+};
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2_hw;
 #if CC_OP == 1

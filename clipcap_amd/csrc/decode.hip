@@ -1173,9 +1173,7 @@ static int decode_fwd_impl(const cc_gpt2_cfg* c, int32_t R, int32_t Tn, int32_t 
     hipStream_t st = S_(stream);
     DecWS w;
     dec_carve(c, R, Tn, ws, w);
-#if CC_OP == 2
-    x3_set_scratch(w.x3, w.x3_bytes);
-#endif
+    Call cx{st, nullptr, w.x3, w.x3_bytes};
     constexpr int PL = kX3 ? 3 : 1;          // operand-arena addressing as in api.hip (W16): bf16x3 weights own 3x the elements at 3x the offset
     const int D = c->D, M = R * Tn, H = c->H, hd = D / H;
     // arena offsets (same order as api.hip::gpt2_offsets)
@@ -1280,7 +1278,7 @@ static int decode_fwd_impl(const cc_gpt2_cfg* c, int32_t R, int32_t Tn, int32_t 
         SkinnyFuse fq;
         if (f_qkv) { fq.kcache = kc; fq.vcache = vc; fq.Tn = Tn; fq.pos0 = pos0; fq.ctx_max = ctx_max; }
         fq.bimg = bimg ? bimg + aw : nullptr;
-        CC_TRY(gemm_nt_skinny(w.xn, D, w16t + (size_t)PL * aw, D, M, 3 * D, D, w32 + ab, 0, nullptr, nullptr, w.qkv, 3 * D, w.scratch, w.scratch_bytes, st, &fq));
+        CC_TRY(gemm_nt_skinny(w.xn, D, w16t + (size_t)PL * aw, D, M, 3 * D, D, w32 + ab, 0, nullptr, nullptr, w.qkv, 3 * D, w.scratch, w.scratch_bytes, cx, &fq));
         if (grp_attn) {
             const int ng = R / group, app = f_qkv ? 0 : 1;
 #define CC_GRP(G_)                                                                                                                            \
@@ -1305,11 +1303,11 @@ static int decode_fwd_impl(const cc_gpt2_cfg* c, int32_t R, int32_t Tn, int32_t 
         SkinnyFuse f2;
         if (f_d) { f2.ln_gamma = w32 + l2w; f2.ln_beta = w32 + l2b; f2.ln_out16 = w.xn; }
         f2.bimg = bimg ? bimg + pw : nullptr;
-        CC_TRY(gemm_nt_skinny(w.att, D, w16t + (size_t)PL * pw, D, M, D, D, w32 + pb, 0, w.x, w.x1, nullptr, D, w.scratch, w.scratch_bytes, st, &f2));
+        CC_TRY(gemm_nt_skinny(w.att, D, w16t + (size_t)PL * pw, D, M, D, D, w32 + pb, 0, w.x, w.x1, nullptr, D, w.scratch, w.scratch_bytes, cx, &f2));
         if (!f_d) CC_TRY(ln_fwd(w.x1, D, nullptr, w32 + l2w, w32 + l2b, w.xn, nullptr, nullptr, nullptr, M, D, st));
         SkinnyFuse f3;
         f3.bimg = bimg ? bimg + fw : nullptr;
-        CC_TRY(gemm_nt_skinny(w.xn, D, w16t + (size_t)PL * fw, D, M, 4 * D, D, w32 + fb, 2, nullptr, nullptr, w.hact, 4 * D, w.scratch, w.scratch_bytes, st, &f3));
+        CC_TRY(gemm_nt_skinny(w.xn, D, w16t + (size_t)PL * fw, D, M, 4 * D, D, w32 + fb, 2, nullptr, nullptr, w.hact, 4 * D, w.scratch, w.scratch_bytes, cx, &f3));
         // mlp.c_proj + residual (+ fused ln_1 of the next layer: its parameters sit right behind this layer's in the arena)
         // (after the LAST layer p points at ln_f: with one new position per row the finishing pass normalises straight into hf)
         const bool last = l + 1 == c->NL;
@@ -1317,7 +1315,7 @@ static int decode_fwd_impl(const cc_gpt2_cfg* c, int32_t R, int32_t Tn, int32_t 
         SkinnyFuse f1;
         if (f_next) { f1.ln_gamma = w32 + p; f1.ln_beta = w32 + p + D; f1.ln_out16 = last ? w.hf : w.xn; }      // p now points at layer l+1's ln_1.weight (or ln_f)
         f1.bimg = bimg ? bimg + p2w : nullptr;
-        CC_TRY(gemm_nt_skinny(w.hact, 4 * D, w16t + (size_t)PL * p2w, 4 * D, M, D, 4 * D, w32 + p2b, 0, w.x1, w.x, nullptr, D, w.scratch, w.scratch_bytes, st, &f1));
+        CC_TRY(gemm_nt_skinny(w.hact, 4 * D, w16t + (size_t)PL * p2w, 4 * D, M, D, 4 * D, w32 + p2b, 0, w.x1, w.x, nullptr, D, w.scratch, w.scratch_bytes, cx, &f1));
         xn_ready = f_next && !last;
         hf_ready = f_next && last;
     }
@@ -1328,9 +1326,9 @@ static int decode_fwd_impl(const cc_gpt2_cfg* c, int32_t R, int32_t Tn, int32_t 
     }
     if (lpart) {      // logits + per-(row, 64-column block) softmax partials for cc_beam_step_p
         const int npart = (Ns + 63) / 64;
-        CC_TRY(gemm_logits_part(w.hf, D, w16 + (size_t)PL * wte, D, R, Ns, c->V, D, logits, (int)ldl, lpart, lpart + (size_t)R * npart, npart, st));
+        CC_TRY(gemm_logits_part(w.hf, D, w16 + (size_t)PL * wte, D, R, Ns, c->V, D, logits, (int)ldl, lpart, lpart + (size_t)R * npart, npart, cx));
     } else {
-        CC_TRY(gemm_f32out(0, 0, w.hf, D, w16 + (size_t)PL * wte, D, R, Ns, D, logits, (int)ldl, nullptr, 0, 1.0f, 1, st));
+        CC_TRY(gemm_f32out(0, 0, w.hf, D, w16 + (size_t)PL * wte, D, R, Ns, D, logits, (int)ldl, nullptr, 0, 1.0f, 1, cx));
     }
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }

@@ -10,61 +10,56 @@ namespace CC_NS {
 // are test / microbenchmark hooks living in shared.cpp.
 // al/bl: 0 = K-contiguous operand ([rows][K]), 1 = K-strided operand ([K][rows]).  See gemm.hip.h.
 //
-// Operand types.  A is an ACTIVATION (act_t), B a WEIGHT from the 16-bit operand arena, C / pre / aux activations again.  In the bf16 /
+// Operand types.  A is an ACTIVATION (ActIn), B a WEIGHT from the 16-bit operand arena, C / pre / aux activations again.  In the bf16 /
 // fp16 builds act_t is the 16-bit operand type and the calls are what they say.  In the bf16x3 build (common.hip.h) activations are
-// fp32: every wrapper below first splits A into its [hi | hi | lo] operand image in the call's scratch (x3_set_scratch, set by the
-// C-ABI entry point from its workspace), B is the pre-split [hi | lo | hi] image the weight sync left in the operand arena
+// fp32: a wrapper splits a plain A (A.img == 0) into its [hi | hi | lo] operand image in the call's scratch (Call::x3) and reads an A
+// that already is that image (A.img == K) in place; B is the pre-split [hi | lo | hi] image the weight sync left in the operand arena
 // (row stride 3 * ldb), and the unchanged NT kernels run with K' = 3 K.  Callers pass the LOGICAL lda / ldb / K in every build.
-// Only al = bl = 0 is supported there.
-int gemm_bf16out(int al, int bl, const act_t* A, int lda, const op16_t* B, int ldb, int M, int N, int K, act_t* C, int ldc,
-                 const float* bias, int act, act_t* pre, hipStream_t st);
-int gemm_resid(int al, int bl, const act_t* A, int lda, const op16_t* B, int ldb, int M, int N, int K, float* out, const float* res,
-               int ld, const float* bias, hipStream_t st, Drop drop = Drop());
+// Only al = bl = 0 is supported there.  An output C with C.img == n leaves the epilogue as the image of an n-deep A operand (epi_store8).
+int gemm_bf16out(int al, int bl, ActIn A, int lda, const op16_t* B, int ldb, int M, int N, int K, Act C, int ldc,
+                 const float* bias, int act, act_t* pre, Call& cx);
+int gemm_resid(int al, int bl, ActIn A, int lda, const op16_t* B, int ldb, int M, int N, int K, float* out, const float* res,
+               int ld, const float* bias, Call& cx, Drop drop = Drop());
 // mode 0 store (+bias), 1 add, 2 atomic add (required when ksplit > 1)
-int gemm_f32out(int al, int bl, const act_t* A, int lda, const op16_t* B, int ldb, int M, int N, int K, float* C, int ldc,
-                const float* bias, int mode, float alpha, int ksplit, hipStream_t st);
-int gemm_dact(int al, int bl, const act_t* A, int lda, const op16_t* B, int ldb, int M, int N, int K, act_t* C, int ldc,
-              const act_t* aux, int act, hipStream_t st);
-// cref != nullptr: exponential form (C = exp(logit - cref[row]), see gemm.hip.h EpiLMHead)
-int gemm_lmhead(const act_t* A, int lda, const op16_t* B, int ldb, int M, int Vp, int V, int K, act_t* C, int ldc, float* pmax,
-                float* psum, int npart, const int* target, float* tgt_logit, hipStream_t st, const float* cref = nullptr);
+int gemm_f32out(int al, int bl, ActIn A, int lda, const op16_t* B, int ldb, int M, int N, int K, float* C, int ldc,
+                const float* bias, int mode, float alpha, int ksplit, Call& cx);
+int gemm_dact(int al, int bl, ActIn A, int lda, const op16_t* B, int ldb, int M, int N, int K, Act C, int ldc,
+              const act_t* aux, int act, Call& cx);
+// cref != nullptr: exponential form (C = exp(logit - cref[row]), see gemm.hip.h EpiLMHead); only that form writes C as an image
+int gemm_lmhead(ActIn A, int lda, const op16_t* B, int ldb, int M, int Vp, int V, int K, Act C, int ldc, float* pmax,
+                float* psum, int npart, const int* target, float* tgt_logit, Call& cx, const float* cref = nullptr);
 
 // decode lm_head: fp32 logits [M][ldc] (Ns columns stored, Ns % 8 == 0) + per-(row, 64-column block) softmax partials over the V real
 // columns (pmax / psum [M][npart], npart >= ceil(Ns / 64)) — gemm.hip.h EpiLogits
-int gemm_logits_part(const act_t* A, int lda, const op16_t* B, int ldb, int M, int Ns, int V, int K, float* C, int ldc, float* pmax, float* psum,
-                     int npart, hipStream_t st);
+int gemm_logits_part(ActIn A, int lda, const op16_t* B, int ldb, int M, int Ns, int V, int K, float* C, int ldc, float* pmax, float* psum,
+                     int npart, Call& cx);
 
 #if CC_OP == 2
-// bf16x3: scratch for the operand images of the GEMM being launched (stream order makes reuse by the next GEMM safe).  Thread-local:
-// the C ABI stays re-entrant across host threads / streams; every compute entry point sets it from its own workspace.
-void x3_set_scratch(void* base, size_t bytes);
-// split `rows` x `width` fp32 (row stride ld) into the scratch: form 0 = [hi | hi | lo] (A side), 1 = [hi | lo | hi] (B side).
-// first = true restarts the scratch (one GEMM's operands live there at a time).  Returns nullptr (rc set) when it does not fit.
-const op16_t* x3_operand(const float* src, size_t ld, int rows, int width, int form, bool first, hipStream_t st, int* rc);
-// Producer-written operand images (round 4): x3_expect_image(p) before a GEMM wrapper call says "the A pointer p of the next call already
-// IS its [hi | hi | lo] image" (written by the previous GEMM's epilogue, epi_store8) — the split pass is skipped; x3_emit_image(p, n) says
-// "write the output C == p of the next gemm_bf16out / gemm_dact call as the image of an n-wide A operand".  Thread-local one-shot hints
-// (consumed by the next matching call), like the scratch: the C ABI stays re-entrant.
-op16_t* x3_scratch_block(size_t bytes);
-void x3_expect_image(const void* a);
-bool x3_take_expected(const void* a);
-void x3_emit_image(const void* c, int width);
-int x3_take_emit(const void* c);
-#define CC_X3_NT(A, lda, ldb, M, K, A16, al, bl, st)                                      \
-    {                                                                                     \
-        if ((al) || (bl)) return CC_ERR_ARG;                                              \
-        if (x3_take_expected(A)) {                                                        \
-            A16 = reinterpret_cast<const op16_t*>(A);                                     \
-        } else {                                                                          \
-            int rc_ = CC_OK;                                                              \
-            A16 = x3_operand(A, (size_t)(lda), M, K, 0, true, st, &rc_);                  \
-            if (!A16) return rc_;                                                         \
-        }                                                                                 \
-        lda = 3 * (K); ldb = 3 * (ldb); K = 3 * (K);                                      \
-    }
-#else
-#define CC_X3_NT(A, lda, ldb, M, K, A16, al, bl, st) A16 = A;
+// split `rows` x `width` fp32 (row stride ld) into the call's image scratch: form 0 = [hi | hi | lo] (A side), 1 = [hi | lo | hi] (B side).
+// first = true restarts the scratch (one GEMM's operands live there at a time; stream order makes reuse by the next GEMM safe).
+// Returns nullptr (rc set, CC_ERR_STATE) when the call has no scratch or the image does not fit.
+const op16_t* x3_operand(Call& cx, const float* src, size_t ld, int rows, int width, int form, bool first, int* rc);
 #endif
+// the whole image scratch as one block, for a producer kernel that writes the next GEMM's A image itself; nullptr when it does not fit
+inline op16_t* x3_scratch_block(const Call& cx, size_t bytes) { return (cx.x3 && bytes <= cx.x3_bytes) ? reinterpret_cast<op16_t*>(cx.x3) : nullptr; }
+// The A operand of an NT wrapper as its kernel reads it (A16; lda / ldb / K become the image's in the bf16x3 build).
+inline int nt_operand(Call& cx, ActIn A, int al, int bl, int M, int& lda, int& ldb, int& K, const op16_t*& A16) {
+#if CC_OP == 2
+    if (al || bl || (A.img && A.img != K)) return CC_ERR_ARG;
+    if (A.img) {
+        A16 = reinterpret_cast<const op16_t*>(A.p);
+    } else {
+        int rc = CC_OK;
+        A16 = x3_operand(cx, A.p, (size_t)lda, M, K, 0, true, &rc);
+        if (!A16) return rc;
+    }
+    lda = 3 * K; ldb = 3 * ldb; K = 3 * K;
+#else
+    if (A.img) return CC_ERR_ARG;
+    A16 = A.p;
+#endif
+    return CC_OK;
+}
 // weight gradient dW[Mw][Nw] += X^T Y with X stored [K][Mw], Y stored [K][Nw].  Split-K for occupancy: the K slices
 // write fp32 slabs into `scratch` (plain stores) and a second kernel folds them into dW — fp32 atomics on the same
 // tile from 7-14 concurrent blocks measured 3x slower than the whole GEMM (profiles/r01_b_gemm_microbench.md).
@@ -92,8 +87,10 @@ struct WgradBatch {
     float* scratch = nullptr;
 };
 int wgrad_flush(WgradBatch& b, hipStream_t st);
-int gemm_wgrad(const act_t* X, int ldx, const act_t* Y, int ldy, int Mw, int Nw, int K, float* dW, int ldw, float* scratch,
-               hipStream_t st, WgradBatch* batch = nullptr);
+// bf16x3: X and Y are split into the call's image scratch; an X that already is its [hi | hi | lo] image (X.img == Mw: the form the
+// input-gradient GEMM of the same tensor reads as its A operand, split once for both) is read in place.
+int gemm_wgrad(ActIn X, int ldx, const act_t* Y, int ldy, int Mw, int Nw, int K, float* dW, int ldw, float* scratch,
+               Call& cx, WgradBatch* batch = nullptr);
 // Skinny-M NT GEMMs (KV-cached decode: M = beams x samples, a handful of 128x128 tiles): split K over blockIdx.z so every CU
 // streams a distinct slice of the weights, fp32 slabs in `scratch`, then ONE finishing kernel sums the slabs and applies the
 // epilogue (bias, gelu_new, fp32 residual, bf16 / fp32 stores).  Falls back to the single-pass GEMM when the grid is already wide.
@@ -109,16 +106,16 @@ struct SkinnyFuse {
     const op16_t* bimg = nullptr;      // the weight's fragment-ordered image (k_skinny_image; cc_decode_image): B is then loaded global -> VGPR where the form allows
 };
 int skinny_image(const op16_t* W, op16_t* img, int N, int K, hipStream_t st);
-int gemm_nt_skinny(const act_t* A, int lda, const op16_t* B, int ldb, int M, int N, int K, const float* bias, int act, const float* res,
-                   float* out32, act_t* out16, int ldo, float* scratch, size_t scratch_bytes, hipStream_t st,
+int gemm_nt_skinny(ActIn A, int lda, const op16_t* B, int ldb, int M, int N, int K, const float* bias, int act, const float* res,
+                   float* out32, act_t* out16, int ldo, float* scratch, size_t scratch_bytes, Call& cx,
                    const SkinnyFuse* fuse = nullptr);
 // Narrow output, very deep K (the lm_head input gradient: [B*cap, Vp] x [Vp, D] -> 10240 x 768 over K = 50304): the 256 x 256 kernel on
 // 120 tiles leaves half the chip idle, so K is cut into as many slices as fill the CUs (fp32 slabs in `scratch`), and one elementwise
 // pass sums the slabs into the 16-bit output.  Returns CC_ERR_SHAPE when the shape does not call for it (caller then uses gemm_bf16out).
 // fix (optional): out[m][n] = fac[2m] * acc - fac[2m+1] * wte[target[m]][n] — the lm_head input gradient of the exponential form
 struct LmFix { const float* fac; const int* target; const op16_t* wte; };
-int gemm_nt_deepk(const act_t* A, int lda, const op16_t* B, int ldb, int M, int N, int K, act_t* out16, int ldo, float* scratch,
-                  size_t scratch_bytes, hipStream_t st, const LmFix* fix = nullptr);
+int gemm_nt_deepk(ActIn A, int lda, const op16_t* B, int ldb, int M, int N, int K, act_t* out16, int ldo, float* scratch,
+                  size_t scratch_bytes, Call& cx, const LmFix* fix = nullptr);
 int skinny_single_min_tiles();   // grids of at least this many 128 x 128 tiles skip split-K (CC_SKINNY_SINGLE; tuning knob)
 // whether gemm_nt_skinny will take the slab + row-finish path for this problem (the only path that supports SkinnyFuse)
 bool gemm_nt_skinny_can_fuse(int M, int N, int K, size_t scratch_bytes);

@@ -1,16 +1,17 @@
 #include "gemm.hip.h"
 #include "gemm_api.h"
 namespace CC_NS {
-int gemm_bf16out(int al, int bl, const act_t* A, int lda, const op16_t* B, int ldb, int M, int N, int K, act_t* C, int ldc,
-                 const float* bias, int act, act_t* pre, hipStream_t st) {
+int gemm_bf16out(int al, int bl, ActIn A, int lda, const op16_t* B, int ldb, int M, int N, int K, Act Co, int ldc,
+                 const float* bias, int act, act_t* pre, Call& cx) {
+    const hipStream_t st = cx.st;
+    act_t* const C = Co.p;
     cc_shared::ProfScope _all(cc_shared::SITE_ALL_GEMMS, st, 2.0 * M * N * (double)K);
     if ((ldc & 7) || (N & 7)) return CC_ERR_SHAPE;
     const op16_t* A16;
-    CC_X3_NT(A, lda, ldb, M, K, A16, al, bl, st);
+    const int rca = nt_operand(cx, A, al, bl, M, lda, ldb, K, A16);
+    if (rca != CC_OK) return rca;
     EpiBF16 e{C, pre, bias, ldc, M, N, act};
-#if CC_OP == 2
-    e.img = x3_take_emit(C);
-#endif
+    e.img = Co.img;
     static const bool nt = []() { const char* v = cc_lab_env("CC_PRE_NT"); return v && atoi(v) != 0; }();      // experiment switch
     e.pre_nt = nt;
     // plain launches (no activation, no pre-activation copy, no operand image): the functor without run-time switches

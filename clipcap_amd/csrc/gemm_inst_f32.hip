@@ -12,11 +12,13 @@ static int gemm_f32out_op(int al, int bl, const op16_t* A, int lda, const op16_t
     EpiF32 e{C, bias, ldc, M, N, mode, alpha};
     return launch_gemm(al, bl, A, lda, B, ldb, M, N, K, ksplit, e, st);
 }
-int gemm_f32out(int al, int bl, const act_t* A, int lda, const op16_t* B, int ldb, int M, int N, int K, float* C, int ldc,
-                const float* bias, int mode, float alpha, int ksplit, hipStream_t st) {
+int gemm_f32out(int al, int bl, ActIn A, int lda, const op16_t* B, int ldb, int M, int N, int K, float* C, int ldc,
+                const float* bias, int mode, float alpha, int ksplit, Call& cx) {
+    const hipStream_t st = cx.st;
     cc_shared::ProfScope _all(cc_shared::SITE_ALL_GEMMS, st, 2.0 * M * N * (double)K);
     const op16_t* A16;
-    CC_X3_NT(A, lda, ldb, M, K, A16, al, bl, st);
+    const int rca = nt_operand(cx, A, al, bl, M, lda, ldb, K, A16);
+    if (rca != CC_OK) return rca;
     return gemm_f32out_op(al, bl, A16, lda, B, ldb, M, N, K, C, ldc, bias, mode, alpha, ksplit, st);
 }
 __global__ __launch_bounds__(256) void k_slab_reduce(const float* __restrict__ slabs, size_t slab_elems, int ks, int Nw, float* __restrict__ dW,
@@ -171,8 +173,9 @@ static int wgrad_reduce(const float* slabs, size_t slab, int ks, int Nw, float* 
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 
-int gemm_wgrad(const act_t* Xa, int ldx, const act_t* Ya, int ldy, int Mw, int Nw, int K, float* dW, int ldw, float* scratch,
-               hipStream_t st, WgradBatch* batch) {
+int gemm_wgrad(ActIn Xa, int ldx, const act_t* Ya, int ldy, int Mw, int Nw, int K, float* dW, int ldw, float* scratch,
+               Call& cx, WgradBatch* batch) {
+    const hipStream_t st = cx.st;
     if ((Nw & 7) || (ldw & 3)) return CC_ERR_SHAPE;
     const double flops = 2.0 * Mw * Nw * (double)K;
 #if CC_OP == 2
@@ -180,18 +183,20 @@ int gemm_wgrad(const act_t* Xa, int ldx, const act_t* Ya, int ldy, int Mw, int N
     // rows (hi, hi, lo) per source row, the [hi | lo | hi] image of Y rows (hi, lo, hi): the unchanged kernels contract over K' = 3K.
     // The images live in the call's scratch, so nothing can be deferred to a grouped launch.
     if (Mw & 7) return CC_ERR_SHAPE;
+    if (Xa.img && Xa.img != Mw) return CC_ERR_ARG;
     int rcx = CC_OK;
     // the first operand (the output gradient) has the [hi | hi | lo] form the input-gradient GEMM of the same tensor reads as its A operand:
-    // a caller that has split it once for both passes it as an image (x3_expect_image)
-    const bool ximg = x3_take_expected(Xa);
-    const op16_t* X = ximg ? reinterpret_cast<const op16_t*>(Xa) : x3_operand(Xa, (size_t)ldx, K, Mw, 0, true, st, &rcx);
+    // a caller that has split it once for both passes that image
+    const bool ximg = Xa.img != 0;
+    const op16_t* X = ximg ? reinterpret_cast<const op16_t*>(Xa.p) : x3_operand(cx, Xa.p, (size_t)ldx, K, Mw, 0, true, &rcx);
     if (!X) return rcx;
-    const op16_t* Y = x3_operand(Ya, (size_t)ldy, K, Nw, 1, ximg, st, &rcx);
+    const op16_t* Y = x3_operand(cx, Ya, (size_t)ldy, K, Nw, 1, ximg, &rcx);
     if (!Y) return rcx;
     ldx = Mw; ldy = Nw; K *= 3;
     const bool may_defer = false;
 #else
-    const op16_t* X = Xa;
+    if (Xa.img) return CC_ERR_ARG;
+    const op16_t* X = Xa.p;
     const op16_t* Y = Ya;
     const bool may_defer = true;
 #endif
@@ -438,8 +443,9 @@ __global__ __launch_bounds__(256) void k_deepk_finish_lm(const float* __restrict
     }
 }
 
-int gemm_nt_deepk(const act_t* Aa, int lda, const op16_t* B, int ldb, int M, int N, int K, act_t* out16, int ldo, float* scratch,
-                  size_t scratch_bytes, hipStream_t st, const LmFix* fix) {
+int gemm_nt_deepk(ActIn Aa, int lda, const op16_t* B, int ldb, int M, int N, int K, act_t* out16, int ldo, float* scratch,
+                  size_t scratch_bytes, Call& cx, const LmFix* fix) {
+    const hipStream_t st = cx.st;
     static const int knob = []() { const char* e = cc_lab_env("CC_DEEPK"); return e ? atoi(e) : -1; }();   // 0 = off, n > 0 = force n slices
     if (knob == 0 || g_gemm_tile_mode == 0 || !scratch || (N & 7) || (ldo & 7) || (K % 64) || (lda & 7) || (ldb & 7)) return CC_ERR_SHAPE;
     const long tiles = (long)((M + H_BM - 1) / H_BM) * ((N + H_BN - 1) / H_BN);
@@ -451,7 +457,8 @@ int gemm_nt_deepk(const act_t* Aa, int lda, const op16_t* B, int ldb, int M, int
     if (ks < 2 || tiles > 128) return CC_ERR_SHAPE;
     cc_shared::ProfScope _all(cc_shared::SITE_ALL_GEMMS, st, 2.0 * M * N * (double)K);
     const op16_t* A;
-    CC_X3_NT(Aa, lda, ldb, M, K, A, 0, 0, st);
+    const int rca = nt_operand(cx, Aa, 0, 0, M, lda, ldb, K, A);
+    if (rca != CC_OK) return rca;
     EpiF32 e{scratch, nullptr, N, M, N, 3, 1.0f};
     e.zstride = slab;
     // tile order: an XCD's share of the grid (tiles / 8 consecutive logical tiles per K slice) should hold whole row panels, so that the
@@ -496,12 +503,14 @@ int skinny_image(const op16_t* W, op16_t* img, int N, int K, hipStream_t st) {
 }
 #endif
 
-int gemm_nt_skinny(const act_t* Aa, int lda, const op16_t* B, int ldb, int M, int N, int K, const float* bias, int act, const float* res,
-                   float* out32, act_t* out16, int ldo, float* scratch, size_t scratch_bytes, hipStream_t st, const SkinnyFuse* fuse) {
+int gemm_nt_skinny(ActIn Aa, int lda, const op16_t* B, int ldb, int M, int N, int K, const float* bias, int act, const float* res,
+                   float* out32, act_t* out16, int ldo, float* scratch, size_t scratch_bytes, Call& cx, const SkinnyFuse* fuse) {
+    const hipStream_t st = cx.st;
     cc_shared::ProfScope _all(cc_shared::SITE_ALL_GEMMS, st, 2.0 * M * N * (double)K);
     if ((N & 7) || (ldo & 7)) return CC_ERR_SHAPE;
     const op16_t* A;
-    CC_X3_NT(Aa, lda, ldb, M, K, A, 0, 0, st);
+    const int rca = nt_operand(cx, Aa, 0, 0, M, lda, ldb, K, A);
+    if (rca != CC_OK) return rca;
     const int tiles = ((M + G_BM - 1) / G_BM) * ((N + G_BN - 1) / G_BN);
     const size_t slab = (size_t)M * N;
     const bool can_slab = scratch && slab && (K % G_BK) == 0 && scratch_bytes >= slab * sizeof(float);

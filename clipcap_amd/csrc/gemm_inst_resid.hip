@@ -1,12 +1,14 @@
 #include "gemm.hip.h"
 #include "gemm_api.h"
 namespace CC_NS {
-int gemm_resid(int al, int bl, const act_t* A, int lda, const op16_t* B, int ldb, int M, int N, int K, float* out, const float* res,
-               int ld, const float* bias, hipStream_t st, Drop drop) {
+int gemm_resid(int al, int bl, ActIn A, int lda, const op16_t* B, int ldb, int M, int N, int K, float* out, const float* res,
+               int ld, const float* bias, Call& cx, Drop drop) {
+    const hipStream_t st = cx.st;
     cc_shared::ProfScope _all(cc_shared::SITE_ALL_GEMMS, st, 2.0 * M * N * (double)K);
     if ((ld & 7) || (N & 7)) return CC_ERR_SHAPE;
     const op16_t* A16;
-    CC_X3_NT(A, lda, ldb, M, K, A16, al, bl, st);
+    const int rca = nt_operand(cx, A, al, bl, M, lda, ldb, K, A16);
+    if (rca != CC_OK) return rca;
     EpiResid e{out, res, bias, ld, M, N, drop};
     // accumulators initialised from the residual (256-row kernels only read the flag): not with residual dropout, whose mask scales
     // acc + bias but not the residual; CC_RESID_INIT=0 is the A/B switch

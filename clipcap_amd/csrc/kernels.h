@@ -15,11 +15,10 @@ int slice_f32_to_bf16(const float* src, size_t src_stride, act_t* dst, size_t ds
 int broadcast_rows(float* dst, size_t dst_stride, const float* src, int len, int B, hipStream_t st);
 int add_rows(float* dst, size_t dst_stride, const float* add, int len, int B, hipStream_t st);
 // Reductions across blocks (batch_sum, ln_bwd's parameter gradients, colsum_bf16*) write per-block partials into the call's reduction
-// scratch and fold them in a fixed order, so a gradient is the same bit for bit from run to run (fp32 atomics are not).  Every C-ABI
-// entry that reaches them sets the scratch first (RED_SCRATCH_FLOATS floats of its workspace); without it they return CC_ERR_STATE.
+// scratch and fold them in a fixed order, so a gradient is the same bit for bit from run to run (fp32 atomics are not).  They take the
+// Call, whose `red` is RED_SCRATCH_FLOATS floats of the entry point's workspace; when they need it and it is null: CC_ERR_STATE.
 constexpr size_t RED_SCRATCH_FLOATS = size_t(1) << 20;
-void red_set_scratch(float* base);
-int batch_sum(const float* src, size_t src_stride, float* dst, int len, int B, hipStream_t st);
+int batch_sum(const float* src, size_t src_stride, float* dst, int len, int B, Call& cx);
 int copy_rows(const float* src, size_t src_stride, float* dst, size_t dst_stride, int len, int B, hipStream_t st);
 
 int transpose_bf16(const op16_t* src, op16_t* dst, int R, int C, hipStream_t st);
@@ -31,25 +30,28 @@ struct TransposeBatch {
 };
 int transpose_bf16_multi(const TransposeBatch& b, hipStream_t st);   // up to 32 matrices in one launch
 
-int ln_fwd(const float* x, int ldx, const int* row_map, const float* gamma, const float* beta, act_t* y, float* y32, float* mean,
+// Outputs of type Act (common.hip.h): a handle with img != 0 is written as the operand image of the GEMM that reads it (bf16x3 build);
+// a producer that cannot do that for the shape it is given returns CC_ERR_STATE (ln_bwd with dcol / dmask / ldx != D, attn_* outside
+// attn_*_can_image).
+int ln_fwd(const float* x, int ldx, const int* row_map, const float* gamma, const float* beta, Act y, float* y32, float* mean,
            float* rstd, int rows, int D, hipStream_t st);
 int ln_bwd(const act_t* dy, const float* x, int ldx, const int* row_map, const float* mean, const float* rstd, const float* gamma,
-           const float* dres, float* dx32, act_t* dx16, float* dgamma, float* dbeta, int rows, int D, hipStream_t st,
+           const float* dres, float* dx32, Act dx16, float* dgamma, float* dbeta, int rows, int D, Call& cx,
            float* dcol = nullptr, Drop dmask = Drop());
 // dcol (needs dgamma, dx16, no row_map): += column sums of the 16-bit dx16 (a bias gradient).  dmask: dropout mask applied to the
 // 16-bit copy dx16 only (element index row * D + col; dx32 stays unmasked) — the residual dropout of the c_proj that consumes dx16.
-int colsum_bf16(const act_t* X, int ld, int M, int N, float* out, hipStream_t st);
+int colsum_bf16(const act_t* X, int ld, int M, int N, float* out, Call& cx);
 struct ColsumBatch { const act_t* X[32]; float* out[32]; int n = 0; void add(const act_t* x, float* o) { X[n] = x; out[n] = o; n++; } };
-int colsum_bf16_multi(const ColsumBatch& b, int ld, int M, int N, hipStream_t st);      // out[i][c] += sum_r X[i][r][c] for n equally shaped matrices, one launch
+int colsum_bf16_multi(const ColsumBatch& b, int ld, int M, int N, Call& cx);      // out[i][c] += sum_r X[i][r][c] for n equally shaped matrices, one launch
 
 int attn_probs(const act_t* qkv, int B, int S, int H, int hd, float* out, hipStream_t st);
-int attn_fwd(const act_t* qkv, int B, int S, int H, int hd, bool causal, act_t* out, float* lse, hipStream_t st, Drop drop = Drop());
+int attn_fwd(const act_t* qkv, int B, int S, int H, int hd, bool causal, Act out, float* lse, hipStream_t st, Drop drop = Drop());
 // o: forward output (for delta = rowsum(dO*O)); delta: fp32 scratch [B*H*S].  Both may be null -> VALU kernel.
 int attn_bwd(const act_t* qkv, const act_t* dout, const act_t* o, const float* lse, float* delta, int B, int S, int H, int hd, bool causal,
-             act_t* dqkv, hipStream_t st, Drop drop = Drop());
+             Act dqkv, hipStream_t st, Drop drop = Drop());
 // in-place dropout of an fp32 / bf16 buffer of n elements (n % 4 == 0 / n % 8 == 0): x[i] *= keep(i) / (1 - p)
-bool attn_fwd_can_image(int S, int hd);      // bf16x3: attn_fwd will honour x3_emit_image(out) (and the backward will not need the fp32 output)
-bool attn_bwd_can_image(int S, int hd);      // bf16x3: attn_bwd will honour x3_emit_image(dqkv) for this shape
+bool attn_fwd_can_image(int S, int hd);      // bf16x3: attn_fwd can write `out` as an operand image (and the backward will not need the fp32 output)
+bool attn_bwd_can_image(int S, int hd);      // bf16x3: attn_bwd can write dqkv as an operand image for this shape
 int dropout_f32(float* x, size_t n, Drop drop, hipStream_t st);
 int dropout_bf16(act_t* x, size_t n, Drop drop, hipStream_t st);
 int dropout_mask_u8(unsigned char* out, size_t n, Drop drop, hipStream_t st);   // test hook: out[i] = keep(i)

@@ -127,11 +127,7 @@ int add_rows(float* dst, size_t dst_stride, const float* add, int len, int B, hi
 }
 
 // ---- deterministic cross-block reductions (kernels.h): per-block partials in the call's scratch, folded in a fixed order ----
-namespace {
-thread_local float* g_red = nullptr;
-}  // namespace
-void red_set_scratch(float* base) { g_red = base; }
-static float* red_scratch(size_t floats) { return floats <= RED_SCRATCH_FLOATS ? g_red : nullptr; }
+static float* red_scratch(const Call& cx, size_t floats) { return floats <= RED_SCRATCH_FLOATS ? cx.red : nullptr; }
 
 // partials part[y][s][j] (y < gridDim.y groups of S slices x n columns): out[y * k + j / m][j % m] += sum over s of part[y][s][j], the
 // slices summed in one fixed order: per chunk of 256 slices, lane g (of 16) of a column loads s = g, g + 16, ..., g + 240 at once and adds
@@ -192,13 +188,14 @@ __global__ __launch_bounds__(256) void k_batch_sum(const float* __restrict__ src
     if (gridDim.y == 1) dst[i] += s;
     else part[(size_t)blockIdx.y * len + i] = s;
 }
-int batch_sum(const float* src, size_t src_stride, float* dst, int len, int B, hipStream_t st) {
+int batch_sum(const float* src, size_t src_stride, float* dst, int len, int B, Call& cx) {
+    const hipStream_t st = cx.st;
     if (!len || B <= 0) return CC_OK;
     const int colb = (len + 255) / 256;
     int slices = std::max(1, std::min(B / 8, 1024 / colb));        // ~1k blocks, at least 8 rows per slice
     const int per = (B + slices - 1) / slices;
     slices = (B + per - 1) / per;
-    float* part = slices > 1 ? red_scratch((size_t)slices * len) : nullptr;
+    float* part = slices > 1 ? red_scratch(cx, (size_t)slices * len) : nullptr;
     if (slices > 1 && !part) return CC_ERR_STATE;
     hipLaunchKernelGGL(k_batch_sum, dim3(colb, slices), dim3(256), 0, st, src, src_stride, dst, len, B, per, part);
     if (slices == 1) return CC_OK;
@@ -382,16 +379,15 @@ __global__ __launch_bounds__(256) void k_ln_fwd(const float* __restrict__ x, int
         }
     }
 }
-int ln_fwd(const float* x, int ldx, const int* row_map, const float* gamma, const float* beta, act_t* y, float* y32,
+int ln_fwd(const float* x, int ldx, const int* row_map, const float* gamma, const float* beta, Act yo, float* y32,
            float* mean, float* rstd, int rows, int D, hipStream_t st) {
     if (D > LN_MAXV * 256 || (D & 3) || (ldx & 3)) return CC_ERR_SHAPE;
     if (rows <= 0) return CC_OK;
     const int rpb = D <= 1024 ? 8 : 4;      // rows per block: 4 waves x (2 rows for NV <= 4, else 1)
     const dim3 gr((rows + rpb - 1) / rpb);
-    int img = 0;
-#if CC_OP == 2
-    img = x3_take_emit(y) ? 1 : 0;            // the caller asked for y as its consumer GEMM's operand image (gemm_api.h x3_emit_image)
-#endif
+    act_t* const y = yo.p;
+    const int img = yo.img ? 1 : 0;           // y leaves as its consumer GEMM's operand image
+    if (img && (!kX3 || yo.img != D)) return CC_ERR_STATE;
 #define LN_FWD(NV) hipLaunchKernelGGL(k_ln_fwd<NV>, gr, dim3(256), 0, st, x, ldx, row_map, gamma, beta, y, y32, mean, rstd, rows, D, 1e-5f, img)
     if (D <= 256) LN_FWD(1); else if (D <= 512) LN_FWD(2); else if (D <= 768) LN_FWD(3); else if (D <= 1024) LN_FWD(4); else LN_FWD(LN_MAXV);
 #undef LN_FWD
@@ -551,8 +547,10 @@ __global__ __launch_bounds__(NW * 64) void k_ln_bwd(const act_t* __restrict__ dy
     }
 }
 int ln_bwd(const act_t* dy, const float* x, int ldx, const int* row_map, const float* mean, const float* rstd,
-           const float* gamma, const float* dres, float* dx32, act_t* dx16, float* dgamma, float* dbeta, int rows, int D,
-           hipStream_t st, float* dcol, Drop dmask) {
+           const float* gamma, const float* dres, float* dx32, Act dxo, float* dgamma, float* dbeta, int rows, int D,
+           Call& cx, float* dcol, Drop dmask) {
+    const hipStream_t st = cx.st;
+    act_t* const dx16 = dxo.p;
     if (D > LN_MAXV * 256 || (D & 3) || (ldx & 3) || (dcol && (!dgamma || !dx16 || row_map)) || (dmask.thresh && (row_map || ldx != D)))
         return CC_ERR_SHAPE;
     if (rows <= 0) return CC_OK;
@@ -562,16 +560,11 @@ int ln_bwd(const act_t* dy, const float* x, int ldx, const int* row_map, const f
     static const int dg_grid = []() { const char* e = cc_lab_env("CC_LNBWD_GRID"); return e ? atoi(e) : 256; }();   // tuning knob
     const int nvec = dcol ? 3 : 2;
     const int grid = std::min((rows + nw - 1) / nw, dgamma ? std::max(1, std::min(dg_grid, (int)(RED_SCRATCH_FLOATS / ((size_t)nvec * D)))) : 8192);
-    float* part = dgamma ? red_scratch((size_t)grid * nvec * D) : nullptr;
+    float* part = dgamma ? red_scratch(cx, (size_t)grid * nvec * D) : nullptr;
     if (dgamma && !part) return CC_ERR_STATE;
     const size_t sh = dgamma ? (size_t)2 * nw * D * sizeof(float) : 0;
-    int img = 0;
-#if CC_OP == 2
-    if (x3_take_emit(dx16)) {                 // the caller's next GEMM will read dx16 as an operand image: either honour it or fail loudly
-        if (ldx != D || dcol || dmask.thresh) return CC_ERR_STATE;
-        img = 1;
-    }
-#endif
+    const int img = dxo.img ? 1 : 0;          // the next GEMM reads dx16 as an operand image: either write one or fail loudly
+    if (img && (!kX3 || dxo.img != D || ldx != D || dcol || dmask.thresh)) return CC_ERR_STATE;
 #define LN_BWD(NV, DG, NW) hipLaunchKernelGGL((k_ln_bwd<NV, DG, NW>), dim3(grid), dim3(NW * 64), sh, st, dy, x, ldx, row_map, mean, rstd, gamma, dres, dx32, dx16, dgamma, dbeta, dcol, rows, D, dmask, img, part)
 #define LN_BWD_D(DG, NW) { if (D <= 256) LN_BWD(1, DG, NW); else if (D <= 512) LN_BWD(2, DG, NW); else if (D <= 768) LN_BWD(3, DG, NW); else if (D <= 1024) LN_BWD(4, DG, NW); else LN_BWD(LN_MAXV, DG, NW); }
     if (dgamma && nw == 8) LN_BWD_D(true, 8) else if (dgamma) LN_BWD_D(true, 4) else LN_BWD_D(false, 4)
@@ -647,14 +640,15 @@ __global__ __launch_bounds__(256) void k_colsum_bf16_multi(ColsumBatch b, int ld
         }
     }
 }
-int colsum_bf16_multi(const ColsumBatch& b, int ld, int M, int N, hipStream_t st) {
+int colsum_bf16_multi(const ColsumBatch& b, int ld, int M, int N, Call& cx) {
+    const hipStream_t st = cx.st;
     if ((N & 7) || (ld & 7) || b.n < 0 || b.n > 32) return CC_ERR_SHAPE;
     if (M <= 0 || N <= 0 || b.n == 0) return CC_OK;
     const int cb = (N + 63) / 64;
     int slices = std::max(1, std::min((M + 255) / 256, std::max(1, 1024 / (cb * b.n))));
     const int rps = ((M + slices - 1) / slices + 31) / 32 * 32;
     slices = (M + rps - 1) / rps;
-    float* part = slices > 1 ? red_scratch((size_t)b.n * slices * N) : nullptr;
+    float* part = slices > 1 ? red_scratch(cx, (size_t)b.n * slices * N) : nullptr;
     if (slices > 1 && !part) return CC_ERR_STATE;
     hipLaunchKernelGGL(k_colsum_bf16_multi, dim3(cb, slices, b.n), dim3(256), 0, st, b, ld, M, N, rps, part);
     if (hipGetLastError() != hipSuccess) return CC_ERR_LAUNCH;
@@ -664,14 +658,15 @@ int colsum_bf16_multi(const ColsumBatch& b, int ld, int M, int N, hipStream_t st
     o.m = N; o.k = 1;
     return fold_partials(part, slices, N, b.n, o, st);
 }
-int colsum_bf16(const act_t* X, int ld, int M, int N, float* out, hipStream_t st) {
+int colsum_bf16(const act_t* X, int ld, int M, int N, float* out, Call& cx) {
+    const hipStream_t st = cx.st;
     if ((N & 7) || (ld & 7)) return CC_ERR_SHAPE;
     if (M <= 0 || N <= 0) return CC_OK;
     const int cb = (N + 63) / 64;
     int slices = std::max(1, std::min((M + 255) / 256, 1024 / cb));
     const int rps = ((M + slices - 1) / slices + 31) / 32 * 32;
     slices = (M + rps - 1) / rps;
-    float* part = slices > 1 ? red_scratch((size_t)slices * N) : nullptr;
+    float* part = slices > 1 ? red_scratch(cx, (size_t)slices * N) : nullptr;
     if (slices > 1 && !part) return CC_ERR_STATE;
     hipLaunchKernelGGL(k_colsum_bf16, dim3(cb, slices), dim3(256), 0, st, X, ld, M, N, out, rps, part);
     if (slices == 1) return CC_OK;
@@ -2332,15 +2327,11 @@ static bool attn_f32mfma_ok(int S, int hd, bool bwd) {
     }
 #endif   // CC_OP == 2
 
-int attn_fwd(const act_t* qkv, int B, int S, int H, int hd, bool causal, act_t* out, float* lse, hipStream_t st, Drop drop) {
+int attn_fwd(const act_t* qkv, int B, int S, int H, int hd, bool causal, Act outo, float* lse, hipStream_t st, Drop drop) {
     if ((hd & 7) || S <= 0) return CC_ERR_SHAPE;
-    int img = 0;
-#if CC_OP == 2
-    if (x3_take_emit(out)) {                // the caller's next GEMM will read `out` as an operand image (asked after attn_fwd_can_image)
-        if (!attn_fwd_can_image(S, hd)) return CC_ERR_STATE;
-        img = 1;
-    }
-#endif
+    act_t* const out = outo.p;
+    const int img = outo.img ? 1 : 0;       // the next GEMM reads `out` as an operand image (the owner asked attn_fwd_can_image)
+    if (img && (outo.img != H * hd || !attn_fwd_can_image(S, hd))) return CC_ERR_STATE;
 #if CC_OP != 2
     static const bool no_mfma = cc_lab_env("CC_ATTN_VALU") != nullptr;   // A/B switch for profiling
     if (!no_mfma || drop.thresh) {
@@ -2653,7 +2644,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_small(const act_t* __restrict_
         act_st4(o + 2 * D, dv.x, dv.y, dv.z, dv.w);
     }
 }
-// bf16x3: whether attn_fwd will honour an x3_emit_image(out) request — the LDS-tile VALU kernels must serve BOTH directions for this shape
+// bf16x3: whether attn_fwd can write `out` as an operand image — the LDS-tile VALU kernels must serve BOTH directions for this shape
 // (the backward of the other attention forms reads the fp32 output again)
 bool attn_fwd_can_image(int S, int hd) {
 #if CC_OP == 2
@@ -2664,7 +2655,7 @@ bool attn_fwd_can_image(int S, int hd) {
     return false;
 #endif
 }
-// bf16x3: whether attn_bwd will honour an x3_emit_image(dqkv) request for this shape (only the LDS-tile VALU kernel writes images)
+// bf16x3: whether attn_bwd can write dqkv as an operand image for this shape (only the LDS-tile VALU kernel writes images)
 bool attn_bwd_can_image(int S, int hd) {
 #if CC_OP == 2
     return (hd & 7) == 0 && S > 0 && (attn_bwd_m3_ok(S, hd) || (!attn_f32mfma_ok(S, hd, true) && attn_bwd_lds(S, hd) <= 160 * 1024));
@@ -2674,15 +2665,11 @@ bool attn_bwd_can_image(int S, int hd) {
 #endif
 }
 int attn_bwd(const act_t* qkv, const act_t* dout, const act_t* o, const float* lse, float* delta, int B, int S, int H, int hd, bool causal,
-             act_t* dqkv, hipStream_t st, Drop drop) {
+             Act dqkvo, hipStream_t st, Drop drop) {
     if ((hd & 7) || S <= 0) return CC_ERR_SHAPE;
-    int img = 0;
-#if CC_OP == 2
-    if (x3_take_emit(dqkv)) {
-        if (!attn_bwd_can_image(S, hd)) return CC_ERR_STATE;
-        img = 1;
-    }
-#endif
+    act_t* const dqkv = dqkvo.p;
+    const int img = dqkvo.img ? 1 : 0;
+    if (img && (dqkvo.img != 3 * H * hd || !attn_bwd_can_image(S, hd))) return CC_ERR_STATE;
 #if CC_OP != 2
     static const bool no_mfma = cc_lab_env("CC_ATTN_VALU") != nullptr;
     if ((!no_mfma || drop.thresh) && o && delta) {
@@ -3486,41 +3473,13 @@ int x3_split_multi(const X3SplitBatch& b, hipStream_t st) {
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 
-namespace {
-struct X3Scratch { char* base = nullptr; size_t bytes = 0, used = 0; };
-thread_local X3Scratch g_x3;
-thread_local const void* g_x3_expect = nullptr;
-thread_local const void* g_x3_emit = nullptr;
-thread_local int g_x3_emit_w = 0;
-}  // namespace
-// every C-ABI entry sets the call's scratch first: a one-shot image hint armed by an earlier call that returned early (an error path between
-// arm and take) must not reach this call's producers / consumers through a recycled workspace pointer
-void x3_set_scratch(void* base, size_t bytes) {
-    g_x3.base = static_cast<char*>(base); g_x3.bytes = bytes; g_x3.used = 0;
-    g_x3_expect = nullptr; g_x3_emit = nullptr; g_x3_emit_w = 0;
-}
-// the call's operand-image scratch as one block (a producer kernel writes the NEXT GEMM's A image there itself); nullptr when it does not fit
-op16_t* x3_scratch_block(size_t bytes) { return (g_x3.base && bytes <= g_x3.bytes) ? reinterpret_cast<op16_t*>(g_x3.base) : nullptr; }
-void x3_expect_image(const void* a) { g_x3_expect = a; }
-bool x3_take_expected(const void* a) {
-    const bool hit = a && g_x3_expect == a;
-    g_x3_expect = nullptr;                       // one shot: a hint never outlives the call it was set for
-    return hit;
-}
-void x3_emit_image(const void* c, int width) { g_x3_emit = c; g_x3_emit_w = width; }
-int x3_take_emit(const void* c) {
-    const int w = (c && g_x3_emit == c) ? g_x3_emit_w : 0;
-    g_x3_emit = nullptr;
-    g_x3_emit_w = 0;
-    return w;
-}
-const op16_t* x3_operand(const float* src, size_t ld, int rows, int width, int form, bool first, hipStream_t st, int* rc) {
-    if (first) g_x3.used = 0;
+const op16_t* x3_operand(Call& cx, const float* src, size_t ld, int rows, int width, int form, bool first, int* rc) {
+    if (first) cx.x3_used = 0;
     const size_t need = (((size_t)rows * 3 * width * sizeof(op16_t)) + 255) & ~size_t(255);
-    if (!g_x3.base || g_x3.used + need > g_x3.bytes) { *rc = CC_ERR_STATE; return nullptr; }
-    op16_t* dst = reinterpret_cast<op16_t*>(g_x3.base + g_x3.used);
-    g_x3.used += need;
-    *rc = x3_split_rows(src, ld, dst, rows, width, form, st);
+    if (!cx.x3 || cx.x3_used + need > cx.x3_bytes) { *rc = CC_ERR_STATE; return nullptr; }
+    op16_t* dst = reinterpret_cast<op16_t*>(cx.x3 + cx.x3_used);
+    cx.x3_used += need;
+    *rc = x3_split_rows(src, ld, dst, rows, width, form, cx.st);
     return *rc == CC_OK ? dst : nullptr;
 }
 #endif   // CC_OP == 2

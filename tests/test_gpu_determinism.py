@@ -1,5 +1,5 @@
 """Bit reproducibility of the training step (the cross-block gradient reductions fold per-block partials in a fixed order, kernels.h
-red_set_scratch): the same seeded model, inputs and step count give the same loss, gradients and weights bit for bit, at the bench's
+RED_SCRATCH_FLOATS): the same seeded model, inputs and step count give the same loss, gradients and weights bit for bit, at the bench's
 configs[1] (frozen GPT-2-small, B = 256) in bf16 and split-bf16 operands — the sizes at which LayerNorm dgamma / dbeta, the bias column
 sums and the prefix batch sum all reduce over many blocks."""
 import pytest

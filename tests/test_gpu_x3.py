@@ -282,6 +282,29 @@ def test_x3_module_autograd_paths_vs_reference_gradients():
     assert worst <= 2e-3 and wm <= 2e-3
 
 
+def test_x3_frozen_lm_logits_autograd_input_gradient_vs_reference():
+    """``lm(inputs_embeds=x).logits`` -> backward with every GPT-2 parameter frozen (cc_gpt2_logits_bwd in mode 1: prefix-only training
+    through Module.forward at the reference's default precision).  The logits gradient arrives as plain fp32 values in the buffer the
+    fused loss path uses for an operand image; the input gradient must match the reference's own (tests/golden/gpt2_tiny grad.in.x) to
+    the bound of the trainable case above, and no parameter gradient appears."""
+    from clipcap_amd.model.gpt2 import GPT2LM
+    from tests.util import sd_of
+    g = load_golden("gpt2_tiny")
+    D, n_layer, n_head, V, npos = [int(v) for v in g["cfg"]]
+    lm = GPT2LM(n_embd=D, n_layer=n_layer, n_head=n_head, vocab_size=V, n_positions=npos, precision=32)
+    lm.load_state_dict(sd_of(g), strict=False)
+    lm = lm.to("cuda")
+    lm.requires_grad_(False)
+    x = torch.from_numpy(g["in.x"]).cuda().requires_grad_(True)
+    logits = lm(inputs_embeds=x).logits
+    assert logits.requires_grad and (logits.detach().cpu() - torch.from_numpy(g["logits"])).abs().max().item() <= 1e-4
+    logits.square().mean().backward()
+    ref = torch.from_numpy(g["grad.in.x"])
+    rel = float((x.grad.cpu() - ref).norm() / ref.norm())
+    print(f"split-bf16 frozen-LM logits autograd: relative input-gradient error {rel:.2e}")
+    assert rel <= 2e-3 and all(p.grad is None for p in lm.parameters())
+
+
 @pytest.mark.parametrize("B,S,H,hd,causal", [(3, 50, 2, 64, 1), (2, 20, 3, 96, 0), (2, 64, 2, 64, 1), (2, 33, 1, 96, 1), (1, 32, 2, 64, 0),
                                              (2, 1, 2, 64, 1), (2, 7, 1, 128, 0), (1, 61, 2, 96, 0), (2, 75, 1, 64, 1), (1, 180, 2, 96, 0),
                                              (2, 17, 2, 32, 1), (3, 40, 2, 128, 1)])
