@@ -119,6 +119,13 @@ SIGNATURES = {
     "cc_sample_step_lp": (_I, [_P, _I, _I, _I, _F, _I, _F, _I, _P, _I, _I, _F, _I, _F, _P, _P, _P, _P]),
     "cc_wgrad_scratch_bytes": (_L, []),
     "cc_gemm_wgrad": (_I, [_I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _P]),
+    "cc_x3_image_bytes": (_L, [_L, _L]),
+    "cc_x3_split_rows": (_I, [_I, _P, _L, _I, _I, _I, _P, _P]),
+    "cc_gemm_act": (_I, [_I, _I, _I, _P, _I, _I, _P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P, _P, _L, _P]),
+    "cc_gemm_resid": (_I, [_I, _I, _I, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _F, C.c_uint64, _I, _I, _P, _L, _P]),
+    "cc_gemm_dact": (_I, [_I, _I, _I, _P, _I, _I, _P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P, _L, _P]),
+    "cc_gemm_f32": (_I, [_I, _I, _I, _P, _I, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _F, _I, _P, _L, _P]),
+    "cc_gemm_wgrad_split": (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _I, _P, _I, _P, _P, _L, _P]),
     "cc_gemm_tile_mode": (_I, [_I]),
     "cc_gemm_skinny_mode": (_I, [_I]),
     "cc_decode_mode": (_I, [_I]),

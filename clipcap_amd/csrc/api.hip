@@ -1139,4 +1139,92 @@ int CC_API(cc_attention_bwd)(const uint16_t* qkv, const uint16_t* dout, const ui
                     causal != 0, reinterpret_cast<act_t*>(dqkv), S_(stream));
 }
 
+// ---- GEMM wrapper hooks (tests/test_gpu_gemm_epilogues.py): one wrapper call each on caller buffers, the call's image scratch passed in
+namespace {
+inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// what every NT hook checks before it builds its Call: operands present and 16-B aligned, leading dimensions cover the rows they stride
+inline bool hook_operands_ok(int al, int bl, const void* A, int a_img, int lda, const void* B, int ldb, int M, int N, int K) {
+    if (!A || !B || !al16(A) || !al16(B) || M <= 0 || N <= 0 || K <= 0 || a_img < 0) return false;
+    if (!kX3 && a_img) return false;
+    return lda >= (a_img ? 0 : (al ? M : K)) && ldb >= (bl ? N : K);
+}
+inline void hook_scratch(Call& cx, void* x3, int64_t x3_bytes) {
+    if (kX3 && x3 && x3_bytes > 0 && al16(x3)) { cx.x3 = static_cast<char*>(x3); cx.x3_bytes = (size_t)x3_bytes; }
+}
+inline bool hook_c_img_ok(int c_img, int N) { return c_img == 0 || (kX3 && c_img == N); }
+}  // namespace
+
+int64_t CC_API(cc_x3_image_bytes)(int64_t rows, int64_t depth) {
+    if (rows < 0 || depth < 0) return CC_ERR_ARG;
+    return (int64_t)x3_img((size_t)rows, (size_t)depth);
+}
+
+int CC_API(cc_x3_split_rows)(const float* src, int64_t ld, int32_t rows, int32_t width, int32_t form, uint16_t* dst, void* stream) {
+#if CC_OP == 2
+    if (!src || !dst || rows < 0 || width < 0 || ld < width || (form != 0 && form != 1)) return CC_ERR_ARG;
+    return x3_split_rows(src, (size_t)ld, dst, rows, width, form, S_(stream));
+#else
+    (void)src; (void)ld; (void)rows; (void)width; (void)form; (void)dst; (void)stream;
+    return CC_ERR_ARG;
+#endif
+}
+
+int CC_API(cc_gemm_act)(int32_t al, int32_t bl, const void* A, int32_t a_img, int32_t lda, const uint16_t* B, int32_t ldb, int32_t M, int32_t N, int32_t K,
+                void* C, int32_t c_img, int32_t ldc, const float* bias, int32_t act, void* pre, void* x3, int64_t x3_bytes, void* stream) {
+    if (!hook_operands_ok(al, bl, A, a_img, lda, B, ldb, M, N, K) || !C || !al16(C) || !al16(pre) || !al16(bias) || ldc < N || act < 0 || act > 3 ||
+        !hook_c_img_ok(c_img, N))
+        return CC_ERR_ARG;
+    Call cx{S_(stream)};
+    hook_scratch(cx, x3, x3_bytes);
+    return gemm_bf16out(al, bl, ActIn(static_cast<const act_t*>(A), a_img), lda, B, ldb, M, N, K, Act(static_cast<act_t*>(C), c_img), ldc, bias, act,
+                        static_cast<act_t*>(pre), cx);
+}
+
+int CC_API(cc_gemm_resid)(int32_t al, int32_t bl, const void* A, int32_t a_img, int32_t lda, const uint16_t* B, int32_t ldb, int32_t M, int32_t N, int32_t K,
+                  float* out, const float* res, int32_t ld, const float* bias, float p, uint64_t seed, int32_t site, int32_t layer, void* x3,
+                  int64_t x3_bytes, void* stream) {
+    if (!hook_operands_ok(al, bl, A, a_img, lda, B, ldb, M, N, K) || !out || !res || !al16(out) || !al16(res) || !al16(bias) || ld < N || site < 0 ||
+        site > 3 || layer < 0 || layer > 255 || p < 0.f || p >= 1.f)
+        return CC_ERR_ARG;
+    Call cx{S_(stream)};
+    hook_scratch(cx, x3, x3_bytes);
+    return gemm_resid(al, bl, ActIn(static_cast<const act_t*>(A), a_img), lda, B, ldb, M, N, K, out, res, ld, bias, cx,
+                      make_drop(p, seed, (unsigned)site, (unsigned)layer));
+}
+
+int CC_API(cc_gemm_dact)(int32_t al, int32_t bl, const void* A, int32_t a_img, int32_t lda, const uint16_t* B, int32_t ldb, int32_t M, int32_t N, int32_t K,
+                 void* C, int32_t c_img, int32_t ldc, const void* aux, int32_t act, void* x3, int64_t x3_bytes, void* stream) {
+    if (!hook_operands_ok(al, bl, A, a_img, lda, B, ldb, M, N, K) || !C || !aux || !al16(C) || !al16(aux) || ldc < N || act < 1 || act > 3 ||
+        !hook_c_img_ok(c_img, N))
+        return CC_ERR_ARG;
+    Call cx{S_(stream)};
+    hook_scratch(cx, x3, x3_bytes);
+    return gemm_dact(al, bl, ActIn(static_cast<const act_t*>(A), a_img), lda, B, ldb, M, N, K, Act(static_cast<act_t*>(C), c_img), ldc,
+                     static_cast<const act_t*>(aux), act, cx);
+}
+
+int CC_API(cc_gemm_f32)(int32_t al, int32_t bl, const void* A, int32_t a_img, int32_t lda, const uint16_t* B, int32_t ldb, int32_t M, int32_t N, int32_t K,
+                float* C, int32_t ldc, const float* bias, int32_t mode, float alpha, int32_t ksplit, void* x3, int64_t x3_bytes, void* stream) {
+    if (!hook_operands_ok(al, bl, A, a_img, lda, B, ldb, M, N, K) || !C || !al16(C) || !al16(bias) || ldc < N || mode < 0 || mode > 2 || ksplit < 1 ||
+        (bias && mode != 0))
+        return CC_ERR_ARG;
+    Call cx{S_(stream)};
+    hook_scratch(cx, x3, x3_bytes);
+    return gemm_f32out(al, bl, ActIn(static_cast<const act_t*>(A), a_img), lda, B, ldb, M, N, K, C, ldc, bias, mode, alpha, ksplit, cx);
+}
+
+int CC_API(cc_gemm_wgrad_split)(const void* X, int32_t x_img, int32_t ldx, const float* Y, int32_t ldy, int32_t Mw, int32_t Nw, int32_t K, float* dW,
+                     int32_t ldw, float* scratch, void* x3, int64_t x3_bytes, void* stream) {
+#if CC_OP == 2
+    if (!X || !Y || !dW || !al16(X) || !al16(Y) || !al16(dW) || Mw <= 0 || Nw <= 0 || K <= 0 || x_img < 0 || (!x_img && ldx < Mw) || ldy < Nw || ldw < Nw)
+        return CC_ERR_ARG;
+    Call cx{S_(stream)};
+    hook_scratch(cx, x3, x3_bytes);
+    return gemm_wgrad(ActIn(static_cast<const act_t*>(X), x_img), ldx, Y, ldy, Mw, Nw, K, dW, ldw, scratch, cx);
+#else
+    (void)X; (void)x_img; (void)ldx; (void)Y; (void)ldy; (void)Mw; (void)Nw; (void)K; (void)dW; (void)ldw; (void)scratch; (void)x3; (void)x3_bytes; (void)stream;
+    return CC_ERR_ARG;
+#endif
+}
+
 }  // extern "C"

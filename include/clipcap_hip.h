@@ -33,7 +33,7 @@
  *     reference to 1e-3 at full depth.  Its buffers differ in size only: the operand arena has 6*count 16-bit elements (the
  *     [hi | lo | hi] image of every 2-D weight at 3x its offset, of its transpose at 3*(count + offset)), the KV cache holds fp32
  *     (twice the bytes per element), workspaces are whatever cc_*_ws_bytes says.  cc_*_transpose_weights, cc_adamw_step_cast,
- *     cc_cast_op16 and the bare GEMM hooks do not exist in this mode (CC_ERR_ARG): use cc_adamw_step + cc_*_sync_weights.
+ *     cc_cast_op16 and the bare GEMM hooks (cc_gemm_op16_f32, cc_gemm_wgrad) do not exist in this mode (CC_ERR_ARG): use cc_adamw_step + cc_*_sync_weights.
  *   - parameters live in flat arenas whose element offsets are defined by cc_*_param_offsets(); the fp32 arena is
  *     the master copy (nn.Parameter views alias it).  The 16-bit operand arena has 2*count elements: [0,count) is the
  *     cast of the master (same offsets, reference state-dict layouts: torch.nn.Linear weight [out,in]; HF Conv1D
@@ -62,7 +62,8 @@ extern "C" {
  * cc_adamw_step_cast, cc_mapper_transpose_weights, cc_gpt2_transpose_weights, cc_comm_count, cc_decode_part_floats, cc_decode_fwd_p,
  * cc_beam_step_p; since 3: cc_decode_fwd_g, cc_decode_ws_check, cc_decode_mode, cc_grad_wire_pack, cc_grad_wire_unpack,
  * cc_sample_step_lp, cc_broadcast_bucket, cc_reduce_bucket, cc_embed_tokens_bwd, cc_embed_tokens_bwd_ws,
- * cc_embed_tokens_bwd_ws_bytes; operand mode ADDED: CC_OP_BF16X3.  Round 6 (still 3): the default-off decode experiments
+ * cc_embed_tokens_bwd_ws_bytes, and the GEMM wrapper test hooks cc_x3_image_bytes, cc_x3_split_rows, cc_gemm_act, cc_gemm_resid,
+ * cc_gemm_dact, cc_gemm_f32, cc_gemm_wgrad_split; operand mode ADDED: CC_OP_BF16X3.  Round 6 (still 3): the default-off decode experiments
  * (cc_decode_image*, cc_decode_xt_image*, cc_decode_fwd_x, cc_decode_ws_check, cc_decode_last_path) moved to include/clipcap_hip_lab.h —
  * the lab library exports them, the product library does not. */
 #define CC_ABI_VERSION 3
@@ -378,6 +379,42 @@ int cc_gemm_op16_f32(int32_t op_dtype, int32_t al, int32_t bl, const uint16_t* A
 int64_t cc_wgrad_scratch_bytes(void);
 int cc_gemm_wgrad(int32_t op_dtype, const uint16_t* X, int32_t ldx, const uint16_t* Y, int32_t ldy, int32_t Mw, int32_t Nw, int32_t K, float* dW, int32_t ldw,
                   float* scratch, void* stream);
+/* The four GEMM wrappers every GEMM of a training step leaves through (csrc/gemm_api.h), one call each on caller buffers, in all three
+ * operand modes.  Test hooks: they keep no state and the product path never calls them; cc_gemm_tile_mode / cc_gemm_skinny_mode select
+ * the tile kernel as for cc_gemm_op16_f32.  Common arguments: al / bl, lda / ldb, M, N, K as cc_gemm_op16_f32 (LOGICAL sizes in every
+ * mode).  A: CC_OP_BF16 / CC_OP_FP16 16-bit elements, a_img = 0.  CC_OP_BF16X3: a_img = 0 -> fp32 [M][lda], split per call into the
+ * image scratch; a_img = K -> A already is its [hi | hi | lo] image (rows of 3 K 16-bit elements, lda ignored); any other a_img, or
+ * al / bl != 0 in that mode: CC_ERR_ARG.  B: 16-bit [N][ldb]; CC_OP_BF16X3: the [hi | lo | hi] image, rows of 3 ldb (cc_x3_split_rows
+ * form 1 of an fp32 [N][ldb] matrix).  x3 / x3_bytes: the call's image scratch (Call::x3; 16-B aligned, ignored outside CC_OP_BF16X3);
+ * a plain A of M x K needs cc_x3_image_bytes(M, K) of it — missing or too small: CC_ERR_STATE and nothing is written.  C / pre / aux
+ * are activations: 16-bit, or fp32 in CC_OP_BF16X3; c_img = N (CC_OP_BF16X3 only) writes C as the [hi | hi | lo] image of an N-deep A
+ * operand instead (rows of 3 N 16-bit elements, ldc then strides only pre / aux), any other non-zero c_img: CC_ERR_ARG.
+ *   cc_x3_image_bytes: bytes one rows x depth image takes in the scratch (rounded up to 256).
+ *   cc_x3_split_rows (CC_OP_BF16X3 only): dst [rows][3 width] = image of src fp32 [rows][ld]; form 0 = [hi | hi | lo], 1 = [hi | lo | hi];
+ *                      hi = bf16(x), lo = bf16(x - hi).
+ *   cc_gemm_act:   C = act(A B^T + bias); act 0 none, 1 relu, 2 gelu_new, 3 gelu_new with pre receiving gelu_new'(u); pre (nullable)
+ *                  otherwise receives u = A B^T + bias.
+ *   cc_gemm_resid: out = res + drop(A B^T + bias), fp32 rows of stride ld, out may alias res.  drop: residual dropout with probability p
+ *                  on the mask stream (seed, site, layer) of cc_dropout_mask, element index row * ld + col; p = 0: off.
+ *   cc_gemm_dact:  C = (A B^T) * act'(aux); act 1 relu (aux = post-activation), 2 gelu_new (aux = pre-activation), 3 multiply by aux.
+ *   cc_gemm_f32:   fp32 C: mode 0 = alpha A B^T + bias, 1 += alpha A B^T, 2 atomic += (required when ksplit > 1; bias must be NULL
+ *                  in modes 1 and 2).
+ *   cc_gemm_wgrad_split (CC_OP_BF16X3 only): cc_gemm_wgrad with fp32 X [K][ldx], Y [K][ldy]; x_img = Mw: X already is its [hi | hi | lo]
+ *                  image [K][3 Mw].  Both (x_img = 0) or Y alone are split into the image scratch. */
+int64_t cc_x3_image_bytes(int64_t rows, int64_t depth);
+int cc_x3_split_rows(int32_t op_dtype, const float* src, int64_t ld, int32_t rows, int32_t width, int32_t form, uint16_t* dst, void* stream);
+int cc_gemm_act(int32_t op_dtype, int32_t al, int32_t bl, const void* A, int32_t a_img, int32_t lda, const uint16_t* B, int32_t ldb, int32_t M, int32_t N,
+                int32_t K, void* C, int32_t c_img, int32_t ldc, const float* bias, int32_t act, void* pre, void* x3, int64_t x3_bytes, void* stream);
+int cc_gemm_resid(int32_t op_dtype, int32_t al, int32_t bl, const void* A, int32_t a_img, int32_t lda, const uint16_t* B, int32_t ldb, int32_t M, int32_t N,
+                  int32_t K, float* out, const float* res, int32_t ld, const float* bias, float p, uint64_t seed, int32_t site, int32_t layer,
+                  void* x3, int64_t x3_bytes, void* stream);
+int cc_gemm_dact(int32_t op_dtype, int32_t al, int32_t bl, const void* A, int32_t a_img, int32_t lda, const uint16_t* B, int32_t ldb, int32_t M, int32_t N,
+                 int32_t K, void* C, int32_t c_img, int32_t ldc, const void* aux, int32_t act, void* x3, int64_t x3_bytes, void* stream);
+int cc_gemm_f32(int32_t op_dtype, int32_t al, int32_t bl, const void* A, int32_t a_img, int32_t lda, const uint16_t* B, int32_t ldb, int32_t M, int32_t N,
+                int32_t K, float* C, int32_t ldc, const float* bias, int32_t mode, float alpha, int32_t ksplit, void* x3, int64_t x3_bytes,
+                void* stream);
+int cc_gemm_wgrad_split(int32_t op_dtype, const void* X, int32_t x_img, int32_t ldx, const float* Y, int32_t ldy, int32_t Mw, int32_t Nw, int32_t K,
+                     float* dW, int32_t ldw, float* scratch, void* x3, int64_t x3_bytes, void* stream);
 /* PROCESS-WIDE test knob.  NT GEMM tile choice: -1 = cost-model chooser (default), 0 = 128x128 kernels only (also for cc_gemm_wgrad), 3 / 4 / 5 / 6 =
  * force the 256x192 / 256x256 / 320x256 / 160x256 (8-wave staggered) kernel wherever it is legal; 7 = 160x256 on the persistent 4-wave kernel with the
  * instruction-level K loop (what the chooser launches for that tile when K % 128 == 0 and K >= 256), the staggered one otherwise.  Returns the previous
