@@ -288,6 +288,7 @@ struct Gpt2WS {
     act_t* hf16;       // [Mh, D]   ln_f output rows (Mh = max(B*cap, B*T) so the parity API can use it too)
     float *meanf, *rstdf;
     int *target, *row_map;
+    int* keep;         // [B*cap]  scoring pass (mode 0 with caption rows) only: rows whose log-prob counts
     act_t* logits16;   // [B*cap, Vp]  (what it holds depends on who filled it: lm_logits)
     float *pmax, *psum, *tgt_logit, *lse_row, *row_loss;
     float *cref, *lmfac;   // exponential form of the lm_head outputs (bf16 build): reference shift [Mc], row factors {r, w} [Mc][2]
@@ -344,6 +345,7 @@ void gpt2_carve(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, int cap, void* ws,
     w.rstdf = cv.take<float>(Mh);
     w.target = cv.take<int>(Mh);
     w.row_map = cv.take<int>(Mh);
+    w.keep = nullptr;
     if (keep) {
         const int npart = c->Vp / 64;
         w.logits16 = cv.take<act_t>(Mc * c->Vp * ((kX3 && !full) ? 3 : 2) / 2);               // bf16x3, frozen LM: room for E as an operand image (lm_logits)
@@ -372,6 +374,14 @@ void gpt2_carve(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, int cap, void* ws,
         w.logits16 = nullptr; w.pmax = w.psum = w.tgt_logit = w.lse_row = w.row_loss = nullptr;
         w.cref = w.lmfac = nullptr; w.hfs16 = nullptr;
         w.dx32 = nullptr; w.dx16 = w.dx16b = w.du16 = w.dqkv16 = Act(); w.dhf16 = w.dxn16 = w.datt16 = nullptr;
+        if (Mc > 0) {      // forward-only pass with caption rows (cc_lmhead_score): the per-row buffers of the loss side, and no logits matrix
+            const int npart = c->Vp / 64;
+            w.pmax = cv.take<float>(Mc * npart);
+            w.psum = cv.take<float>(Mc * npart);
+            w.tgt_logit = cv.take<float>(Mc);
+            w.lse_row = cv.take<float>(Mc);
+            w.keep = cv.take<int>(Mc);
+        }
     }
     w.x3 = nullptr; w.x3_bytes = 0;
     if (kX3) {
@@ -851,6 +861,27 @@ int CC_API(cc_lmhead_ce_fwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const
                                                  ef ? w.cref : nullptr));
     CC_TRY(ce_rows(w.pmax, w.psum, npart, w.target, ef ? w.cref : w.tgt_logit, w.lse_row, w.row_loss, stats, Mc, st));   // cref IS the target logit
     return CC_OK;
+}
+
+int CC_API(cc_lmhead_score)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const int64_t* tokens,
+                    int32_t ignore_zero, float* token_logprob, float* sample_stats, void* stream) {
+    if (!gpt2_cfg_ok(c) || !shape_ok(c, s) || s->mode != 0 || s->L < 1 || !w32 || !w16 || !ws || !tokens || !token_logprob || !sample_stats)
+        return CC_ERR_ARG;
+    const int cap = s->T - s->L;
+    if (cap < 1 || cap != s->cap) return CC_ERR_SHAPE;      // every token column is scored
+    hipStream_t st = S_(stream);
+    Gpt2Off o;
+    gpt2_offsets(c, o);
+    Gpt2WS w;
+    gpt2_carve(c, s, cap, ws, w);
+    Call cx = call_of(st, w);
+    const int D = c->D, Mc = s->B * cap, npart = c->Vp / 64;
+    CC_TRY(ce_targets(reinterpret_cast<const long long*>(tokens), w.target, w.row_map, s->B, cap, s->L, s->T, st));
+    CC_TRY(score_keep(reinterpret_cast<const long long*>(tokens), w.keep, Mc, ignore_zero, st));
+    // ln_f only on the rows that predict a caption token: L-1 .. T-2 of every sample
+    CC_TRY(ln_fwd(w.x[c->NL], D, w.row_map, w32 + o.lnf_w, w32 + o.lnf_b, w.hf16, nullptr, w.meanf, w.rstdf, Mc, D, st));
+    CC_TIMED(CC_SITE_LMHEAD_FWD, st, gemm_lmhead_score(w.hf16, D, W16(w16, o.wte), D, Mc, c->Vp, c->V, D, w.pmax, w.psum, npart, w.target, w.tgt_logit, cx));
+    return score_rows(w.pmax, w.psum, npart, w.keep, w.tgt_logit, w.lse_row, token_logprob, sample_stats, s->B, cap, st);
 }
 
 int CC_API(cc_lmhead_ce_bwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const float* denom,

@@ -2157,8 +2157,82 @@ struct EpiLogits {
         }
     }
 };
+// Scoring lm_head (cc_lmhead_score): EpiLMHead's partials and exact target logit from the same fp32 accumulators, and NO C — the
+// forward direction never reads the logits matrix, so it is neither stored nor allocated.  N = the GEMM's column count (Vp).
+struct EpiLMHeadScore {
+    float* pmax;
+    float* psum;           // [M][npart]
+    const int* target;     // [M] token id per row (>=0)
+    float* tgt_logit;      // [M]
+    int M, N, V, npart;    // V = true vocab (columns >= V are padding: excluded from the partials)
+    __device__ __forceinline__ void operator()(int row, int col, float (&v)[8]) const {
+        const bool ok = row < M && col < N;
+        float m = -INFINITY;
+#pragma unroll
+        for (int e = 0; e < 8; e++)
+            if (col + e < V) m = fmaxf(m, v[e]);
+        m = fmaxf(m, __shfl_xor(m, 1, 64));
+        m = fmaxf(m, __shfl_xor(m, 2, 64));
+        m = fmaxf(m, __shfl_xor(m, 4, 64));
+        float s = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; e++)
+            if (col + e < V) s += __expf(v[e] - m);
+        s += __shfl_xor(s, 1, 64);
+        s += __shfl_xor(s, 2, 64);
+        s += __shfl_xor(s, 4, 64);
+        if (!ok) return;
+        if ((col & 63) == 0) {
+            const int blk = col >> 6;
+            pmax[(size_t)row * npart + blk] = m;
+            psum[(size_t)row * npart + blk] = (m == -INFINITY) ? 0.f : s;
+        }
+        const int t = target[row] - col;
+        if (t >= 0 && t < 8) tgt_logit[row] = v[t];
+    }
+    typedef int RowAux;                                                               // the row's target id
+    __device__ __forceinline__ int load_row(int row) const { return row < M ? target[row] : -1; }
+    __device__ __forceinline__ void strip(int row, int ca, int cb, float (&va)[8], float (&vb)[8], int t) const {
+        constexpr float L2E = 1.4426950408889634f;
+        float m, s = 0.f;
+        if (__builtin_amdgcn_readfirstlane(ca | 63) < V) {          // the whole 64-column block is inside the vocabulary (wave-uniform)
+            m = fmaxf(fmaxf(fmaxf(va[0], va[1]), fmaxf(va[2], va[3])), fmaxf(fmaxf(va[4], va[5]), fmaxf(va[6], va[7])));
+            m = fmaxf(m, fmaxf(fmaxf(fmaxf(vb[0], vb[1]), fmaxf(vb[2], vb[3])), fmaxf(fmaxf(vb[4], vb[5]), fmaxf(vb[6], vb[7]))));
+            m = fmaxf(m, __shfl_xor(m, 16, 64));
+            m = fmaxf(m, __shfl_xor(m, 32, 64));
+            const float ml = -m * L2E;
+#pragma unroll
+            for (int e = 0; e < 8; e++) s += __builtin_amdgcn_exp2f(fmaf(va[e], L2E, ml)) + __builtin_amdgcn_exp2f(fmaf(vb[e], L2E, ml));
+        } else {
+            m = -INFINITY;
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+                if (ca + e < V) m = fmaxf(m, va[e]);
+                if (cb + e < V) m = fmaxf(m, vb[e]);
+            }
+            m = fmaxf(m, __shfl_xor(m, 16, 64));
+            m = fmaxf(m, __shfl_xor(m, 32, 64));
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+                if (ca + e < V) s += __expf(va[e] - m);
+                if (cb + e < V) s += __expf(vb[e] - m);
+            }
+        }
+        s += __shfl_xor(s, 16, 64);
+        s += __shfl_xor(s, 32, 64);
+        if (row >= M) return;
+        if ((ca & 63) == 0 && ca < N) {
+            const int blk = ca >> 6;
+            pmax[(size_t)row * npart + blk] = m;
+            psum[(size_t)row * npart + blk] = (m == -INFINITY) ? 0.f : s;
+        }
+        if (t >= ca && t < ca + 8 && ca < N) tgt_logit[row] = va[t - ca];
+        if (t >= cb && t < cb + 8 && cb < N) tgt_logit[row] = vb[t - cb];
+    }
+};
 template <> struct epi_row_strip<EpiLogits> { static constexpr bool value = true; };
 template <> struct epi_row_strip<EpiLMHead> { static constexpr bool value = true; };
+template <> struct epi_row_strip<EpiLMHeadScore> { static constexpr bool value = true; };
 template <> struct epi_row_strip<EpiLMHeadExp> { static constexpr bool value = true; };
 
 // ------------------------------------------------------------------------------------------------

@@ -28,6 +28,10 @@ int gemm_dact(int al, int bl, ActIn A, int lda, const op16_t* B, int ldb, int M,
 // cref != nullptr: exponential form (C = exp(logit - cref[row]), see gemm.hip.h EpiLMHead); only that form writes C as an image
 int gemm_lmhead(ActIn A, int lda, const op16_t* B, int ldb, int M, int Vp, int V, int K, Act C, int ldc, float* pmax,
                 float* psum, int npart, const int* target, float* tgt_logit, Call& cx, const float* cref = nullptr);
+// scoring lm_head (forward only): the same partials over the V real columns and the exact target logit, and no C at all — gemm.hip.h
+// EpiLMHeadScore.  pmax / psum [M][npart] (npart >= Vp / 64), target / tgt_logit [M].
+int gemm_lmhead_score(ActIn A, int lda, const op16_t* B, int ldb, int M, int Vp, int V, int K, float* pmax, float* psum, int npart,
+                      const int* target, float* tgt_logit, Call& cx);
 
 // decode lm_head: fp32 logits [M][ldc] (Ns columns stored, Ns % 8 == 0) + per-(row, 64-column block) softmax partials over the V real
 // columns (pmax / psum [M][npart], npart >= ceil(Ns / 64)) — gemm.hip.h EpiLogits

@@ -18,6 +18,17 @@ int gemm_lmhead(ActIn A, int lda, const op16_t* B, int ldb, int M, int Vp, int V
     EpiLMHead e{C, pmax, psum, target, tgt_logit, ldc, M, V, npart};
     return launch_gemm(0, 0, A16, lda, B, ldb, M, Vp, K, 1, e, st);
 }
+int gemm_lmhead_score(ActIn A, int lda, const op16_t* B, int ldb, int M, int Vp, int V, int K, float* pmax, float* psum, int npart,
+                      const int* target, float* tgt_logit, Call& cx) {
+    const hipStream_t st = cx.st;
+    cc_shared::ProfScope _all(cc_shared::SITE_ALL_GEMMS, st, 2.0 * M * V * (double)K);
+    if ((Vp & 63) || V > Vp || npart * 64 < Vp) return CC_ERR_SHAPE;
+    const op16_t* A16;
+    const int rca = nt_operand(cx, A, 0, 0, M, lda, ldb, K, A16);
+    if (rca != CC_OK) return rca;
+    EpiLMHeadScore e{pmax, psum, target, tgt_logit, M, Vp, V, npart};
+    return launch_gemm(0, 0, A16, lda, B, ldb, M, Vp, K, 1, e, st);
+}
 int gemm_logits_part(ActIn A, int lda, const op16_t* B, int ldb, int M, int Ns, int V, int K, float* C, int ldc, float* pmax, float* psum,
                      int npart, Call& cx) {
     const hipStream_t st = cx.st;

@@ -86,6 +86,10 @@ int scatter_rows(const ScatterSrc& s, int R, int D, int Vp, float* dst, void* ws
 
 int ce_rows(const float* pmax, const float* psum, int npart, const int* target, const float* tgt_logit, float* lse, float* row_loss,
             float* stats, int M, hipStream_t st);
+// scoring: token_logprob[row] = keep[row] ? tgt_logit[row] - lse[row] : 0 (lse folded exactly as ce_rows does), then per sample
+// sample_stats[b] = {sum over its cap rows, kept count} in a fixed order (bit-identical from run to run)
+int score_rows(const float* pmax, const float* psum, int npart, const int* keep, const float* tgt_logit, float* lse, float* token_logprob,
+               float* sample_stats, int B, int cap, hipStream_t st);
 int ce_dlogits(act_t* logits, int ld, int V, const int* target, const float* lse, const float* denom, const float* loss_scale, int M,
                hipStream_t st, op16_t* img = nullptr);   // img (bf16x3): write the gradient as the dgrad GEMM's operand image there instead of in place
 // sample.hip: one sampling step per row (temperature, repetition penalty, top-k, top-p, inverse-CDF draw at u[row])
@@ -93,6 +97,7 @@ int sample_rows(const float* logits, int R, int V, int ld, float temperature, in
                 int hist_len, int hist_ld, float rep_pen, const float* u, int* next_token, float* probs_out, hipStream_t st, int stop_tok = -1,
                 float len_pen = 1.0f);   // stop_tok >= 0: sentence-length penalty (history tokens whose filtered value == stop id are scaled by len_pen)
 int ce_targets(const long long* tokens, int* target, int* row_map, int B, int cap, int L, int T, hipStream_t st);
+int score_keep(const long long* tokens, int* keep, int n, int ignore_zero, hipStream_t st);   // keep[i] = tokens[i] >= 0 (&& != 0 with ignore_zero)
 // Exponential form of the lm_head outputs (gemm.hip.h EpiLMHead, bf16 build):
 //   lm_tgt_ref   cref[m] = hf[m] . wte[target[m]]  (16-bit operands, fp32 accumulate): the reference shift of row m
 //   lm_rowfac    fac[m] = {r, w}: w = (target[m] != 0) * loss_scale / max(denom, 1), r = exp(cref[m] - lse[m]) * w

@@ -3063,13 +3063,12 @@ int scatter_rows(const ScatterSrc& s, int R, int D, int Vp, float* dst, void* ws
 //            stats[0] += sum of kept row losses, stats[1] += number of kept rows.
 // k_ce_dlogits: in place over the bf16 logits: dl = (softmax - onehot) * (kept ? 1/denom : 0); padding columns -> 0.
 // ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_ce_rows(const float* __restrict__ pmax, const float* __restrict__ psum, int npart,
-                                                 const int* __restrict__ target, const float* __restrict__ tgt_logit,
-                                                 float* __restrict__ lse, float* __restrict__ row_loss, int M) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= M) return;
-    float m = -INFINITY, s = 0.f;
+// one wave folds one row's partials: (m, s) with sum over the row's real columns of exp(x) = s exp(m), valid in every lane
+// (shared by k_ce_rows and k_score_rows: one order of operations, one lse)
+__device__ __forceinline__ void ce_row_fold(const float* __restrict__ pmax, const float* __restrict__ psum, int npart, int row, int lane,
+                                            float& m, float& s) {
+    m = -INFINITY;
+    s = 0.f;
     if (npart <= 64 * 16) {
         // all partials of the row are requested at once (one round trip instead of one per 64 partials, and no second read of the maxima)
         float pm[16], ps[16];
@@ -3096,6 +3095,15 @@ __global__ __launch_bounds__(256) void k_ce_rows(const float* __restrict__ pmax,
         }
     }
     s = wave_sum(s);
+}
+__global__ __launch_bounds__(256) void k_ce_rows(const float* __restrict__ pmax, const float* __restrict__ psum, int npart,
+                                                 const int* __restrict__ target, const float* __restrict__ tgt_logit,
+                                                 float* __restrict__ lse, float* __restrict__ row_loss, int M) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    float m, s;
+    ce_row_fold(pmax, psum, npart, row, lane, m, s);
     if (lane == 0) {
         const float l = m + logf(s);
         lse[row] = l;
@@ -3127,6 +3135,49 @@ int ce_rows(const float* pmax, const float* psum, int npart, const int* target, 
     if (M <= 0) return CC_OK;
     hipLaunchKernelGGL(k_ce_rows, dim3((M + 3) / 4), dim3(256), 0, st, pmax, psum, npart, target, tgt_logit, lse, row_loss, M);
     hipLaunchKernelGGL(k_ce_stats, dim3(1), dim3(1024), 0, st, row_loss, target, stats, M);
+    return CC_OK;
+}
+
+// Scoring (cc_lmhead_score): token_logprob[row] = tgt_logit - lse for kept rows, 0 for the others; lse from the same fold as k_ce_rows.
+__global__ __launch_bounds__(256) void k_score_rows(const float* __restrict__ pmax, const float* __restrict__ psum, int npart,
+                                                    const int* __restrict__ keep, const float* __restrict__ tgt_logit,
+                                                    float* __restrict__ lse, float* __restrict__ token_logprob, int M) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    float m, s;
+    ce_row_fold(pmax, psum, npart, row, lane, m, s);
+    if (lane == 0) {
+        const float l = m + logf(s);
+        lse[row] = l;
+        token_logprob[row] = keep[row] ? tgt_logit[row] - l : 0.f;
+    }
+}
+// sample_stats[b] = {sum of the sample's kept log-probs, kept count}: one wave per sample, lane j adds rows j, j + 64, ... in that order,
+// then the fixed wave tree (deterministic, no atomics)
+__global__ __launch_bounds__(256) void k_score_samples(const float* __restrict__ token_logprob, const int* __restrict__ keep,
+                                                       float* __restrict__ sample_stats, int B, int cap) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    float a = 0.f, c = 0.f;
+    for (int i = lane; i < cap; i += 64) {
+        a += token_logprob[(size_t)b * cap + i];
+        c += keep[(size_t)b * cap + i] ? 1.f : 0.f;
+    }
+    a = wave_sum(a);
+    c = wave_sum(c);
+    if (lane == 0) {
+        sample_stats[2 * b] = a;
+        sample_stats[2 * b + 1] = c;
+    }
+}
+int score_rows(const float* pmax, const float* psum, int npart, const int* keep, const float* tgt_logit, float* lse, float* token_logprob,
+               float* sample_stats, int B, int cap, hipStream_t st) {
+    const int M = B * cap;
+    if (M <= 0) return CC_OK;
+    hipLaunchKernelGGL(k_score_rows, dim3((M + 3) / 4), dim3(256), 0, st, pmax, psum, npart, keep, tgt_logit, lse, token_logprob, M);
+    hipLaunchKernelGGL(k_score_samples, dim3((B + 3) / 4), dim3(256), 0, st, token_logprob, keep, sample_stats, B, cap);
     return CC_OK;
 }
 
@@ -3279,6 +3330,19 @@ __global__ void k_ce_targets(const long long* __restrict__ tokens, int* __restri
 int ce_targets(const long long* tokens, int* target, int* row_map, int B, int cap, int L, int T, hipStream_t st) {
     if (B * cap <= 0) return CC_OK;
     hipLaunchKernelGGL(k_ce_targets, dim3((B * cap + 255) / 256), dim3(256), 0, st, tokens, target, row_map, B, cap, L, T);
+    return CC_OK;
+}
+// Kept rows of a scoring call, from the ORIGINAL tokens (ce_targets has already mapped the -1 pads to target 0): keep[i] = tokens[i] >= 0,
+// and with ignore_zero also tokens[i] != 0 (the training loss's ignore_index = 0, model.py:108-109)
+__global__ void k_score_keep(const long long* __restrict__ tokens, int* __restrict__ keep, int n, int ignore_zero) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long long id = tokens[i];
+    keep[i] = (id >= 0 && !(ignore_zero && id == 0)) ? 1 : 0;
+}
+int score_keep(const long long* tokens, int* keep, int n, int ignore_zero, hipStream_t st) {
+    if (n <= 0) return CC_OK;
+    hipLaunchKernelGGL(k_score_keep, dim3((n + 255) / 256), dim3(256), 0, st, tokens, keep, n, ignore_zero);
     return CC_OK;
 }
 

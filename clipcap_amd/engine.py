@@ -616,6 +616,79 @@ class ClipCapEngine:
             m.backward(dprefix, on_layers_done=(None if on_grads_ready is None else (lambda lo, hi: on_grads_ready(0, lo, hi))))
         return stats[0] / stats[1].clamp_min(1.0)
 
+    @torch.no_grad()
+    def score(self, tokens: torch.Tensor, embeds: Optional[torch.Tensor] = None, *, prefix: Optional[torch.Tensor] = None,
+              ignore_zero: bool = False, chunk: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Teacher-forced log-likelihood of every caption under the model: a forward-only pass (mode 0: one layer's activations, eval
+        behaviour, no dropout) whose lm_head stores no logits (cc_lmhead_score).
+
+        tokens int64 (B, cap) padded with -1, as forward_backward takes them.  Exactly one of ``embeds`` (encoder embeddings (B, E) /
+        (B, W, E): the mapper runs without saving) and ``prefix`` (fp32 (B, L, D), any L >= 1: an already mapped prefix, with a text
+        prefix's embeddings appended if the caller wants one).
+        Returns (token_logprob (B, cap): log p(tokens[b, c] | prefix, tokens[b, :c]) at kept positions and 0 elsewhere,
+        sample_sum (B,), sample_count (B,)).  Kept: tokens >= 0; with ``ignore_zero`` also != 0 (the training loss's ignore_index).
+        ``chunk``: samples per library call, bounding the workspace (default: the whole batch).
+        Uses a workspace of its own and leaves ``stats``, the gradient arenas and the training workspaces alone, so it may run between
+        forward_backward and optimizer_step.  With ``embeds`` the mapper's non-saving forward runs in the mapper's save = 0 workspace;
+        the activations and the input a forward(save=True) keeps for MapperEngine.backward are left as they are."""
+        if (embeds is None) == (prefix is None):
+            raise ValueError("ClipCapEngine.score takes exactly one of embeds and prefix")
+        l = _lib.lib()
+        g, m = self.gpt2, self.mapper
+        dev = g.arena.device
+        _require_cuda(g.arena.w32, "ClipCapEngine.score")
+        tokens = tokens.to(device=dev, dtype=torch.int64).contiguous()
+        if tokens.dim() != 2 or tokens.shape[0] < 1 or tokens.shape[1] < 1:
+            raise ValueError(f"tokens must be (B, cap) with B, cap >= 1, got {tuple(tokens.shape)}")
+        B, cap = tokens.shape
+        if prefix is not None:
+            prefix = prefix.to(device=dev, dtype=torch.float32).contiguous()
+            if prefix.dim() != 3 or prefix.shape[0] != B or prefix.shape[1] < 1 or prefix.shape[2] != g.dims["D"]:
+                raise ValueError(f"prefix must be ({B}, L >= 1, {g.dims['D']}), got {tuple(prefix.shape)}")
+            L = prefix.shape[1]
+        else:
+            embeds = embeds.to(device=dev, dtype=torch.float32)
+            if embeds.shape[0] != B:
+                raise ValueError(f"embeds has {embeds.shape[0]} rows for {B} token rows")
+            L = m.dims["L"]
+        T = L + cap
+        if T > g.dims["NPOS"]:
+            raise ValueError(f"prefix ({L}) + caption ({cap}) positions exceed n_positions = {g.dims['NPOS']}")
+        out = torch.empty(B, cap, dtype=torch.float32, device=dev)
+        stats = torch.empty(B, 2, dtype=torch.float32, device=dev)
+        step = B if chunk is None else max(1, int(chunk))
+        g.arena.sync_bf16()
+        st = _stream(dev)
+        ga = g.arena
+        for lo in range(0, B, step):
+            hi = min(B, lo + step)
+            if prefix is not None:
+                pre = prefix[lo:hi]
+            else:
+                kept_alive = getattr(m, "_last", None)      # the input a saved forward holds until its backward has run
+                pre = m.forward(embeds[lo:hi], save=False)
+                if kept_alive is not None:
+                    m._last = kept_alive
+            shp = g.shape(hi - lo, L, T, cap, 0)
+            ws = self._score_workspace(shp)
+            tk = tokens[lo:hi]
+            check(l.cc_gpt2_embed(C.byref(g.cfg), C.byref(shp), _p(ga.w32), _p(pre), _p(tk), _p(ws), st), "cc_gpt2_embed")
+            check(l.cc_gpt2_fwd(C.byref(g.cfg), C.byref(shp), _p(ga.w32), _p(ga.w16), _p(ws), st), "cc_gpt2_fwd")
+            check(l.cc_lmhead_score(C.byref(g.cfg), C.byref(shp), _p(ga.w32), _p(ga.w16), _p(ws), _p(tk), int(bool(ignore_zero)), _p(out[lo:hi]),
+                                    _p(stats[lo:hi]), st), "cc_lmhead_score")
+        return out, stats[:, 0].contiguous(), stats[:, 1].contiguous()
+
+    def _score_workspace(self, shp: Gpt2Shape) -> torch.Tensor:
+        """The scoring pass's own buffer (grown on demand, like Gpt2Engine.workspace; never one of the engine's per-mode buffers)."""
+        g = self.gpt2
+        nbytes = _lib.lib().cc_gpt2_ws_bytes(C.byref(g.cfg), C.byref(shp))
+        check(nbytes, "cc_gpt2_ws_bytes")
+        ws = getattr(self, "_score_ws", None)
+        if ws is None or ws.numel() < nbytes or ws.device != g.arena.device:
+            self._score_ws = None
+            ws = self._score_ws = torch.empty(nbytes, dtype=torch.uint8, device=g.arena.device)
+        return ws
+
     def zero_grad(self):
         if self.mapper.arena.g32 is not None:
             self.mapper.arena.g32.zero_()

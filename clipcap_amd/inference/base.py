@@ -173,17 +173,33 @@ def _rows_for(embeds: torch.Tensor, number_to_generate: int) -> torch.Tensor:
 
 def generate_nucleus_sampling(model, tokenizer: Callable, embeds: torch.Tensor, number_to_generate: int = 1,
                               text_prefix_tokens: Optional[torch.Tensor] = None, entry_length: int = 67, top_p: float = 0.8, top_k=None,
-                              temperature: float = 1.0, generator: Optional[torch.Generator] = None) -> List[str]:
+                              temperature: float = 1.0, generator: Optional[torch.Generator] = None, rerank: bool = False) -> List[str]:
     """base.py:135-201 with a KV cache and the sampling step on the device.  The reference is batch-1 and loops number_to_generate
     times; here every (prefix row, repetition) is one row of a single batched decode.  The returned text of a row includes its
-    stop token, as the reference's does (it appends before breaking, base.py:186-195)."""
+    stop token, as the reference's does (it appends before breaking, base.py:186-195).
+    ``rerank`` (not in the reference; off by default): the ``number_to_generate`` texts of every prefix row come back ordered by their
+    length-normalised likelihood under the model, best first (inference/score.py rerank_captions), instead of in sampling order."""
     stop = _stop_id(tokenizer)
     embeds = _with_text_prefix(model, embeds, text_prefix_tokens)
     toks, stop_pos = sample_tokens(model, _rows_for(embeds, number_to_generate), entry_length, stop, mode=0, top_p=top_p, top_k=top_k,
                                    temperature=temperature, generator=generator)
+    rows = list(range(toks.shape[0]))
+    if rerank and number_to_generate > 1:
+        rows = _likelihood_order(model, embeds, toks, stop_pos, number_to_generate)
     head = [] if text_prefix_tokens is None else [int(t) for t in text_prefix_tokens.flatten()]
     toks, stop_pos = toks.cpu(), stop_pos.cpu()
-    return [tokenizer.decode(head + toks[r, :min(int(stop_pos[r]) + 1, toks.shape[1])].tolist()) for r in range(toks.shape[0])]
+    return [tokenizer.decode(head + toks[r, :min(int(stop_pos[r]) + 1, toks.shape[1])].tolist()) for r in rows]
+
+
+def _likelihood_order(model, embeds: torch.Tensor, toks: torch.Tensor, stop_pos: torch.Tensor, n_gen: int) -> List[int]:
+    """Row indices of a sample_tokens result of ``n_gen`` repetitions per prefix row, each prefix row's repetitions best first:
+    every text as it is returned (up to and including its stop token) scored by rerank_captions."""
+    from clipcap_amd.inference.score import rerank_captions
+    keep = torch.arange(toks.shape[1], device=toks.device).view(1, -1) <= stop_pos.view(-1, 1)
+    cand = torch.where(keep, toks, torch.full_like(toks, -1)).view(embeds.shape[0], n_gen, -1)
+    order, _ = rerank_captions(model, embeds, cand)
+    base = torch.arange(embeds.shape[0], device=order.device).view(-1, 1) * n_gen
+    return (base + order).flatten().tolist()
 
 
 def generate_no_beam(model, tokenizer: Callable, embeds: torch.Tensor, text_prefix_tokens: Optional[torch.Tensor] = None,

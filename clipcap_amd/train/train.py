@@ -137,6 +137,34 @@ def _run_epochs(args, model, dataset, device, sched, reducer, saver, sharded, ra
     return step
 
 
+@torch.no_grad()
+def evaluate(model, dataset_path: str, batch_size: int = 256, max_batches=None, *, tokenizer=None, max_token_length: int = 64) -> dict:
+    """Held-out loss of ``model`` over a dataset folder (the layout train() reads): {"loss", "perplexity", "tokens"}.
+
+    ``loss`` is the training objective (model.py:94-113: mean cross-entropy over the kept targets, ignore_index = 0, pads -> 0) on data
+    the model is not being trained on — token-weighted over the batches, from the forward-only scoring pass (ClipCapEngine.score with
+    ignore_zero), so it needs no gradient arenas and no training workspace.  ``perplexity`` = exp(loss); ``tokens`` = kept targets seen.
+    ``max_batches``: stop after that many batches.  ``tokenizer`` / ``max_token_length``: as get_dataloader takes them (default: the
+    tokenizer of model.config.language_model)."""
+    import math
+    dataset, _ = get_dataloader(dataset_path, model.config.language_model, batch_size, tokenizer=tokenizer, max_token_length=max_token_length)
+    device = model.language_model.engine.arena.device
+    total = torch.zeros(2, dtype=torch.float64, device=device)          # [sum of kept log-probs, kept count]
+    try:
+        for i, (tokens, embeds) in enumerate(DevicePrefetcher(dataset, device)):
+            if max_batches is not None and i >= max_batches:
+                break
+            _, logprob, count = model.engine.score(tokens, embeds, ignore_zero=True)
+            total[0] += logprob.sum(dtype=torch.float64)
+            total[1] += count.sum(dtype=torch.float64)
+    finally:
+        if hasattr(dataset, "close"):
+            dataset.close()
+    s, n = (float(v) for v in total.cpu())
+    loss = -s / max(n, 1.0)
+    return {"loss": loss, "perplexity": math.exp(min(loss, 700.0)), "tokens": int(n)}
+
+
 def start_training() -> int:
     parser = ArgumentParser(description=__doc__, formatter_class=ArgumentDefaultsHelpFormatter)
     parser = add_training_args(parser)

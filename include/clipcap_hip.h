@@ -196,6 +196,12 @@ int cc_gpt2_logits_bwd(const cc_gpt2_cfg* cfg, const cc_gpt2_shape* shp, const f
  * pads(-1)->0).  stats (2 device floats, zeroed by this call): [0] sum of kept-row losses, [1] number of kept rows. */
 int cc_lmhead_ce_fwd(const cc_gpt2_cfg* cfg, const cc_gpt2_shape* shp, const float* w32, const uint16_t* w16, void* ws,
                      const int64_t* tokens, float* stats, void* stream);
+/* teacher-forced log-likelihood of tokens[b, :] given the pass's prefix rows: forward only, nothing differentiable kept,
+ * no logits stored.  Needs a mode-0 pass with L >= 1 and cap == T - L (cc_gpt2_embed, cc_gpt2_fwd with the same shape).
+ * token_logprob fp32 [B, cap]; sample_stats fp32 [B, 2] = {sum of kept log-probs, kept count}.  ignore_zero != 0 reproduces
+ * the training loss's ignore_index = 0 (model.py:108-109).  Both outputs are fully written by the call. */
+int cc_lmhead_score(const cc_gpt2_cfg* cfg, const cc_gpt2_shape* shp, const float* w32, const uint16_t* w16, void* ws,
+                    const int64_t* tokens, int32_t ignore_zero, float* token_logprob, float* sample_stats, void* stream);
 /* backward of the above through lm_head and ln_f into the residual-stream gradient kept in the workspace.
  * denom (device float[1]) = divisor of the mean (local or all-reduced kept-row count).  loss_scale (device float[1], NULL = 1):
  * every gradient of this backward pass (dprefix and what is accumulated into the g32 arenas) is multiplied by it — fp16 operands
@@ -461,7 +467,7 @@ int cc_batch_sum(const float* src, int64_t src_stride, float* dst, int32_t len, 
  * GEMM host launch of the library — with HIP events recorded on the launch stream.  PROCESS-WIDE, off by default, never used by
  * the product path.
  * ------------------------------------------------------------------------------------------------------------ */
-#define CC_SITE_LMHEAD_FWD 1      /* [B*cap, D] x wte^T           (cc_lmhead_ce_fwd) */
+#define CC_SITE_LMHEAD_FWD 1      /* [B*cap, D] x wte^T           (cc_lmhead_ce_fwd, cc_lmhead_score) */
 #define CC_SITE_LMHEAD_DGRAD 2    /* dlogits [B*cap, Vp] x wte    (cc_lmhead_ce_bwd) */
 #define CC_SITE_GPT2_FC_FWD 3     /* c_fc  [B*T, D] x [D, 4D]     (cc_gpt2_fwd, per layer) */
 #define CC_SITE_GPT2_PROJ2_FWD 4  /* mlp.c_proj [B*T, 4D] x [4D, D] (cc_gpt2_fwd) */
