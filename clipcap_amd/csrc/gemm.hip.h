@@ -130,8 +130,8 @@ template <class E> struct epi_row_strip { static constexpr bool value = false; }
 // functors whose additive input can initialise the accumulators (Epi::init_from_input() / init4(row, col, acc4)): see gemm_stag256_body
 template <class E, class = void> struct epi_acc_init { static constexpr bool value = false; };
 template <class E> struct epi_acc_init<E, decltype((void)&E::init4)> { static constexpr bool value = true; };
-template <class E, class = void> struct epi_strip_aux { static constexpr bool value = false; };
-template <class E> struct epi_strip_aux<E, decltype((void)sizeof(typename E::StripAux))> { static constexpr bool value = true; };
+template <class E, class = void> struct epi_strip_aux { static constexpr bool value = false; typedef char type; };
+template <class E> struct epi_strip_aux<E, decltype((void)sizeof(typename E::StripAux))> { static constexpr bool value = true; typedef typename E::StripAux type; };
 
 // ---- epilogue: wave-private LDS strip [16][68] fp32; C layout of 16x16x32: col = lane&15, row = (lane>>4)*4 + reg.
 // Every lane ends up with 8 consecutive columns of one row -> vector epilogue.  Caller must have passed a barrier
@@ -140,8 +140,10 @@ template <class Epi, int I0 = 0, int I1 = 4>
 __device__ __forceinline__ void gemm_epilogue(f32x4 (&acc)[4][4], char* smem, int wave, int lane, int row0, int col0, const Epi& epi) {
     float* strip = reinterpret_cast<float*>(smem) + wave * (16 * G_EPI_LD);
     const int er = (lane >> 4) * 4, ec = lane & 15;
-    if constexpr (epi_strip_aux<Epi>::value) {
-        typename Epi::StripAux aux[4][2];
+    constexpr bool kAux = epi_strip_aux<Epi>::value;
+    typename epi_strip_aux<Epi>::type aux[4][2];
+    (void)aux;
+    if constexpr (kAux) {
 #pragma unroll
         for (int i = I0; i < I1; i++)
 #pragma unroll
@@ -150,24 +152,6 @@ __device__ __forceinline__ void gemm_epilogue(f32x4 (&acc)[4][4], char* smem, in
                 aux[i][s] = epi.load_aux(row0 + i * 16 + (q >> 3), col0 + (q & 7) * 8);
             }
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = I0; i < I1; i++) {
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) strip[(er + r) * G_EPI_LD + j * 16 + ec] = acc[i][j][r];
-#pragma unroll
-            for (int s = 0; s < 2; s++) {
-                const int q = lane + 64 * s;
-                const int lr = q >> 3, c8 = q & 7;
-                float v[8];
-                const float4 a = *reinterpret_cast<const float4*>(strip + lr * G_EPI_LD + c8 * 8);
-                const float4 b = *reinterpret_cast<const float4*>(strip + lr * G_EPI_LD + c8 * 8 + 4);
-                v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-                epi(row0 + i * 16 + lr, col0 + c8 * 8, v, aux[i][s]);
-            }
-        }
-        return;
     }
 #pragma unroll
     for (int i = I0; i < I1; i++) {
@@ -183,7 +167,8 @@ __device__ __forceinline__ void gemm_epilogue(f32x4 (&acc)[4][4], char* smem, in
             const float4 a = *reinterpret_cast<const float4*>(strip + lr * G_EPI_LD + c8 * 8);
             const float4 b = *reinterpret_cast<const float4*>(strip + lr * G_EPI_LD + c8 * 8 + 4);
             v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-            epi(row0 + i * 16 + lr, col0 + c8 * 8, v);
+            if constexpr (kAux) epi(row0 + i * 16 + lr, col0 + c8 * 8, v, aux[i][s]);
+            else epi(row0 + i * 16 + lr, col0 + c8 * 8, v);
         }
     }
 }
@@ -269,6 +254,15 @@ __device__ __forceinline__ void tile_coords(int tile, int tiles_m, int tiles_n, 
     tn = r / gm;
 }
 
+// (of the 128 x 128 kernels' repeated parts only this is shared: their tile set-up, K-step and the 8-wave kernels' partial-sum exchange,
+// moved into helpers, come out of the compiler scheduled differently, and these kernels are kept instruction-identical across refactors)
+__device__ __forceinline__ void acc_zero(f32x4 (&acc)[4][4]) {
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
 template <int AL, int BL, class Epi>
 __global__ __launch_bounds__(G_THREADS, 2) void gemm_bf16_kernel(const op16_t* __restrict__ A,
                                                                   const op16_t* __restrict__ B, GemmShape g, Epi epi) {
@@ -284,10 +278,7 @@ __global__ __launch_bounds__(G_THREADS, 2) void gemm_bf16_kernel(const op16_t* _
     const int nk = (kend - kbeg + G_BK - 1) / G_BK;
 
     f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    acc_zero(acc);
 
     StageRegs ra, rb;
     if (nk > 0) {
@@ -374,10 +365,7 @@ __global__ __launch_bounds__(G_THREADS, 2) void gemm_nt_glds_kernel(const op16_t
     const int nk = (min(g.K, kbeg + g.k_chunk) - kbeg) / G_BK;
 
     f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    acc_zero(acc);
 
     // Two blocks share a CU.  Launched together they run in lockstep — both in the MFMA loop, then both in the (VALU) epilogue — so the
     // two pipes never overlap.  The blocks of the odd 256-block dispatch waves start a fraction of a tile late, which keeps one block's
@@ -442,10 +430,7 @@ __global__ __launch_bounds__(G_THREADS, 2) void gemm_nt_glds_x3f_kernel(const op
     const int m0 = tm * G_BM, n0 = tn * G_BN;
     const int Kl = g.K / 3, nc = Kl / G_BK;                   // logical K, chunks
     f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    acc_zero(acc);
     const int frow = lane & 15, fchunk = lane >> 4;
     op16x8 ah[2][4], bh[2][4];
 #define X3F_ISSUE(C, LO, BUF)                                                                                            \
@@ -517,10 +502,7 @@ __global__ __launch_bounds__(G_THREADS, 1) void gemm_nt_glds4_kernel(const op16_
     const int kbeg = blockIdx.z * g.k_chunk;
     const int nk = (min(g.K, kbeg + g.k_chunk) - kbeg) / G_BK;
     f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    acc_zero(acc);
 #define G4_ISSUE(T)                                                                                                      \
     {                                                                                                                    \
         char* st_ = smem4 + ((T) & 3) * 2 * G_TILE_BYTES;                                                                \
@@ -577,7 +559,7 @@ __global__ __launch_bounds__(2 * G_THREADS, 1) void gemm_nt_glds4x2_kernel(const
     const int m0 = tm * G_BM, n0 = tn * G_BN;
     const int kbeg = blockIdx.z * g.k_chunk;
     const int nk = (min(g.K, kbeg + g.k_chunk) - kbeg) / G_BK;
-    f32x4 acc[4][4];
+    f32x4 acc[4][4];                                          // (cleared in place: through acc_zero one instantiation is scheduled differently)
 #pragma unroll
     for (int i = 0; i < 4; i++)
 #pragma unroll
@@ -652,10 +634,7 @@ __global__ __launch_bounds__(2 * G_THREADS, 1) void gemm_nt_glds4x2_x3f_kernel(c
     const int Kl = g.K / 3;                                   // logical K (g.K = K' = 3 K, one slice)
     const int nk = 2 * (Kl / G_BK);                           // a K chunk = its hi stage, then its lo stage
     f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    acc_zero(acc);
     // group 0 streams the A tile, group 1 the B tile: 4 DMA instructions per wave and K-tile
 #define G4_ISSUE(T)                                                                                                      \
     {                                                                                                                    \
@@ -1680,22 +1659,7 @@ struct EpiBF16T {
             const float4 b1 = *reinterpret_cast<const float4*>(bias + col + 4);
             v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w; v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
         }
-        if (act_() == 3) {
-            float dg[8];
-#pragma unroll
-            for (int e = 0; e < 8; e++) gelu_new_both(v[e], v[e], dg[e]);
-            if (has_pre()) { if (nt_()) act_st8_nt(pre + (size_t)row * ldc + col, dg); else act_st8(pre + (size_t)row * ldc + col, dg); }
-        } else {
-            if (has_pre()) act_st8(pre + (size_t)row * ldc + col, v);
-            if (act_() == 1) {
-#pragma unroll
-                for (int e = 0; e < 8; e++) v[e] = fmaxf(v[e], 0.f);
-            } else if (act_() == 2) {
-#pragma unroll
-                for (int e = 0; e < 8; e++) v[e] = gelu_new_f(v[e]);
-            }
-        }
-        epi_store8(C, ldc, row, col, v, img);
+        finish(row, col, v);
     }
     // Split form for the 256-row kernels (see gemm_nt_stag256_kernel): every global LOAD of the epilogue happens before its first
     // STORE — with loads and stores both pending on the one vmcnt counter the compiler must wait vmcnt(0), i.e. drain the store
@@ -1708,6 +1672,11 @@ struct EpiBF16T {
         if (row >= M || col >= Ns) return;
 #pragma unroll
         for (int e = 0; e < 8; e++) v[e] += b[e];
+        finish(row, col, v);
+    }
+  private:
+    // both entry points end here, on v = acc + bias: the pre-activation copy, the activation, the store
+    __device__ __forceinline__ void finish(int row, int col, float (&v)[8]) const {
         if (act_() == 3) {
             float dg[8];
 #pragma unroll
@@ -1781,8 +1750,8 @@ struct EpiResid {
                 y[e] *= m0; y[e + 1] *= m1;
             }
         }
-        *reinterpret_cast<float4*>(out + o) = make_float4(r0.x + y[0], r0.y + y[1], r0.z + y[2], r0.w + y[3]);
-        *reinterpret_cast<float4*>(out + o + 4) = make_float4(r1.x + y[4], r1.y + y[5], r1.z + y[6], r1.w + y[7]);
+        const float r[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+        store_sum(o, r, y);
     }
     // 256-row kernels, no dropout: the accumulators START from the residual (gemm_stag256_body), pre4 then has nothing to add
     bool acc_init = false;
@@ -1814,9 +1783,13 @@ struct EpiResid {
     __device__ __forceinline__ void bias8(int col, float (&b)[8]) const { load_bias8(drop.thresh ? nullptr : bias, col, Ns, b); }
     __device__ __forceinline__ void fin(int row, int col, float (&v)[8], const float (&b)[8]) const {
         if (row >= M || col >= Ns) return;
-        const size_t o = (size_t)row * ld + col;
-        *reinterpret_cast<float4*>(out + o) = make_float4(v[0] + b[0], v[1] + b[1], v[2] + b[2], v[3] + b[3]);
-        *reinterpret_cast<float4*>(out + o + 4) = make_float4(v[4] + b[4], v[5] + b[5], v[6] + b[6], v[7] + b[7]);
+        store_sum((size_t)row * ld + col, v, b);
+    }
+  private:
+    // both entry points end here: out = x + y, two 16-B stores
+    __device__ __forceinline__ void store_sum(size_t o, const float (&x)[8], const float (&y)[8]) const {
+        *reinterpret_cast<float4*>(out + o) = make_float4(x[0] + y[0], x[1] + y[1], x[2] + y[2], x[3] + y[3]);
+        *reinterpret_cast<float4*>(out + o + 4) = make_float4(x[4] + y[4], x[5] + y[5], x[6] + y[6], x[7] + y[7]);
     }
 };
 
@@ -1939,6 +1912,74 @@ using EpiDAct = EpiDActT<>;
 template <class E> struct epi_is_dact { static constexpr bool value = false; };
 template <int A> struct epi_is_dact<EpiDActT<A>> { static constexpr bool value = true; };
 
+// ---- row statistics of the lm_head functors: per (row, 64-column block) the maximum m and the sum of exp(x - m) over the columns < V ----
+// the lanes that together hold one row's 64-column block differ in the lane-id bits LO .. HI: 1, 2, 4 in the 8-wide form, 16, 32 in the strip form
+template <int LO, int HI>
+__device__ __forceinline__ float xor_max(float m) {
+#pragma unroll
+    for (int d = LO; d <= HI; d <<= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
+    return m;
+}
+template <int LO, int HI>
+__device__ __forceinline__ float xor_sum(float s) {
+#pragma unroll
+    for (int d = LO; d <= HI; d <<= 1) s += __shfl_xor(s, d, 64);
+    return s;
+}
+// 8-wide form: the lane holds columns col .. col + 7.  (EpiLMHead, which also zeroes the columns >= V in v, keeps its own copy: through
+// this helper one of its kernels changes the encoding of a compare, and the kernels are kept instruction-identical across refactors.)
+__device__ __forceinline__ void row_stats8(int col, int V, const float (&v)[8], float& m, float& s) {
+    m = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < 8; e++)
+        if (col + e < V) m = fmaxf(m, v[e]);
+    m = xor_max<1, 4>(m);
+    s = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; e++)
+        if (col + e < V) s += __expf(v[e] - m);
+    s = xor_sum<1, 4>(s);
+}
+// strip form: the lane holds columns ca .. ca + 7 and cb .. cb + 7.  ZERO_PAD: columns >= V are also set to 0 in va / vb (they are stored).
+// FAST: a block that lies whole inside V (wave-uniform test) skips the column tests and takes its exponentials as
+// exp2(x log2 e - m log2 e); without it every block goes through __expf(x - m)
+template <bool ZERO_PAD, bool FAST>
+__device__ __forceinline__ void row_stats_strip(int ca, int cb, int V, float (&va)[8], float (&vb)[8], float& m, float& s) {
+    constexpr float L2E = 1.4426950408889634f;
+    s = 0.f;
+    if (FAST && __builtin_amdgcn_readfirstlane(ca | 63) < V) {
+        m = fmaxf(fmaxf(fmaxf(va[0], va[1]), fmaxf(va[2], va[3])), fmaxf(fmaxf(va[4], va[5]), fmaxf(va[6], va[7])));
+        m = fmaxf(m, fmaxf(fmaxf(fmaxf(vb[0], vb[1]), fmaxf(vb[2], vb[3])), fmaxf(fmaxf(vb[4], vb[5]), fmaxf(vb[6], vb[7]))));
+        m = xor_max<16, 32>(m);
+        const float ml = -m * L2E;
+#pragma unroll
+        for (int e = 0; e < 8; e++) s += __builtin_amdgcn_exp2f(fmaf(va[e], L2E, ml)) + __builtin_amdgcn_exp2f(fmaf(vb[e], L2E, ml));
+    } else {
+        m = -INFINITY;
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            if (ca + e >= V) { if (ZERO_PAD) va[e] = 0.f; } else m = fmaxf(m, va[e]);
+            if (cb + e >= V) { if (ZERO_PAD) vb[e] = 0.f; } else m = fmaxf(m, vb[e]);
+        }
+        m = xor_max<16, 32>(m);
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            if (ca + e < V) s += __expf(va[e] - m);
+            if (cb + e < V) s += __expf(vb[e] - m);
+        }
+    }
+    s = xor_sum<16, 32>(s);
+}
+// the partials of the block that starts at column col (one lane per row and block calls this); a block with no column < V (m = -inf)
+// gets the sum 0.  (It takes the functor, not its pointers: the fields are then read where the statements stood, and the generated
+// code does not change.)  EpiLMHeadExp, with its own exponent form and clamp, keeps its own statistics.
+template <class E>
+__device__ __forceinline__ void put_partials(const E& f, int row, int col, float m, float s) {
+    const int blk = col >> 6;
+    f.pmax[(size_t)row * f.npart + blk] = m;
+    f.psum[(size_t)row * f.npart + blk] = (m == -INFINITY) ? 0.f : s;
+}
+
 // lm_head: bf16 logits + per-(row, 64-column block) softmax partials from the fp32 accumulators + exact target logit.
 struct EpiLMHead {
     act_t* C;
@@ -1979,39 +2020,10 @@ struct EpiLMHead {
     typedef int RowAux;                                                               // per-row value fetched before the first store: the target id
     __device__ __forceinline__ int load_row(int row) const { return row < M ? target[row] : -1; }
     __device__ __forceinline__ void strip(int row, int ca, int cb, float (&va)[8], float (&vb)[8], int t) const {
-        constexpr float L2E = 1.4426950408889634f;
-        float m, s = 0.f;
-        if (__builtin_amdgcn_readfirstlane(ca | 63) < V) {          // the whole 64-column block is inside the vocabulary (wave-uniform)
-            m = fmaxf(fmaxf(fmaxf(va[0], va[1]), fmaxf(va[2], va[3])), fmaxf(fmaxf(va[4], va[5]), fmaxf(va[6], va[7])));
-            m = fmaxf(m, fmaxf(fmaxf(fmaxf(vb[0], vb[1]), fmaxf(vb[2], vb[3])), fmaxf(fmaxf(vb[4], vb[5]), fmaxf(vb[6], vb[7]))));
-            m = fmaxf(m, __shfl_xor(m, 16, 64));
-            m = fmaxf(m, __shfl_xor(m, 32, 64));
-            const float ml = -m * L2E;
-#pragma unroll
-            for (int e = 0; e < 8; e++) s += __builtin_amdgcn_exp2f(fmaf(va[e], L2E, ml)) + __builtin_amdgcn_exp2f(fmaf(vb[e], L2E, ml));
-        } else {
-            m = -INFINITY;
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-                if (ca + e >= V) va[e] = 0.f; else m = fmaxf(m, va[e]);
-                if (cb + e >= V) vb[e] = 0.f; else m = fmaxf(m, vb[e]);
-            }
-            m = fmaxf(m, __shfl_xor(m, 16, 64));
-            m = fmaxf(m, __shfl_xor(m, 32, 64));
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-                if (ca + e < V) s += __expf(va[e] - m);
-                if (cb + e < V) s += __expf(vb[e] - m);
-            }
-        }
-        s += __shfl_xor(s, 16, 64);
-        s += __shfl_xor(s, 32, 64);
+        float m, s;
+        row_stats_strip<true, true>(ca, cb, V, va, vb, m, s);
         if (row >= M) return;
-        if ((ca & 63) == 0 && ca < ldc) {
-            const int blk = ca >> 6;
-            pmax[(size_t)row * npart + blk] = m;
-            psum[(size_t)row * npart + blk] = (m == -INFINITY) ? 0.f : s;
-        }
+        if ((ca & 63) == 0 && ca < ldc) put_partials(*this, row, ca, m, s);
         if (ca < ldc) {
             if (t >= ca && t < ca + 8) tgt_logit[row] = va[t - ca];
             act_st8(C + (size_t)row * ldc + ca, va);
@@ -2097,26 +2109,10 @@ struct EpiLogits {
     int ldc, M, Ns, V, npart;
     __device__ __forceinline__ void operator()(int row, int col, float (&v)[8]) const {
         const bool ok = row < M && col < Ns;
-        float m = -INFINITY;
-#pragma unroll
-        for (int e = 0; e < 8; e++)
-            if (col + e < V) m = fmaxf(m, v[e]);
-        m = fmaxf(m, __shfl_xor(m, 1, 64));
-        m = fmaxf(m, __shfl_xor(m, 2, 64));
-        m = fmaxf(m, __shfl_xor(m, 4, 64));
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; e++)
-            if (col + e < V) s += __expf(v[e] - m);
-        s += __shfl_xor(s, 1, 64);
-        s += __shfl_xor(s, 2, 64);
-        s += __shfl_xor(s, 4, 64);
+        float m, s;
+        row_stats8(col, V, v, m, s);
         if (!ok) return;
-        if ((col & 63) == 0) {
-            const int blk = col >> 6;
-            pmax[(size_t)row * npart + blk] = m;
-            psum[(size_t)row * npart + blk] = (m == -INFINITY) ? 0.f : s;
-        }
+        if ((col & 63) == 0) put_partials(*this, row, col, m, s);
         float* p = C + (size_t)row * ldc + col;
         *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
         *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
@@ -2124,27 +2120,10 @@ struct EpiLogits {
     typedef int RowAux;
     __device__ __forceinline__ int load_row(int) const { return 0; }
     __device__ __forceinline__ void strip(int row, int ca, int cb, float (&va)[8], float (&vb)[8], int) const {
-        float m = -INFINITY, s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; e++) {
-            if (ca + e < V) m = fmaxf(m, va[e]);
-            if (cb + e < V) m = fmaxf(m, vb[e]);
-        }
-        m = fmaxf(m, __shfl_xor(m, 16, 64));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
-#pragma unroll
-        for (int e = 0; e < 8; e++) {
-            if (ca + e < V) s += __expf(va[e] - m);
-            if (cb + e < V) s += __expf(vb[e] - m);
-        }
-        s += __shfl_xor(s, 16, 64);
-        s += __shfl_xor(s, 32, 64);
+        float m, s;
+        row_stats_strip<false, false>(ca, cb, V, va, vb, m, s);       // no fast path: these bits reach the beam search
         if (row >= M) return;
-        if ((ca & 63) == 0 && ca < Ns) {
-            const int blk = ca >> 6;
-            pmax[(size_t)row * npart + blk] = m;
-            psum[(size_t)row * npart + blk] = (m == -INFINITY) ? 0.f : s;
-        }
+        if ((ca & 63) == 0 && ca < Ns) put_partials(*this, row, ca, m, s);
         if (ca < Ns) {
             float* p = C + (size_t)row * ldc + ca;
             *reinterpret_cast<float4*>(p) = make_float4(va[0], va[1], va[2], va[3]);
@@ -2167,65 +2146,20 @@ struct EpiLMHeadScore {
     int M, N, V, npart;    // V = true vocab (columns >= V are padding: excluded from the partials)
     __device__ __forceinline__ void operator()(int row, int col, float (&v)[8]) const {
         const bool ok = row < M && col < N;
-        float m = -INFINITY;
-#pragma unroll
-        for (int e = 0; e < 8; e++)
-            if (col + e < V) m = fmaxf(m, v[e]);
-        m = fmaxf(m, __shfl_xor(m, 1, 64));
-        m = fmaxf(m, __shfl_xor(m, 2, 64));
-        m = fmaxf(m, __shfl_xor(m, 4, 64));
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; e++)
-            if (col + e < V) s += __expf(v[e] - m);
-        s += __shfl_xor(s, 1, 64);
-        s += __shfl_xor(s, 2, 64);
-        s += __shfl_xor(s, 4, 64);
+        float m, s;
+        row_stats8(col, V, v, m, s);
         if (!ok) return;
-        if ((col & 63) == 0) {
-            const int blk = col >> 6;
-            pmax[(size_t)row * npart + blk] = m;
-            psum[(size_t)row * npart + blk] = (m == -INFINITY) ? 0.f : s;
-        }
+        if ((col & 63) == 0) put_partials(*this, row, col, m, s);
         const int t = target[row] - col;
         if (t >= 0 && t < 8) tgt_logit[row] = v[t];
     }
     typedef int RowAux;                                                               // the row's target id
     __device__ __forceinline__ int load_row(int row) const { return row < M ? target[row] : -1; }
     __device__ __forceinline__ void strip(int row, int ca, int cb, float (&va)[8], float (&vb)[8], int t) const {
-        constexpr float L2E = 1.4426950408889634f;
-        float m, s = 0.f;
-        if (__builtin_amdgcn_readfirstlane(ca | 63) < V) {          // the whole 64-column block is inside the vocabulary (wave-uniform)
-            m = fmaxf(fmaxf(fmaxf(va[0], va[1]), fmaxf(va[2], va[3])), fmaxf(fmaxf(va[4], va[5]), fmaxf(va[6], va[7])));
-            m = fmaxf(m, fmaxf(fmaxf(fmaxf(vb[0], vb[1]), fmaxf(vb[2], vb[3])), fmaxf(fmaxf(vb[4], vb[5]), fmaxf(vb[6], vb[7]))));
-            m = fmaxf(m, __shfl_xor(m, 16, 64));
-            m = fmaxf(m, __shfl_xor(m, 32, 64));
-            const float ml = -m * L2E;
-#pragma unroll
-            for (int e = 0; e < 8; e++) s += __builtin_amdgcn_exp2f(fmaf(va[e], L2E, ml)) + __builtin_amdgcn_exp2f(fmaf(vb[e], L2E, ml));
-        } else {
-            m = -INFINITY;
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-                if (ca + e < V) m = fmaxf(m, va[e]);
-                if (cb + e < V) m = fmaxf(m, vb[e]);
-            }
-            m = fmaxf(m, __shfl_xor(m, 16, 64));
-            m = fmaxf(m, __shfl_xor(m, 32, 64));
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-                if (ca + e < V) s += __expf(va[e] - m);
-                if (cb + e < V) s += __expf(vb[e] - m);
-            }
-        }
-        s += __shfl_xor(s, 16, 64);
-        s += __shfl_xor(s, 32, 64);
+        float m, s;
+        row_stats_strip<false, true>(ca, cb, V, va, vb, m, s);
         if (row >= M) return;
-        if ((ca & 63) == 0 && ca < N) {
-            const int blk = ca >> 6;
-            pmax[(size_t)row * npart + blk] = m;
-            psum[(size_t)row * npart + blk] = (m == -INFINITY) ? 0.f : s;
-        }
+        if ((ca & 63) == 0 && ca < N) put_partials(*this, row, ca, m, s);
         if (t >= ca && t < ca + 8 && ca < N) tgt_logit[row] = va[t - ca];
         if (t >= cb && t < cb + 8 && cb < N) tgt_logit[row] = vb[t - cb];
     }
@@ -2238,6 +2172,14 @@ template <> struct epi_row_strip<EpiLMHeadExp> { static constexpr bool value = t
 // ------------------------------------------------------------------------------------------------
 // Host launcher
 // ------------------------------------------------------------------------------------------------
+// Launch of a kernel with dynamic LDS beyond the default limit: the first launch of each kernel instantiation raises its limit to `shmem`
+// (every instantiation is only ever launched with one size).
+template <auto Kernel, class... Args>
+inline void launch_dyn(dim3 grid, dim3 block, size_t shmem, hipStream_t st, const Args&... args) {
+    static bool attr = false;
+    if (!attr) { (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); attr = true; }
+    hipLaunchKernelGGL(Kernel, grid, block, shmem, st, args...);
+}
 template <class Epi>
 inline int launch_gemm_s64(const op16_t* A, int lda, const op16_t* B, int ldb, int M, int N, int K, int ksplit, int nj, const Epi& epi, int* ks_eff,
                            hipStream_t st, const op16_t* Bimg = nullptr);
@@ -2311,13 +2253,7 @@ inline int launch_gemm(int al, int bl, const op16_t* A, int lda, const op16_t* B
         const int bm = 32 * ni;
         const size_t sh = (size_t)H_NS * (bm + H_BN) * H_BK * 2;
         const dim3 gr((unsigned)(((M + bm - 1) / bm) * ((N + 64 * nj - 1) / (64 * nj))), 1, (unsigned)ksplit);
-#define CC_LAUNCH_STAG(NJ_, NI_)                                                                                         \
-    {                                                                                                                    \
-        static bool attr_ = false;                                                                                       \
-        if (!attr_) { (void)hipFuncSetAttribute((const void*)gemm_nt_stag256_kernel<Epi, NJ_, false, NI_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); attr_ = true; } \
-        hipLaunchKernelGGL((gemm_nt_stag256_kernel<Epi, NJ_, false, NI_>), gr, dim3(512), sh, st, A, B, g, epi);        \
-    }
-        if (nj == 4 && ni == 8) CC_LAUNCH_STAG(4, 8)
+        if (nj == 4 && ni == 8) launch_dyn<gemm_nt_stag256_kernel<Epi, 4, false, 8>>(gr, dim3(512), sh, st, A, B, g, epi);
         else if (nj == 4 && ni == 5) {
             if constexpr (can160) {
                 // (round 6) the 160 x 256 launches go to the persistent 4-wave kernel with 64-deep full-line stages (gemm_q4.hip.h) wherever K fits its
@@ -2334,34 +2270,25 @@ inline int launch_gemm(int al, int bl, const op16_t* A, int lda, const op16_t* B
                     const int tiles = ((M + 159) / 160) * ((N + 255) / 256);
                     const dim3 gq((unsigned)(tiles < ncu ? tiles : ncu));
                     if (ns == 3) {
-                        constexpr size_t shq = (size_t)3 * (160 + 256) * 128;
-                        static bool attr_ = false;
-                        if (!attr_) { (void)hipFuncSetAttribute((const void*)gemm_nt_q4_kernel<Epi, 5, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shq); attr_ = true; }
-                        hipLaunchKernelGGL((gemm_nt_q4_kernel<Epi, 5, 3>), gq, dim3(256), shq, st, A, B, g, epi);
+                        launch_dyn<gemm_nt_q4_kernel<Epi, 5, 3>>(gq, dim3(256), (size_t)3 * (160 + 256) * 128, st, A, B, g, epi);
                     } else {
-                        constexpr size_t shq = (size_t)2 * (160 + 256) * 128;
-                        static bool attr_ = false;
-                        if (!attr_) { (void)hipFuncSetAttribute((const void*)gemm_nt_q4_kernel<Epi, 5, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shq); attr_ = true; }
-                        hipLaunchKernelGGL((gemm_nt_q4_kernel<Epi, 5, 2>), gq, dim3(256), shq, st, A, B, g, epi);
+                        launch_dyn<gemm_nt_q4_kernel<Epi, 5, 2>>(gq, dim3(256), (size_t)2 * (160 + 256) * 128, st, A, B, g, epi);
                     }
-                } else CC_LAUNCH_STAG(4, 5)
+                } else launch_dyn<gemm_nt_stag256_kernel<Epi, 4, false, 5>>(gr, dim3(512), sh, st, A, B, g, epi);
             }
         }
-        else if (nj == 4) CC_LAUNCH_STAG(4, 10)
+        else if (nj == 4) launch_dyn<gemm_nt_stag256_kernel<Epi, 4, false, 10>>(gr, dim3(512), sh, st, A, B, g, epi);
         else if constexpr (!epi_row_strip<Epi>::value) {
             bool fused = false;
             if constexpr (kX3) {       // bf16x3 build: every NT launch carries operand images over K' = 3 K — the fused two-stage form (gemm_stag256_body, X3F)
                 const bool x3f_on = x3_fused_on();
                 if (x3f_on && (K % (3 * H_BK)) == 0 && ksplit <= K / (3 * H_BK)) {     // (K slices: ranges of the logical K's chunks, every slice non-empty)
-                    static bool attr_ = false;
-                    if (!attr_) { (void)hipFuncSetAttribute((const void*)gemm_nt_stag256_kernel<Epi, 3, false, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); attr_ = true; }
-                    hipLaunchKernelGGL((gemm_nt_stag256_kernel<Epi, 3, false, 8, true>), gr, dim3(512), sh, st, A, B, g, epi);
+                    launch_dyn<gemm_nt_stag256_kernel<Epi, 3, false, 8, true>>(gr, dim3(512), sh, st, A, B, g, epi);
                     fused = true;
                 }
             }
-            if (!fused) CC_LAUNCH_STAG(3, 8)
+            if (!fused) launch_dyn<gemm_nt_stag256_kernel<Epi, 3, false, 8>>(gr, dim3(512), sh, st, A, B, g, epi);
         }
-#undef CC_LAUNCH_STAG
     } else
 #ifdef CC_GEMM_ABLATION
     static const int abl = []() { const char* e = cc_lab_env("CC_GEMM_ABL"); return e ? atoi(e) : 0; }();
@@ -2375,25 +2302,17 @@ inline int launch_gemm(int al, int bl, const op16_t* A, int lda, const op16_t* B
     if (al == 0 && bl == 0 && (K % G_BK) == 0 && (long)grid.x * grid.z <= 256 && g_gemm_tile_mode != 0 && K / (int)grid.z >= 4 * G_BK) {
         // at most one block per CU: nothing co-resident to hide the 2-stage kernel's per-K-step round trip -> 4-stage variant
         constexpr size_t sh4 = (size_t)8 * G_TILE_BYTES;
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute((const void*)gemm_nt_glds4_kernel<Epi>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh4);
-            (void)hipFuncSetAttribute((const void*)gemm_nt_glds4x2_kernel<Epi>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh4);
-            attr = true;
-        }
         bool fused = false;
         if constexpr (kX3) {
             const bool x3f_on = x3_fused_on();
             if (g_gemm_small_x2 && x3f_on && ksplit == 1 && (K % (3 * G_BK)) == 0) {
-                static bool attr2 = false;
-                if (!attr2) { (void)hipFuncSetAttribute((const void*)gemm_nt_glds4x2_x3f_kernel<Epi>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh4); attr2 = true; }
-                hipLaunchKernelGGL((gemm_nt_glds4x2_x3f_kernel<Epi>), grid, dim3(2 * G_THREADS), sh4, st, A, B, g, epi);
+                launch_dyn<gemm_nt_glds4x2_x3f_kernel<Epi>>(grid, dim3(2 * G_THREADS), sh4, st, A, B, g, epi);
                 fused = true;
             }
         }
         if (fused) {}
-        else if (g_gemm_small_x2) hipLaunchKernelGGL((gemm_nt_glds4x2_kernel<Epi>), grid, dim3(2 * G_THREADS), sh4, st, A, B, g, epi);
-        else hipLaunchKernelGGL((gemm_nt_glds4_kernel<Epi>), grid, dim3(G_THREADS), sh4, st, A, B, g, epi);
+        else if (g_gemm_small_x2) launch_dyn<gemm_nt_glds4x2_kernel<Epi>>(grid, dim3(2 * G_THREADS), sh4, st, A, B, g, epi);
+        else launch_dyn<gemm_nt_glds4_kernel<Epi>>(grid, dim3(G_THREADS), sh4, st, A, B, g, epi);
     } else if (al == 0 && bl == 0 && (K % G_BK) == 0) {
         bool fused = false;
         if constexpr (kX3) {       // bf16x3 build: operand images over K' = 3 K -> the fused two-stage form
@@ -2433,36 +2352,25 @@ inline int launch_gemm_s64(const op16_t* A, int lda, const op16_t* B, int ldb, i
     g.k_chunk = per * G_BK;
     if (ks_eff) *ks_eff = ksplit;
     const int tm = (M + 63) / 64;
-#define S64_LAUNCH(NJ_, NS_, KG_)                                                                                        \
-    {                                                                                                                    \
-        constexpr size_t sh = (size_t)(NS_) * (64 + 64 * (NJ_)) * 128;                                                   \
-        static bool attr = false;                                                                                        \
-        if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_nt_s64_kernel<Epi, NJ_, NS_, KG_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); attr = true; } \
-        hipLaunchKernelGGL((gemm_nt_s64_kernel<Epi, NJ_, NS_, KG_>), dim3((unsigned)(tm * ((N + 64 * (NJ_) - 1) / (64 * (NJ_)))), 1, (unsigned)ksplit), \
-                           dim3(G_THREADS * (KG_)), sh, st, A, B, g, epi);                                               \
-    }
 #ifdef CC_EXPERIMENTS
     if (nj == 3 && Bimg && (N % 64) == 0 && ((uintptr_t)Bimg & 15) == 0) {      // ... with the weight operand global -> VGPR from its fragment-ordered image
         constexpr size_t sh = (size_t)4 * 128 * 128;      // (the epilogue's partial tiles need the 64 KiB)
-        static bool attr = false;
-        if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_nt_s64kwb_kernel<Epi, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); attr = true; }
-        hipLaunchKernelGGL((gemm_nt_s64kwb_kernel<Epi, 4>), dim3((unsigned)(tm * (N / 64)), 1, (unsigned)ksplit), dim3(320), sh, st, A, Bimg, g, epi);
+        launch_dyn<gemm_nt_s64kwb_kernel<Epi, 4>>(dim3((unsigned)(tm * (N / 64)), 1, (unsigned)ksplit), dim3(320), sh, st, A, Bimg, g, epi);
     } else
 #else
     (void)Bimg;
 #endif
     if (nj == 4) {                   // 80 x 64 tiles, K split over the waves (gemm_nt_s80kw_kernel)
         constexpr size_t sh = (size_t)4 * 6 * 16 * 64 * sizeof(float);      // the epilogue's partial tiles: 96 KiB (the four 20-KiB stages fit inside)
-        static bool attr = false;
-        if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_nt_s80kw_kernel<Epi>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); attr = true; }
-        hipLaunchKernelGGL((gemm_nt_s80kw_kernel<Epi>), dim3((unsigned)(((M + 79) / 80) * ((N + 63) / 64)), 1, (unsigned)ksplit), dim3(G_THREADS), sh, st, A, B, g, epi);
+        launch_dyn<gemm_nt_s80kw_kernel<Epi>>(dim3((unsigned)(((M + 79) / 80) * ((N + 63) / 64)), 1, (unsigned)ksplit), dim3(G_THREADS), sh, st, A, B, g, epi);
     } else if (nj == 3) {                   // K split over the waves (gemm_nt_s64kw_kernel)
         constexpr size_t sh = (size_t)4 * 128 * 128;
-        static bool attr = false;
-        if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_nt_s64kw_kernel<Epi>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); attr = true; }
-        hipLaunchKernelGGL((gemm_nt_s64kw_kernel<Epi>), dim3((unsigned)(tm * ((N + 63) / 64)), 1, (unsigned)ksplit), dim3(G_THREADS), sh, st, A, B, g, epi);
-    } else if (nj == 2) S64_LAUNCH(2, 3, 1) else S64_LAUNCH(1, 4, 1)
-#undef S64_LAUNCH
+        launch_dyn<gemm_nt_s64kw_kernel<Epi>>(dim3((unsigned)(tm * ((N + 63) / 64)), 1, (unsigned)ksplit), dim3(G_THREADS), sh, st, A, B, g, epi);
+    } else if (nj == 2) {
+        launch_dyn<gemm_nt_s64_kernel<Epi, 2, 3, 1>>(dim3((unsigned)(tm * ((N + 127) / 128)), 1, (unsigned)ksplit), dim3(G_THREADS), (size_t)3 * (64 + 128) * 128, st, A, B, g, epi);
+    } else {
+        launch_dyn<gemm_nt_s64_kernel<Epi, 1, 4, 1>>(dim3((unsigned)(tm * ((N + 63) / 64)), 1, (unsigned)ksplit), dim3(G_THREADS), (size_t)4 * (64 + 64) * 128, st, A, B, g, epi);
+    }
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 
@@ -2484,10 +2392,8 @@ inline int launch_gemm_tt256(const op16_t* A, int lda, const op16_t* B, int ldb,
     g.k_chunk = per * G_BK;
     if (ks_eff) *ks_eff = ksplit;
     constexpr size_t sh = (size_t)H_NS * H_STAGE;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_nt_stag256_kernel<Epi, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); attr = true; }
     const dim3 gr((unsigned)(((M + H_BM - 1) / H_BM) * ((N + H_BN - 1) / H_BN)), 1, (unsigned)ksplit);
-    hipLaunchKernelGGL((gemm_nt_stag256_kernel<Epi, 4, true>), gr, dim3(512), sh, st, A, B, g, epi);
+    launch_dyn<gemm_nt_stag256_kernel<Epi, 4, true>>(gr, dim3(512), sh, st, A, B, g, epi);
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 
@@ -2598,18 +2504,14 @@ static __global__ __launch_bounds__(256) void gemm_tt_tail_reduce_kernel(TTGroup
 }
 inline int launch_gemm_tt256_group(const TTGroup& grp, hipStream_t st) {
     constexpr size_t sh = (size_t)H_NS * H_STAGE;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_tt_stag256_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); attr = true; }
     const unsigned blocks = grp.whole >= 0 ? (unsigned)(grp.whole + (grp.first[grp.n] - grp.whole) * grp.split) : (unsigned)grp.first[grp.n];
-    hipLaunchKernelGGL(gemm_tt_stag256_group_kernel, dim3(blocks), dim3(512), sh, st, grp);
+    launch_dyn<gemm_tt_stag256_group_kernel>(dim3(blocks), dim3(512), sh, st, grp);
     if (grp.whole >= 0) hipLaunchKernelGGL(gemm_tt_tail_reduce_kernel, dim3((unsigned)(grp.first[grp.n] - grp.whole) * 16), dim3(256), 0, st, grp);
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 inline int launch_gemm_tt128_group(const TTGroup& grp, hipStream_t st) {
     const size_t sh = 4 * 2 * G_TILE_BYTES;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_tt_glds4_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); attr = true; }
-    hipLaunchKernelGGL(gemm_tt_glds4_group_kernel, dim3((unsigned)grp.first[grp.n]), dim3(G_THREADS), sh, st, grp);
+    launch_dyn<gemm_tt_glds4_group_kernel>(dim3((unsigned)grp.first[grp.n]), dim3(G_THREADS), sh, st, grp);
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 
@@ -2629,10 +2531,8 @@ inline int launch_gemm_tt128(const op16_t* A, int lda, const op16_t* B, int ldb,
     g.k_chunk = per * G_BK;
     if (ks_eff) *ks_eff = ksplit;
     constexpr size_t sh = (size_t)8 * G_TILE_BYTES;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_tt_glds4_kernel<Epi>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); attr = true; }
     const dim3 gr((unsigned)(((M + G_BM - 1) / G_BM) * ((N + G_BN - 1) / G_BN)), 1, (unsigned)ksplit);
-    hipLaunchKernelGGL((gemm_tt_glds4_kernel<Epi>), gr, dim3(G_THREADS), sh, st, A, B, g, epi);
+    launch_dyn<gemm_tt_glds4_kernel<Epi>>(gr, dim3(G_THREADS), sh, st, A, B, g, epi);
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 

@@ -3,9 +3,10 @@ the split-bf16 operand path, one wrapper call at a time through the test hooks c
 cc_gemm_wgrad_split / cc_x3_split_rows, against float64 (tests/gemm_ref.py) in all three operand builds.
 
 Reference: float64 products of the values the kernel really multiplies (the 16-bit-rounded operands; in the split-bf16 build the hi / lo
-planes of tests/gemm_ref.py's own split), then the epilogue in float64.  Every epilogue has two hand-written copies of its arithmetic
-(operator() for the 128-row and skinny kernels, pre4 / bias8 / fin for the 256-row kernels) plus compile-time specialisations; the tile
-modes below force each of them at every shape.
+planes of tests/gemm_ref.py's own split), then the epilogue in float64.  Every epilogue has two entry points (operator() for the 128-row
+and skinny kernels, pre4 / bias8 / fin for the 256-row kernels) plus compile-time specialisations: in the 16-bit-store and residual functors
+both end in one shared body (activation, copies, stores), the fp32 and activation-gradient functors still write their arithmetic once per
+entry point; the tile modes below force each entry point at every shape.
 
 Bounds (derived in tests/gemm_ref.py, none tuned): accumulation (steps * MFMA_ROUNDINGS + additions) * 2^-24 * sum |terms| with the step
 count of the kernel that ran; one 2^-24 rounding per epilogue addition; 16-bit stores u |ref| + (1 + u) * error, u = 2^-8 / 2^-11; the
