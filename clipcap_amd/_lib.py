@@ -134,6 +134,8 @@ SIGNATURES = {
     "cc_layernorm_fwd": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "cc_attention_fwd": (_I, [_I, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "cc_attention_bwd": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "cc_attention_fwd_x": (_I, [_I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _F, C.c_uint64, _I, _P]),
+    "cc_attention_bwd_x": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _F, C.c_uint64, _I, _P]),
     "cc_red_scratch_floats": (_L, []),
     "cc_layernorm_bwd": (_I, [_I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "cc_colsum_bf16": (_I, [_I, _P, _I, _I, _I, _P, _P, _P]),

@@ -1170,6 +1170,21 @@ int CC_API(cc_attention_bwd)(const uint16_t* qkv, const uint16_t* dout, const ui
                     causal != 0, reinterpret_cast<act_t*>(dqkv), S_(stream));
 }
 
+// ---- attention test hooks (tests/test_gpu_attention_ref.py): the same launchers with the call's Drop and Act handles built from arguments
+int CC_API(cc_attention_fwd_x)(const uint16_t* qkv, int32_t B, int32_t S, int32_t H, int32_t hd, int32_t causal, uint16_t* out, int32_t out_img, float* lse,
+                       float p, uint64_t seed, int32_t layer, void* stream) {
+    if (!qkv || !out || !(p >= 0.f && p < 1.f) || layer < 0 || layer > 255 || out_img < 0 || (!kX3 && out_img)) return CC_ERR_ARG;
+    return attn_fwd(reinterpret_cast<const act_t*>(qkv), B, S, H, hd, causal != 0, Act(reinterpret_cast<act_t*>(out), out_img), lse, S_(stream),
+                    make_drop(p, seed, DROP_ATTN, (unsigned)layer));
+}
+
+int CC_API(cc_attention_bwd_x)(const uint16_t* qkv, const uint16_t* dout, const uint16_t* o, const float* lse, float* delta_ws, int32_t B, int32_t S,
+                       int32_t H, int32_t hd, int32_t causal, uint16_t* dqkv, int32_t dqkv_img, float p, uint64_t seed, int32_t layer, void* stream) {
+    if (!qkv || !dout || !lse || !dqkv || !(p >= 0.f && p < 1.f) || layer < 0 || layer > 255 || dqkv_img < 0 || (!kX3 && dqkv_img)) return CC_ERR_ARG;
+    return attn_bwd(reinterpret_cast<const act_t*>(qkv), reinterpret_cast<const act_t*>(dout), reinterpret_cast<const act_t*>(o), lse, delta_ws, B, S, H, hd,
+                    causal != 0, Act(reinterpret_cast<act_t*>(dqkv), dqkv_img), S_(stream), make_drop(p, seed, DROP_ATTN, (unsigned)layer));
+}
+
 // ---- GEMM wrapper hooks (tests/test_gpu_gemm_epilogues.py): one wrapper call each on caller buffers, the call's image scratch passed in
 namespace {
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }

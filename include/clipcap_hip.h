@@ -63,7 +63,7 @@ extern "C" {
  * cc_beam_step_p; since 3: cc_decode_fwd_g, cc_decode_ws_check, cc_decode_mode, cc_grad_wire_pack, cc_grad_wire_unpack,
  * cc_sample_step_lp, cc_broadcast_bucket, cc_reduce_bucket, cc_embed_tokens_bwd, cc_embed_tokens_bwd_ws,
  * cc_embed_tokens_bwd_ws_bytes, and the GEMM wrapper test hooks cc_x3_image_bytes, cc_x3_split_rows, cc_gemm_act, cc_gemm_resid,
- * cc_gemm_dact, cc_gemm_f32, cc_gemm_wgrad_split; operand mode ADDED: CC_OP_BF16X3.  Round 6 (still 3): the default-off decode experiments
+ * cc_gemm_dact, cc_gemm_f32, cc_gemm_wgrad_split, and the attention test hooks cc_attention_fwd_x, cc_attention_bwd_x; operand mode ADDED: CC_OP_BF16X3.  Round 6 (still 3): the default-off decode experiments
  * (cc_decode_image*, cc_decode_xt_image*, cc_decode_fwd_x, cc_decode_ws_check, cc_decode_last_path) moved to include/clipcap_hip_lab.h —
  * the lab library exports them, the product library does not. */
 #define CC_ABI_VERSION 3
@@ -442,6 +442,17 @@ int cc_attention_fwd(int32_t op_dtype, const uint16_t* qkv, int32_t B, int32_t S
 /* o = forward output and delta_ws = fp32 scratch [B*H*S] select the MFMA kernels (hd 64/96/128); NULL -> LDS/VALU kernel */
 int cc_attention_bwd(int32_t op_dtype, const uint16_t* qkv, const uint16_t* dout, const uint16_t* o, const float* lse, float* delta_ws, int32_t B, int32_t S,
                      int32_t H, int32_t hd, int32_t causal, uint16_t* dqkv, void* stream);
+/* The same two launchers with attention-probability dropout and the operand-image outputs of the split-bf16 build.  Test hooks: the
+ * product path never calls them.  p = 0: no dropout; otherwise the mask stream cc_dropout_mask(seed, 1, layer, p, ...) returns, element
+ * index ((b H + h) S + i) S + j (query i, key j), kept probabilities scaled by 1 / (1 - p); p outside [0, 1) or layer outside 0..255:
+ * CC_ERR_ARG.  Dropout needs causal != 0 and a kernel that carries it (CC_ERR_SHAPE otherwise, nothing is written).  out_img / dqkv_img:
+ * 0, or (CC_OP_BF16X3 only) H hd / 3 H hd: out / dqkv receive the [hi | hi | lo] operand image of the GEMM that reads them (rows of
+ * 3 H hd / 9 H hd 16-bit elements, cc_x3_split_rows form 0 of the fp32 rows); a shape whose kernels cannot write images returns
+ * CC_ERR_STATE, any other non-zero value in that build CC_ERR_STATE, a non-zero value in the 16-bit builds CC_ERR_ARG. */
+int cc_attention_fwd_x(int32_t op_dtype, const uint16_t* qkv, int32_t B, int32_t S, int32_t H, int32_t hd, int32_t causal, uint16_t* out, int32_t out_img,
+                       float* lse, float p, uint64_t seed, int32_t layer, void* stream);
+int cc_attention_bwd_x(int32_t op_dtype, const uint16_t* qkv, const uint16_t* dout, const uint16_t* o, const float* lse, float* delta_ws, int32_t B, int32_t S,
+                       int32_t H, int32_t hd, int32_t causal, uint16_t* dqkv, int32_t dqkv_img, float p, uint64_t seed, int32_t layer, void* stream);
 /* The cross-block reductions of the backward passes, one call each (the training step reaches them only inside cc_mapper_bwd*,
  * cc_gpt2_bwd* and cc_lmhead_ce_bwd).  Test hooks: the product path never calls them.  Every gradient output is ACCUMULATED (+=).
  * red_ws = device scratch of cc_red_scratch_floats() floats for the per-block partial sums, used by this call only; a shape whose
