@@ -93,6 +93,8 @@ SIGNATURES = {
     "cc_lmhead_ce_fwd": (_I, [_GC, _GS, _P, _P, _P, _P, _P, _P]),
     "cc_lmhead_score": (_I, [_GC, _GS, _P, _P, _P, _P, _I, _P, _P, _P]),
     "cc_lmhead_ce_bwd": (_I, [_GC, _GS, _P, _P, _P, _P, _P, _P, _P]),
+    "cc_lmhead_put_x": (_I, [_GC, _GS, _P, _P, _P]),
+    "cc_lmhead_get": (_I, [_GC, _GS, _P, _I, _P, _L, _P]),
     "cc_gpt2_bwd": (_I, [_GC, _GS, _P, _P, _P, _P, _P, _P, _P]),
     "cc_decode_ws_bytes": (_L, [_GC, _I, _I]),
     "cc_decode_fwd": (_I, [_GC, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _L, _P]),

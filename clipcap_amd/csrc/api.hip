@@ -937,6 +937,36 @@ int CC_API(cc_lmhead_ce_bwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const
     return CC_OK;
 }
 
+// Test hooks around the lm_head / loss chain (tests/lm_ref.py): carve and copy, no kernels of their own.
+int CC_API(cc_lmhead_put_x)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, void* ws, const float* x, void* stream) {
+    if (!gpt2_cfg_ok(c) || !shape_ok(c, s) || !ws || !x) return CC_ERR_ARG;
+    Gpt2WS w;
+    gpt2_carve(c, s, s->T - s->L, ws, w);
+    const size_t bytes = (size_t)s->B * s->T * c->D * sizeof(float);
+    return hipMemcpyAsync(w.x[c->NL], x, bytes, hipMemcpyDeviceToDevice, S_(stream)) == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
+}
+
+int CC_API(cc_lmhead_get)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, void* ws, int32_t field, void* dst, int64_t dst_bytes, void* stream) {
+    if (!gpt2_cfg_ok(c) || !shape_ok(c, s) || !ws || !dst || field < CC_LM_LSE || field > CC_LM_DX32) return CC_ERR_ARG;
+    if (s->T - s->L < 1) return CC_ERR_SHAPE;      // no caption rows: the pass has no lm_head / loss side
+    Gpt2WS w;
+    gpt2_carve(c, s, s->T - s->L, ws, w);
+    const size_t Mc = (size_t)s->B * (s->T - s->L), M = (size_t)s->B * s->T, D = c->D;
+    const void* src = nullptr;
+    size_t bytes = 0;
+    switch (field) {
+        case CC_LM_LSE: src = w.lse_row; bytes = Mc * sizeof(float); break;
+        case CC_LM_TGT: src = (s->mode >= 1 && lm_exp_form(s)) ? w.cref : w.tgt_logit; bytes = Mc * sizeof(float); break;
+        case CC_LM_ROW_LOSS: src = w.row_loss; bytes = Mc * sizeof(float); break;
+        case CC_LM_HF: src = w.hf16; bytes = Mc * D * sizeof(act_t); break;
+        case CC_LM_DHF: src = w.dhf16; bytes = Mc * D * sizeof(act_t); break;
+        default: src = w.dx32; bytes = M * D * sizeof(float); break;
+    }
+    if (!src) return CC_ERR_STATE;      // this shape's mode does not carve the field
+    if (dst_bytes < 0 || (size_t)dst_bytes != bytes) return CC_ERR_SHAPE;
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, S_(stream)) == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
+}
+
 int CC_API(cc_gpt2_logits_bwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const float* dlogits,
                        int64_t ldl, float* dx0, float* g32, void* stream) {
     if (!gpt2_cfg_ok(c) || !shape_ok(c, s) || s->mode < 1 || s->L != 0 || !w32 || !w16 || !ws || !dlogits || ldl < c->V || (s->mode == 2 && !g32))

@@ -453,6 +453,23 @@ int cc_attention_fwd_x(int32_t op_dtype, const uint16_t* qkv, int32_t B, int32_t
                        float* lse, float p, uint64_t seed, int32_t layer, void* stream);
 int cc_attention_bwd_x(int32_t op_dtype, const uint16_t* qkv, const uint16_t* dout, const uint16_t* o, const float* lse, float* delta_ws, int32_t B, int32_t S,
                        int32_t H, int32_t hd, int32_t causal, uint16_t* dqkv, int32_t dqkv_img, float p, uint64_t seed, int32_t layer, void* stream);
+/* The lm_head / loss chain (cc_lmhead_ce_fwd, cc_lmhead_ce_bwd, cc_lmhead_score) on a caller's input, and its per-row state.  Test hooks:
+ * the product path never calls them.  Both carve the workspace of (cfg, shp) exactly as the entry points of the pass do and copy with
+ * hipMemcpyAsync on the call's stream; they launch no kernel and do not change cc_gpt2_ws_bytes.
+ * cc_lmhead_put_x: x fp32 [B*T][D] becomes the final residual stream of the pass (what cc_gpt2_fwd leaves for ln_f).
+ * cc_lmhead_get: copies one field into dst, dst_bytes = the field's exact byte count (CC_ERR_SHAPE otherwise; CC_ERR_STATE for a field
+ * the shape's mode does not carve: a mode-0 pass keeps only CC_LM_LSE, CC_LM_TGT and CC_LM_HF; CC_ERR_SHAPE also for a shape without
+ * caption rows, T == L; CC_ERR_ARG for NULL pointers or an unknown
+ * field).  Rows are the B*cap caption rows (cap = T - L), row b*cap + c = position L-1+c of sample b; "stored type" = the operand type's
+ * 16-bit element, fp32 in CC_OP_BF16X3. */
+#define CC_LM_LSE 0        /* fp32 [B*cap]: log-sum-exp of the row's logits */
+#define CC_LM_TGT 1        /* fp32 [B*cap]: the target logit the loss used (the reference shift of the exponential form, the epilogue's value otherwise) */
+#define CC_LM_ROW_LOSS 2   /* fp32 [B*cap]: lse - target logit, 0 on ignored rows */
+#define CC_LM_HF 3         /* stored type [B*cap][D]: ln_f output rows */
+#define CC_LM_DHF 4        /* stored type [B*cap][D]: gradient of the ln_f output rows (after cc_lmhead_ce_bwd) */
+#define CC_LM_DX32 5       /* fp32 [B*T][D]: gradient of the final residual stream (after cc_lmhead_ce_bwd) */
+int cc_lmhead_put_x(const cc_gpt2_cfg* cfg, const cc_gpt2_shape* shp, void* ws, const float* x, void* stream);
+int cc_lmhead_get(const cc_gpt2_cfg* cfg, const cc_gpt2_shape* shp, void* ws, int32_t field, void* dst, int64_t dst_bytes, void* stream);
 /* The cross-block reductions of the backward passes, one call each (the training step reaches them only inside cc_mapper_bwd*,
  * cc_gpt2_bwd* and cc_lmhead_ce_bwd).  Test hooks: the product path never calls them.  Every gradient output is ACCUMULATED (+=).
  * red_ws = device scratch of cc_red_scratch_floats() floats for the per-block partial sums, used by this call only; a shape whose
