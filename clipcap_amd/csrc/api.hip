@@ -1,5 +1,5 @@
 // C ABI (include/clipcap_hip.h) — orchestration of the mapper and GPT-2 training/inference passes out of the HIP
-// kernels in gemm.hip.h / kernels.hip.  No state, no allocation, no synchronisation: everything is enqueued on the
+// kernels in gemm.hip.h / kernels.hip / attention.hip.  No state, no allocation, no synchronisation: everything is enqueued on the
 // caller's stream and lives in caller-owned arenas / workspaces.
 #include "../../include/clipcap_hip.h"
 #include "gemm_api.h"

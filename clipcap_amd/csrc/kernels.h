@@ -1,4 +1,4 @@
-// Host-side launchers of the non-GEMM kernels (definitions in kernels.hip / decode.hip).  Internal to the library.
+// Host-side launchers of the non-GEMM kernels (definitions in kernels.hip / attention.hip / decode.hip).  Internal to the library.
 #pragma once
 #include <algorithm>
 #include <cmath>

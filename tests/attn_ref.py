@@ -1,9 +1,9 @@
-"""float64 reference of the attention launchers attn_fwd / attn_bwd (clipcap_amd/csrc/kernels.hip), the per-element error bounds the GPU
+"""float64 reference of the attention launchers attn_fwd / attn_bwd (clipcap_amd/csrc/attention.hip), the per-element error bounds the GPU
 test holds their kernels to (tests/test_gpu_attention_ref.py), float64 emulations of the defects those bounds must catch, and the case
 list both tests walk.  Plain torch, no GPU needed (every function runs on whatever device its tensors are on); tests/test_attn_ref.py
 pins this module itself.  It stands to attention as tests/gemm_ref.py stands to the GEMMs and reuses its constants.
 
-Definitions (kernels.hip, the comment above k_attn_bwd).  q, k, v, dO are [B][H][S][hd]; scale = hd^-1/2; keep M in {0, 1}, ks = 1/(1-p):
+Definitions (attention.hip, the comment above k_attn_bwd).  q, k, v, dO are [B][H][S][hd]; scale = hd^-1/2; keep M in {0, 1}, ks = 1/(1-p):
     s = q k^T scale (key j > query i masked when causal)    m = rowmax s    l = rowsum exp(s - m)    lse = m + log l    A = exp(s - lse)
     A_d = M A ks    out = A_d v                                   (dropout enters P V only; the row sum l does not see it)
     dA_d = dO v^T   dA = M ks dA_d   delta = rowsum(A dA) (= rowsum(dO out))   dS = A (dA - delta) scale
@@ -43,7 +43,7 @@ EXP_ULPS = 4.6
 LOG_ULPS = 9.3
 
 
-# ---- legality of the LDS-tile backward (kernels.hip: attn_bwd_lds, 160 KiB of LDS) ------------------------------------------------------
+# ---- legality of the LDS-tile backward (attention.hip: attn_bwd_lds, 160 KiB of LDS) ------------------------------------------------------
 LDS_BYTES = 160 * 1024
 
 

@@ -3,6 +3,7 @@
 
     hipcc <Makefile flags> -DCC_OP=<n> --cuda-device-only -S x.hip -o a/x.s      (once per tree)
     tools/isa_compare.py a/x.s b/x.s [more pairs: a/y.s b/y.s ...]   or   tools/isa_compare.py a/ b/   (every *.s of both directories)
+    tools/isa_compare.py a/x.s b/x.s+b/y.s      (a side may be several listings joined with '+': kernels that moved to another unit)
 
 For every kernel symbol it compares the resource figures (each .amdhsa_* directive of the kernel descriptor and each numeric field of the
 kernel's metadata record: register counts, scratch, LDS, spills) and the histogram of instruction mnemonics.  It prints one line per file
@@ -82,8 +83,16 @@ def parse(path):
     return kernels
 
 
+def parse_side(spec):
+    """one listing, or several joined with '+' whose kernel tables are merged"""
+    kernels = {}
+    for path in spec.split("+"):
+        kernels.update(parse(path))
+    return kernels
+
+
 def compare(pa, pb):
-    a, b = parse(pa), parse(pb)
+    a, b = parse_side(pa), parse_side(pb)
     bad = 0
     for k in sorted(set(a) ^ set(b)):
         print(f"  symbol only in {'first' if k in a else 'second'}: {k}")
