@@ -117,6 +117,10 @@ SIGNATURES = {
     "cc_grad_wire_unpack": (_I, [_P, _P, _L, _P]),
     "cc_grad_nonfinite": (_I, [_P, _L, _P, _P]),
     "cc_loss_scale_update": (_I, [_P, _P, _F, _F, _I, _P]),
+    "cc_grad_norm_scratch_floats": (_L, []),
+    "cc_grad_sqnorm": (_I, [_P, _L, _P, _P, _P]),
+    "cc_grad_clip_coef": (_I, [_P, _F, _F, _P, _P, _P]),
+    "cc_adamw_step_clip": (_I, [_I, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _F, _P, _P, _P, _P, _P]),
     "cc_dropout_mask": (_I, [C.c_uint64, _I, _I, _F, _L, _P, _P]),
     "cc_sample_step": (_I, [_P, _I, _I, _I, _F, _I, _F, _I, _P, _I, _I, _F, _P, _P, _P, _P]),
     "cc_sample_step_lp": (_I, [_P, _I, _I, _I, _F, _I, _F, _I, _P, _I, _I, _F, _I, _F, _P, _P, _P, _P]),

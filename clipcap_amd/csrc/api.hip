@@ -1088,6 +1088,26 @@ int CC_API(cc_adamw_step_cast)(float* p32, const float* g32, float* m, float* v,
     return adamw(p32, g32, m, v, (size_t)n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, loss_scale, found_inf, S_(stream), w16);
 }
 
+int CC_API(cc_adamw_step_clip)(float* p32, const float* g32, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                       float weight_decay, int32_t step, float grad_scale, const float* loss_scale, const float* found_inf, const float* clip,
+                       uint16_t* w16, void* stream) {
+    if (!p32 || !g32 || !m || !v || n < 0 || step < 0 || (step == 0 && !loss_scale)) return CC_ERR_ARG;
+    if (w16 && kX3) return CC_ERR_ARG;      // as cc_adamw_step_cast: no flat cast in the bf16x3 mode
+    return adamw(p32, g32, m, v, (size_t)n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, loss_scale, found_inf, S_(stream), w16, clip);
+}
+
+int64_t CC_API(cc_grad_norm_scratch_floats)(void) { return (int64_t)GRAD_NORM_BLOCKS; }
+
+int CC_API(cc_grad_sqnorm)(const float* g32, int64_t n, float* scratch, float* sumsq, void* stream) {
+    if (!g32 || !scratch || !sumsq || n < 0) return CC_ERR_ARG;
+    return grad_sqnorm(g32, (size_t)n, scratch, sumsq, S_(stream));
+}
+
+int CC_API(cc_grad_clip_coef)(const float* sumsq, float max_norm, float grad_scale, const float* loss_scale, float* clip, void* stream) {
+    if (!sumsq || !clip || !(max_norm >= 0.f)) return CC_ERR_ARG;
+    return grad_clip_coef(sumsq, max_norm, grad_scale, loss_scale, clip, S_(stream));
+}
+
 int CC_API(cc_cast_op16)(const float* src, uint16_t* dst, int64_t n, void* stream) {
     if (!src || !dst || n < 0 || kX3) return CC_ERR_ARG;
     return f32_to_bf16(src, dst, (size_t)n, S_(stream));

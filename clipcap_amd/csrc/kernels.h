@@ -109,8 +109,26 @@ int lm_dgrad_fix(act_t* dhf, const float* fac, const int* target, const op16_t* 
 int lm_scale_rows(const act_t* hf, const float* fac, act_t* out, int D, int M, hipStream_t st);
 
 int adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, float wd, int step, float gscale,
-          const float* loss_scale, const float* found_inf, hipStream_t st, op16_t* w16 = nullptr);   // w16: also store the 16-bit copy of the updated parameters
+          const float* loss_scale, const float* found_inf, hipStream_t st, op16_t* w16 = nullptr,   // w16: also store the 16-bit copy of the updated parameters
+          const float* clip = nullptr);            // clip (device, nullable): the gradient is also multiplied by clip[0] (grad_clip_coef)
 int grad_nonfinite(const float* g, size_t n, float* found_inf, hipStream_t st);
+// sumsq[0] += sum of g[i]^2, i < n (n % 4 == 0), bit for bit the same from run to run and from box to box: the grid depends on n alone.
+// scratch: GRAD_NORM_BLOCKS floats of device scratch for this call.  The order, with n4 = n / 4 float4 groups,
+// nb = min(ceil(n4 / GRAD_NORM_THREADS), GRAD_NORM_BLOCKS) blocks and S = nb * GRAD_NORM_THREADS:
+//   * group i contributes q_i = (x*x + y*y) + (z*z + w*w) of its four elements (at most 3 roundings on an element's way in);
+//   * thread T = block * GRAD_NORM_THREADS + lane visits groups T, T + S, T + 2S, ...; visit k is added to accumulator k % GRAD_NORM_ACC
+//     (each starts at 0, visits in ascending k): an accumulator takes at most ceil(ceil(n4 / S) / GRAD_NORM_ACC) additions;
+//   * thread sum = (a0 + a1) + (a2 + a3) (2 levels); wave sum = common.hip.h wave_sum (6 levels); block partial =
+//     (w0 + w1) + (w2 + w3) over its four waves (2 levels);
+//   * fold (one block): thread t adds partials [4t, 4t + 4) below nb in index order to 0 (GRAD_NORM_BLOCKS / GRAD_NORM_THREADS
+//     additions), then wave_sum (6 levels) and (w0 + w1) + (w2 + w3) (2 levels); thread 0: sumsq[0] = sumsq[0] + total (1).
+constexpr int GRAD_NORM_BLOCKS = 1024;
+constexpr int GRAD_NORM_THREADS = 256;
+constexpr int GRAD_NORM_ACC = 4;
+int grad_sqnorm(const float* g, size_t n, float* scratch, float* sumsq, hipStream_t st);
+// clip[1] = sqrt(sumsq[0]) * grad_scale / (loss_scale ? loss_scale[0] : 1), clip[0] = min(1, max_norm / (clip[1] + 1e-6)); a norm that
+// is not finite gives clip[0] = NaN; max_norm = +inf gives exactly 1.0f
+int grad_clip_coef(const float* sumsq, float max_norm, float grad_scale, const float* loss_scale, float* clip, hipStream_t st);
 
 // bf16x3 build: GEMM operand pairs (common.hip.h).  dst[r][0:3K] = form 0 (A operand): [hi | hi | lo], form 1 (B operand): [hi | lo | hi]
 // of src[r][0:K] (fp32, row stride lds); hi = bf16(x), lo = bf16(x - hi).  K % 8 == 0.

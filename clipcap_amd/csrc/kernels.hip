@@ -1303,9 +1303,11 @@ template <bool DEVSTEP>      // DEVSTEP: Adam's step number is read from the los
 __global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                float* __restrict__ v, size_t n4, float lr, float b1, float b2, float eps, float wd, float bc1,
                                                float bc2_sqrt, float gscale, const float* __restrict__ loss_scale,
-                                               const float* __restrict__ found_inf, op16_t* __restrict__ w16) {
+                                               const float* __restrict__ found_inf, op16_t* __restrict__ w16,
+                                               const float* __restrict__ clip) {
     if (found_inf && found_inf[0] != 0.f) return;
     if (loss_scale) gscale /= loss_scale[0];
+    if (clip) gscale *= clip[0];      // global-norm clip coefficient (k_grad_clip_coef); 1.0f leaves gscale's bits as they are
     if constexpr (DEVSTEP) {      // step number = 1 + the loss scaler's count of APPLIED steps (loss_scale[2]): a skipped step does not advance Adam's bias correction
         const float t = loss_scale[2] + 1.0f;
         bc1 = 1.0f - __builtin_amdgcn_exp2f(t * __log2f(b1));
@@ -1332,7 +1334,7 @@ __global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const floa
     }
 }
 int adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, float wd, int step, float gscale,
-          const float* loss_scale, const float* found_inf, hipStream_t st, op16_t* w16) {
+          const float* loss_scale, const float* found_inf, hipStream_t st, op16_t* w16, const float* clip) {
     if (n & 3) return CC_ERR_SHAPE;
     if (!n) return CC_OK;
     if (step < 1 && !loss_scale) return CC_ERR_ARG;
@@ -1340,8 +1342,8 @@ int adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, floa
     const float bc2s = sqrtf(1.0f - powf(b2, (float)std::max(step, 1)));
     const size_t n4 = n >> 2;
     const dim3 gr((int)std::min<size_t>((n4 + 255) / 256, 4096));
-    if (step < 1) hipLaunchKernelGGL(k_adamw<true>, gr, dim3(256), 0, st, p, g, m, v, n4, lr, b1, b2, eps, wd, bc1, bc2s, gscale, loss_scale, found_inf, w16);
-    else hipLaunchKernelGGL(k_adamw<false>, gr, dim3(256), 0, st, p, g, m, v, n4, lr, b1, b2, eps, wd, bc1, bc2s, gscale, loss_scale, found_inf, w16);
+    if (step < 1) hipLaunchKernelGGL(k_adamw<true>, gr, dim3(256), 0, st, p, g, m, v, n4, lr, b1, b2, eps, wd, bc1, bc2s, gscale, loss_scale, found_inf, w16, clip);
+    else hipLaunchKernelGGL(k_adamw<false>, gr, dim3(256), 0, st, p, g, m, v, n4, lr, b1, b2, eps, wd, bc1, bc2s, gscale, loss_scale, found_inf, w16, clip);
     return CC_OK;
 }
 
@@ -1382,6 +1384,66 @@ __global__ void k_loss_scale_update(float* state, float* found_inf, float growth
 }
 int loss_scale_update(float* state, float* found_inf, float growth, float backoff, int interval, hipStream_t st) {
     hipLaunchKernelGGL(k_loss_scale_update, dim3(1), dim3(64), 0, st, state, found_inf, growth, backoff, interval);
+    return CC_OK;
+}
+
+// ---- global gradient norm + clip coefficient (torch.nn.utils.clip_grad_norm_, all on the device) ----
+// sumsq[0] += sum g[i]^2 over a flat fp32 slice.  HBM-bound: 4 B read per parameter (AdamW moves 28).  Streaming-reduction shape: 16-byte
+// loads, GRAD_NORM_ACC independent accumulators per thread (that many loads in flight), DPP wave_sum, cross-wave fold through LDS, one
+// partial per block; a second, single-block launch folds the partials.  No atomics: the order is fixed by n alone (kernels.h states it).
+__device__ __forceinline__ float sq4(const float4 G) { return (G.x * G.x + G.y * G.y) + (G.z * G.z + G.w * G.w); }
+__global__ __launch_bounds__(GRAD_NORM_THREADS) void k_grad_sqnorm(const float* __restrict__ g, size_t n4, float* __restrict__ part) {
+    static_assert(GRAD_NORM_THREADS == 256 && GRAD_NORM_ACC == 4, "the fold below is written for 4 waves and 4 accumulators");
+    __shared__ float red[4];
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    const size_t S = (size_t)gridDim.x * GRAD_NORM_THREADS;
+    size_t i = (size_t)blockIdx.x * GRAD_NORM_THREADS + threadIdx.x;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    for (; i + 3 * S < n4; i += 4 * S) {      // four visits per round: the loads are independent, each feeds its own accumulator
+        const float4 G0 = g4[i], G1 = g4[i + S], G2 = g4[i + 2 * S], G3 = g4[i + 3 * S];
+        a0 += sq4(G0); a1 += sq4(G1); a2 += sq4(G2); a3 += sq4(G3);
+    }
+    if (i < n4) a0 += sq4(g4[i]);             // the last (partial) round: visit k still goes to accumulator k % 4
+    if (i + S < n4) a1 += sq4(g4[i + S]);
+    if (i + 2 * S < n4) a2 += sq4(g4[i + 2 * S]);
+    // every lane reaches the reduction (no early exit; a lane without elements brings 0): wave_sum's full-wave precondition
+    const float w = wave_sum((a0 + a1) + (a2 + a3));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+__global__ __launch_bounds__(GRAD_NORM_THREADS) void k_grad_sqnorm_fold(const float* __restrict__ part, int nb, float* __restrict__ sumsq) {
+    __shared__ float red[4];
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < GRAD_NORM_BLOCKS / GRAD_NORM_THREADS; e++) {      // thread t: its run of consecutive partials, in index order
+        const int j = threadIdx.x * (GRAD_NORM_BLOCKS / GRAD_NORM_THREADS) + e;
+        if (j < nb) s += part[j];
+    }
+    const float w = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
+    __syncthreads();
+    if (threadIdx.x == 0) sumsq[0] += (red[0] + red[1]) + (red[2] + red[3]);
+}
+int grad_sqnorm(const float* g, size_t n, float* scratch, float* sumsq, hipStream_t st) {
+    if (n & 3) return CC_ERR_SHAPE;
+    if (!n) return CC_OK;
+    const size_t n4 = n >> 2;
+    const int nb = (int)std::min<size_t>((n4 + GRAD_NORM_THREADS - 1) / GRAD_NORM_THREADS, GRAD_NORM_BLOCKS);
+    hipLaunchKernelGGL(k_grad_sqnorm, dim3(nb), dim3(GRAD_NORM_THREADS), 0, st, g, n4, scratch);
+    hipLaunchKernelGGL(k_grad_sqnorm_fold, dim3(1), dim3(GRAD_NORM_THREADS), 0, st, scratch, nb, sumsq);
+    return CC_OK;
+}
+// clip[1] = the true (unscaled) norm, clip[0] = min(1, max_norm / (norm + 1e-6)); a non-finite norm gives a NaN coefficient
+__global__ void k_grad_clip_coef(const float* sumsq, float max_norm, float grad_scale, const float* loss_scale, float* clip) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    float norm = sqrtf(sumsq[0]) * grad_scale;
+    if (loss_scale) norm /= loss_scale[0];
+    clip[1] = norm;
+    clip[0] = (norm - norm == 0.f) ? fminf(1.0f, max_norm / (norm + 1e-6f)) : __builtin_nanf("");
+}
+int grad_clip_coef(const float* sumsq, float max_norm, float grad_scale, const float* loss_scale, float* clip, hipStream_t st) {
+    hipLaunchKernelGGL(k_grad_clip_coef, dim3(1), dim3(64), 0, st, sumsq, max_norm, grad_scale, loss_scale, clip);
     return CC_OK;
 }
 

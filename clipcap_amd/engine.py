@@ -145,10 +145,35 @@ class _Arena:
             self.g32 = torch.zeros(self.n, dtype=torch.float32, device=self.device)
         return self.g32
 
+    def _adamw(self, p, g, m, v, n, w16, lr, step, betas, eps, weight_decay, grad_scale, scaler, clip) -> None:
+        """One AdamW launch over n elements; w16 None: no cast.  ``clip`` None: the entry points every step used before clipping existed."""
+        l, st = _lib.lib(), _stream(self.device)
+        step = 0 if scaler is not None else step      # with a loss scaler the step number is its device-side count of applied steps
+        ls = _p(scaler.scale) if scaler is not None else None
+        fi = _p(scaler.found_inf) if scaler is not None else None
+        if clip is not None:
+            check(l.cc_adamw_step_clip(self.op_dtype, _p(p), _p(g), _p(m), _p(v), n, lr, betas[0], betas[1], eps, weight_decay, step, grad_scale,
+                                       ls, fi, _p(clip), _p(w16), st), "cc_adamw_step_clip")
+        elif w16 is None:
+            check(l.cc_adamw_step(_p(p), _p(g), _p(m), _p(v), n, lr, betas[0], betas[1], eps, weight_decay, step, grad_scale, ls, fi, st),
+                  "cc_adamw_step")
+        else:
+            check(l.cc_adamw_step_cast(self.op_dtype, _p(p), _p(g), _p(m), _p(v), n, lr, betas[0], betas[1], eps, weight_decay, step, grad_scale,
+                                       ls, fi, _p(w16), st), "cc_adamw_step_cast")
+
+    def grad_range(self, partitioned: bool) -> Tuple[int, int]:
+        """[lo, hi) of the gradient arena whose reduced sum this rank holds: everything, or with partitioned gradients (ZeRO stage 2) the
+        slice whose moments it owns."""
+        if partitioned and self.zero is not None:
+            return self.zero[1][self.zero[0]]
+        return 0, self.n
+
     def adamw_step(self, lr: float, step: int, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, grad_scale: float = 1.0,
-                   scaler: Optional["LossScaler"] = None):
+                   scaler: Optional["LossScaler"] = None, clip: Optional[torch.Tensor] = None):
         """torch.optim.AdamW math (reference model.py:73-77) over the whole arena, refreshing the 16-bit operand copy.
-        ``scaler`` (fp16 operands): the gradients carry its loss scale, and a step whose backward overflowed is skipped on the device."""
+        ``scaler`` (fp16 operands): the gradients carry its loss scale, and a step whose backward overflowed is skipped on the device.
+        ``clip``: device float[1], the global-norm clip coefficient the gradients are also multiplied by (GradClipper.coef)."""
+        kw = (lr, step, betas, eps, weight_decay, grad_scale, scaler, clip)
         if self.zero is not None:                       # sharded optimizer state: own slice, then the owners' slices travel
             rank, ranges, gather = self.zero
             lo, hi = ranges[rank]
@@ -157,10 +182,7 @@ class _Arena:
                 self.v = torch.zeros(hi - lo, dtype=torch.float32, device=self.device)
             assert self.m.numel() == hi - lo
             if hi > lo:
-                check(_lib.lib().cc_adamw_step(_p(self.w32[lo:hi]), _p(self.grads()[lo:hi]), _p(self.m), _p(self.v), hi - lo, lr, betas[0], betas[1],
-                                               eps, weight_decay, 0 if scaler is not None else step, grad_scale,
-                                               _p(scaler.scale) if scaler is not None else None,
-                                               _p(scaler.found_inf) if scaler is not None else None, _stream(self.device)), "cc_adamw_step")
+                self._adamw(self.w32[lo:hi], self.grads()[lo:hi], self.m, self.v, hi - lo, None, *kw)
             gather(self.w32, ranges)
             self.refresh_bf16()
             return
@@ -171,17 +193,11 @@ class _Arena:
         # transposed half rebuilt.  One corner keeps the full refresh: a step that may be SKIPPED on the device (fp16 overflow) leaves
         # the cast untouched, which is only right if the cast was current before the step.
         if os.environ.get("CC_ADAMW_TWO_PASS") or self.op_dtype == OP_X3:   # A/B switch: the separate-cast form; bf16x3: operand images are per matrix
-            check(_lib.lib().cc_adamw_step(_p(self.w32), _p(self.grads()), _p(self.m), _p(self.v), self.n, lr, betas[0], betas[1], eps,
-                                           weight_decay, 0 if scaler is not None else step, grad_scale, _p(scaler.scale) if scaler is not None else None,
-                                           _p(scaler.found_inf) if scaler is not None else None, _stream(self.device)), "cc_adamw_step")
+            self._adamw(self.w32, self.grads(), self.m, self.v, self.n, None, *kw)
             self.refresh_bf16()
             return
         current = self._stamp() == self._w16_version
-        # with a loss scaler the Adam step number is the scaler's device-side count of applied steps (step = 0 asks the kernel for it)
-        check(_lib.lib().cc_adamw_step_cast(self.op_dtype, _p(self.w32), _p(self.grads()), _p(self.m), _p(self.v), self.n, lr, betas[0],
-                                            betas[1], eps, weight_decay, 0 if scaler is not None else step, grad_scale, _p(scaler.scale) if scaler is not None else None,
-                                            _p(scaler.found_inf) if scaler is not None else None, _p(self.w16), _stream(self.device)),
-              "cc_adamw_step_cast")
+        self._adamw(self.w32, self.grads(), self.m, self.v, self.n, self.w16, *kw)
         if scaler is None or current:
             check(self.sync_fn(None, _p(self.w16), _stream(self.device)), "cc_*_transpose_weights")
             self._w16_version = self._stamp()
@@ -215,6 +231,42 @@ class LossScaler:
         """After the optimizer steps of this iteration: adjust the scale and clear found_inf."""
         check(_lib.lib().cc_loss_scale_update(_p(self.state), _p(self.found_inf), self.growth, self.backoff, self.interval,
                                               _stream(self.device)), "cc_loss_scale_update")
+
+
+class GradClipper:
+    """Global gradient-norm clipping, torch.nn.utils.clip_grad_norm_ semantics (what Lightning's ``gradient_clip_val`` gives the
+    reference's trainer), kept entirely on the device: ``sumsq`` collects the squared norm of the trained arenas (cc_grad_sqnorm),
+    ``clip`` = [coefficient min(1, max_norm / (norm + 1e-6)), norm] (cc_grad_clip_coef); cc_adamw_step_clip reads the coefficient.
+    ``max_norm`` = inf reports the norm and clips nothing.  No host synchronisation anywhere."""
+
+    def __init__(self, device, max_norm: float):
+        self.device = torch.device(device)
+        self.max_norm = float(max_norm)
+        self.sumsq = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self.clip = torch.zeros(2, dtype=torch.float32, device=self.device)
+        self.scratch = torch.empty(_lib.lib().cc_grad_norm_scratch_floats(), dtype=torch.float32, device=self.device)
+
+    @property
+    def coef(self) -> torch.Tensor:
+        return self.clip[0:1]
+
+    @property
+    def norm(self) -> torch.Tensor:
+        return self.clip[1:2]
+
+    def begin(self) -> None:
+        self.sumsq.zero_()
+
+    def add(self, arena: "_Arena", lo: int = 0, hi: Optional[int] = None) -> None:
+        """sumsq += the squared norm of elements [lo, hi) of the arena's (still loss-scaled) gradients."""
+        hi = arena.n if hi is None else hi
+        if hi > lo:
+            check(_lib.lib().cc_grad_sqnorm(_p(arena.grads()[lo:hi]), hi - lo, _p(self.scratch), _p(self.sumsq), _stream(self.device)),
+                  "cc_grad_sqnorm")
+
+    def finish(self, grad_scale: float = 1.0, scaler: Optional[LossScaler] = None) -> None:
+        check(_lib.lib().cc_grad_clip_coef(_p(self.sumsq), self.max_norm, grad_scale, _p(scaler.scale) if scaler is not None else None,
+                                           _p(self.clip), _stream(self.device)), "cc_grad_clip_coef")
 
 
 class MapperEngine:
@@ -525,6 +577,16 @@ class ClipCapEngine:
         # fp16 operands: the backward pass runs under a dynamic loss scale (gradients in g32 are scale x the true ones until
         # optimizer_step divides it out); bf16 operands need none
         self.scaler: Optional[LossScaler] = None
+        # global-norm clipping (optimizer_step(max_grad_norm=...)): built on first use; last_grad_norm views its device-side norm
+        self.clipper: Optional[GradClipper] = None
+        self.last_grad_norm: Optional[torch.Tensor] = None
+
+    def _clipper(self, dev, max_norm: float) -> GradClipper:
+        if self.clipper is None or self.clipper.device != dev:
+            self.clipper = GradClipper(dev, max_norm)
+            self.last_grad_norm = self.clipper.norm
+        self.clipper.max_norm = float(max_norm)
+        return self.clipper
 
     def _scaler(self, dev) -> Optional[LossScaler]:
         if OP_FP16 not in (self.gpt2.op_dtype, self.mapper.op_dtype):
@@ -536,17 +598,30 @@ class ClipCapEngine:
     def arenas(self) -> List[_Arena]:
         return [self.mapper.arena] + ([self.gpt2.arena] if self.train_lm else [])
 
-    def optimizer_step(self, lr: float, step: int, sync_flag=None, **adamw_kw) -> None:
+    def optimizer_step(self, lr: float, step: int, sync_flag=None, max_grad_norm: Optional[float] = None, sync_norm=None, **adamw_kw) -> None:
         """AdamW over every trained arena (reference model.py:67-91).  With fp16 operands: overflow check of the scaled gradients
         (after any all-reduce), the step is skipped on the device if they overflowed, then the loss scale is adjusted.
         ``sync_flag(found_inf)``: optional in-place SUM over the ranks (ddp.GradReducer.reduce_flag) — with partitioned gradients
-        (ZeRO stage 2) a rank only sees its own slice summed, so the ranks agree on the overflow flag before anyone steps."""
+        (ZeRO stage 2) a rank only sees its own slice summed, so the ranks agree on the overflow flag before anyone steps.
+        ``max_grad_norm``: clip the gradients of all trained arenas together to this global 2-norm (clip_grad_norm_'s rule; inf: only
+        measure it) and leave the norm on the device in ``last_grad_norm``; None: the step launches exactly what it launched without
+        this option.  ``sync_norm(sumsq)``: the same in-place 1-float SUM over the ranks, given exactly when the gradients are
+        partitioned — each rank then squares only the slice it owns; with whole reduced arenas every rank computes the same bits alone."""
         sc = self.scaler
         if sc is not None:
             for a in self.arenas():
                 sc.check(a)
             if sync_flag is not None:
                 sync_flag(sc.found_inf)
+        if max_grad_norm is not None:
+            cl = self._clipper(self.arenas()[0].device, max_grad_norm)
+            cl.begin()
+            for a in self.arenas():
+                cl.add(a, *a.grad_range(sync_norm is not None))
+            if sync_norm is not None:
+                sync_norm(cl.sumsq)
+            cl.finish(adamw_kw.get("grad_scale", 1.0), sc)
+            adamw_kw = dict(adamw_kw, clip=cl.coef)
         for a in self.arenas():
             a.adamw_step(lr, step, scaler=sc, **adamw_kw)
         if sc is not None:

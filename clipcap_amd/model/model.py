@@ -99,8 +99,10 @@ class ClipCapModel(nn.Module):
         rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
         return ps + (int(torch.randint(0, 2 ** 48, (1,)).item()) ^ (rank << 50),)
 
-    def fused_step(self, batch: Tuple[torch.Tensor, torch.Tensor], lr: float, reducer=None) -> torch.Tensor:
-        """One optimizer step: zero grads -> forward+backward kernel chains -> (all-reduce) -> fused AdamW. Returns the loss."""
+    def fused_step(self, batch: Tuple[torch.Tensor, torch.Tensor], lr: float, reducer=None, max_grad_norm: Optional[float] = None) -> torch.Tensor:
+        """One optimizer step: zero grads -> forward+backward kernel chains -> (all-reduce) -> fused AdamW. Returns the loss.
+        ``max_grad_norm``: global gradient-norm clipping on the device (Lightning's gradient_clip_val; inf: only report the norm);
+        the norm of this step's gradients is then ``last_grad_norm``."""
         tokens, embeds = batch
         eng = self.engine
         eng.zero_grad()
@@ -112,8 +114,16 @@ class ClipCapModel(nn.Module):
         else:
             loss = eng.forward_backward(tokens, embeds, dropout=self._dropout())
         self._opt_step += 1
-        eng.optimizer_step(lr, self._opt_step, weight_decay=self._weight_decay(), sync_flag=(reducer.reduce_flag if reducer is not None else None))
+        # partitioned gradients (ZeRO stage 2): a rank holds the reduced sum of its own slices only, so the squared norms are summed
+        partitioned = reducer is not None and reducer.owners is not None
+        eng.optimizer_step(lr, self._opt_step, weight_decay=self._weight_decay(), sync_flag=(reducer.reduce_flag if reducer is not None else None),
+                           max_grad_norm=max_grad_norm, sync_norm=(reducer.reduce_flag if partitioned else None))
         return loss
+
+    @property
+    def last_grad_norm(self) -> Optional[torch.Tensor]:
+        """1-element device tensor: the global gradient norm of the last step taken with ``max_grad_norm`` (None before the first)."""
+        return self.engine.last_grad_norm
 
     def _weight_decay(self) -> float:
         """model.py:72-77: ``--enable-deepspeed`` swaps torch.optim.AdamW (weight_decay 0.01) for DeepSpeed's
@@ -143,11 +153,11 @@ class ClipCapModel(nn.Module):
         if reinit_optims:
             self.configure_optimizers()
 
-    def configure_optimizers(self) -> dict:
+    def configure_optimizers(self, max_grad_norm: Optional[float] = None) -> dict:
         tc = self.config.training_config
         assert tc is not None, "You must first use `set_training_config` before training."
         arenas = [self.transformer_mapper] + ([self.language_model] if self._train_lm else [])
-        optimizer = ArenaAdamW(arenas, lr=tc.optimizer_lr, weight_decay=self._weight_decay())
+        optimizer = ArenaAdamW(arenas, lr=tc.optimizer_lr, weight_decay=self._weight_decay(), max_grad_norm=max_grad_norm)
         scheduler = torch.optim.lr_scheduler.LambdaLR(optimizer, linear_warmup_decay(tc.scheduler_warmup_steps, tc.total_steps))
         return {"optimizer": optimizer, "lr_scheduler": {"scheduler": scheduler, "interval": "step", "frequency": 1}}
 

@@ -7,7 +7,7 @@
 """
 from __future__ import annotations
 
-from typing import Callable, List
+from typing import Callable, List, Optional
 
 import torch
 
@@ -21,8 +21,13 @@ def linear_warmup_decay(num_warmup_steps: int, num_training_steps: int) -> Calla
 
 
 class ArenaAdamW(torch.optim.Optimizer):
-    def __init__(self, arena_modules: List, lr: float = 2e-5, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01):
+    def __init__(self, arena_modules: List, lr: float = 2e-5, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01,
+                 max_grad_norm: Optional[float] = None):
+        """``max_grad_norm``: clip the gradients of all arenas together to this global 2-norm before the step, on the device
+        (engine.GradClipper; inf: only measure); the norm is then ``last_grad_norm`` (1-element device tensor)."""
         self.arena_modules = list(arena_modules)
+        self.max_grad_norm = max_grad_norm
+        self._clipper = None
         params = [p for m in self.arena_modules for p in m._arena_params.values()]
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._t = 0
@@ -39,8 +44,26 @@ class ArenaAdamW(torch.optim.Optimizer):
             for name, p in m._arena_params.items():     # gradients produced by autograd live outside the arena: gather them
                 if p.grad is not None and p.grad.data_ptr() != views[name].data_ptr():
                     views[name].copy_(p.grad)
-            arena.adamw_step(g["lr"], self._t, betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"])
+        clip = None
+        if self.max_grad_norm is not None:
+            from clipcap_amd.engine import GradClipper
+            dev = self.arena_modules[0].engine.arena.device
+            if self._clipper is None or self._clipper.device != dev:
+                self._clipper = GradClipper(dev, self.max_grad_norm)
+            cl = self._clipper
+            cl.max_norm = float(self.max_grad_norm)
+            cl.begin()
+            for m in self.arena_modules:
+                cl.add(m.engine.arena)
+            cl.finish()
+            clip = cl.coef
+        for m in self.arena_modules:
+            m.engine.arena.adamw_step(g["lr"], self._t, betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"], clip=clip)
         return loss
+
+    @property
+    def last_grad_norm(self) -> Optional[torch.Tensor]:
+        return self._clipper.norm if self._clipper is not None else None
 
     def zero_grad(self, set_to_none: bool = True):
         for m in self.arena_modules:

@@ -100,6 +100,12 @@ def train(args: Namespace, tokenizer=None, language_model=None, step_hook=None) 
             print(f"clipcap_amd: optimizer state sharded over {world} ranks" + (", gradients reduced onto their owners" if stage >= 2 else "")
                   + f" (--deepspeed-strategy {args.deepspeed_strategy})", flush=True)
     sched = linear_warmup_decay(args.scheduler_warmup_steps, args.total_steps)
+    # Lightning's Trainer(gradient_clip_val=...): global gradient-norm clipping (None / 0 = off; inf = only report the norm).  Not a CLI
+    # flag of the reference: a caller of train() sets it on the namespace
+    clip_val = getattr(args, "gradient_clip_val", None)
+    clip_val = float(clip_val) if clip_val else None
+    if clip_val is not None and rank == 0:
+        print(f"clipcap_amd: gradients clipped to a global norm of {clip_val:g} on the device", flush=True)
     logger = None
     if args.enable_wandb and rank == 0:
         try:
@@ -108,7 +114,7 @@ def train(args: Namespace, tokenizer=None, language_model=None, step_hook=None) 
         except ImportError:
             logger = None
     try:
-        step = _run_epochs(args, model, dataset, device, sched, reducer, saver, sharded, rank, logger, first_epoch, step, step_hook)
+        step = _run_epochs(args, model, dataset, device, sched, reducer, saver, sharded, rank, logger, first_epoch, step, step_hook, clip_val)
     finally:
         if hasattr(dataset, "close"):
             dataset.close()          # the reader's worker processes (do not leave them to interpreter exit)
@@ -118,18 +124,23 @@ def train(args: Namespace, tokenizer=None, language_model=None, step_hook=None) 
     return 0
 
 
-def _run_epochs(args, model, dataset, device, sched, reducer, saver, sharded, rank, logger, first_epoch, step, step_hook):
+def _run_epochs(args, model, dataset, device, sched, reducer, saver, sharded, rank, logger, first_epoch, step, step_hook, clip_val=None):
+    clip_kw = {} if clip_val is None else {"max_grad_norm": clip_val}
     for epoch in range(first_epoch, args.epochs):
         for batch in DevicePrefetcher(dataset, device):
-            loss = model.fused_step(batch, lr=args.optimizer_lr * sched(step), reducer=reducer)
+            loss = model.fused_step(batch, lr=args.optimizer_lr * sched(step), reducer=reducer, **clip_kw)
             step += 1
             if step_hook is not None:
                 step_hook(step, model)
             if rank == 0 and step % max(1, args.logging_frequency) == 0:
                 val = float(loss)
-                print(f"epoch {epoch} step {step}/{args.total_steps} loss {val:.4f}", flush=True)
+                record = {"loss": val}
+                if clip_val is not None:                  # read here only, where float(loss) has already synchronised
+                    record["grad_norm"] = float(model.last_grad_norm)
+                print(f"epoch {epoch} step {step}/{args.total_steps} loss {val:.4f}"
+                      + (f" grad_norm {record['grad_norm']:.4f}" if clip_val is not None else ""), flush=True)
                 if logger is not None:
-                    logger.log({"loss": val}, step=step)
+                    logger.log(record, step=step)
         # with sharded optimizer state, collecting the moments is a collective: every rank takes part, rank 0 writes
         opt = CheckpointSaver.optimizer_state(model) if sharded and epoch % saver.save_every_n_epochs == 0 else None
         if rank == 0:

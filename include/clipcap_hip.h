@@ -65,7 +65,8 @@ extern "C" {
  * cc_embed_tokens_bwd_ws_bytes, and the GEMM wrapper test hooks cc_x3_image_bytes, cc_x3_split_rows, cc_gemm_act, cc_gemm_resid,
  * cc_gemm_dact, cc_gemm_f32, cc_gemm_wgrad_split, and the attention test hooks cc_attention_fwd_x, cc_attention_bwd_x; operand mode ADDED: CC_OP_BF16X3.  Round 6 (still 3): the default-off decode experiments
  * (cc_decode_image*, cc_decode_xt_image*, cc_decode_fwd_x, cc_decode_ws_check, cc_decode_last_path) moved to include/clipcap_hip_lab.h —
- * the lab library exports them, the product library does not. */
+ * the lab library exports them, the product library does not.  ADDED since (still 3: no existing entry point changed): cc_lmhead_score,
+ * cc_grad_norm_scratch_floats, cc_grad_sqnorm, cc_grad_clip_coef, cc_adamw_step_clip. */
 #define CC_ABI_VERSION 3
 int cc_abi_version(void);
 
@@ -315,6 +316,32 @@ int cc_grad_wire_unpack(const uint16_t* wire, float* g32, int64_t n, void* strea
  *                      and state[2] += 1.  Clears *found_inf. */
 int cc_grad_nonfinite(const float* g32, int64_t n, float* found_inf, void* stream);
 int cc_loss_scale_update(float* state, float* found_inf, float growth, float backoff, int32_t interval, void* stream);
+/* Global gradient-norm clipping (torch.nn.utils.clip_grad_norm_, which Lightning's gradient_clip_val runs for the reference's trainer,
+ * clipcap/train/train.py:77-85), entirely on the device:
+ *   cc_grad_sqnorm: sumsq[0] += sum of g32[i]^2, i < n (n % 4 == 0, else CC_ERR_SHAPE and nothing is written; n == 0: no-op).  Call it
+ *                      once per gradient arena (or per owned slice, then SUM sumsq over the ranks) into a zeroed sumsq.  scratch = device
+ *                      scratch of cc_grad_norm_scratch_floats() floats, used by this call only.  No atomics: the result is the same bit for
+ *                      bit from run to run and from machine to machine.  The order — grid constants CC_GRAD_NORM_BLOCKS, _THREADS, _ACC —
+ *                      with n4 = n / 4, nb = min(ceil(n4 / THREADS), BLOCKS) blocks, S = nb * THREADS: float4 group i contributes
+ *                      (x*x + y*y) + (z*z + w*w) (<= 3 roundings per element); thread T visits groups T, T + S, T + 2S, ..., visit k
+ *                      added to its accumulator k % ACC (<= ceil(ceil(n4 / S) / ACC) additions each); (a0 + a1) + (a2 + a3) (2 levels);
+ *                      a 64-lane tree (6 levels); the block's 4 waves as (w0 + w1) + (w2 + w3) (2 levels) -> one partial per block.  A
+ *                      second launch of one block folds them: thread t adds its BLOCKS / THREADS consecutive partials in index order,
+ *                      the same 6 + 2 levels follow, and one thread does sumsq[0] = sumsq[0] + total.
+ *   cc_grad_clip_coef: clip (device float[2]): clip[1] = sqrt(sumsq[0]) * grad_scale / (loss_scale ? loss_scale[0] : 1), the norm of the
+ *                      gradient cc_adamw_step would use; clip[0] = min(1, max_norm / (clip[1] + 1e-6)).  A norm that is not finite gives
+ *                      clip[0] = NaN; max_norm = +inf gives exactly 1.0f (report the norm, clip nothing).  max_norm >= 0.
+ *   cc_adamw_step_clip: cc_adamw_step (w16 NULL) / cc_adamw_step_cast (w16 given) whose gradient is also multiplied by clip[0]
+ *                      (clip: device float[1], NULL = 1).  clip NULL or clip[0] == 1.0f: bit for bit the step without it. */
+#define CC_GRAD_NORM_BLOCKS 1024
+#define CC_GRAD_NORM_THREADS 256
+#define CC_GRAD_NORM_ACC 4
+int64_t cc_grad_norm_scratch_floats(void);
+int cc_grad_sqnorm(const float* g32, int64_t n, float* scratch, float* sumsq, void* stream);
+int cc_grad_clip_coef(const float* sumsq, float max_norm, float grad_scale, const float* loss_scale, float* clip, void* stream);
+int cc_adamw_step_clip(int32_t op_dtype, float* p32, const float* g32, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                       float eps, float weight_decay, int32_t step, float grad_scale, const float* loss_scale, const float* found_inf,
+                       const float* clip, uint16_t* w16 /* nullable: no cast */, void* stream);
 
 /* test hook for the dropout of cc_gpt2_shape: keep flags of one mask stream — site 0 embd [B*T*D], 1 attention [B*H*T*T],
  * 2 residual after attn.c_proj [B*T*D], 3 residual after mlp.c_proj [B*T*D]. */
