@@ -5,20 +5,12 @@
 #include "gemm_api.h"
 #include "kernels.h"
 #include "shared.h"
+#include "layout.h"
+#include <vector>
 
 using namespace CC_NS;
 
-#define CC_TRY(expr)                 \
-    do {                             \
-        int _e = (expr);             \
-        if (_e != CC_OK) return _e;  \
-    } while (0)
-
-#include <vector>
-
 namespace {
-
-constexpr int MAX_LAYERS = 96;
 
 #define CC_TIMED(site, st, expr)                 \
     do {                                         \
@@ -41,30 +33,6 @@ inline int env_tile(const char* name) {
     return e ? atoi(e) : -2;
 }
 
-struct Carver {
-    char* base;
-    size_t off = 0;
-    explicit Carver(void* p) : base(static_cast<char*>(p)) {}
-    template <class T>
-    T* take(size_t n) {
-        off = (off + 255) & ~size_t(255);
-        T* r = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += n * sizeof(T);
-        return r;
-    }
-};
-
-inline hipStream_t S_(void* s) { return static_cast<hipStream_t>(s); }
-inline int rup(int x, int m) { return (x + m - 1) / m * m; }
-
-// Operand arena addressing.  16-bit builds: w16[off] is the cast of w32[off], w16[total + off] the transposed copy.  bf16x3 build: every
-// 2-D GEMM weight [R][C] at element offset off owns 3*R*C operand elements at 3*off — rows [hi | lo | hi] of 3C (the B-operand image,
-// common.hip.h) — and its transposed image [C][3R] at 3*(total + off); the arena has 6*total elements (1-D tensors leave holes).
-constexpr int PL = kX3 ? 3 : 1;
-inline const uint16_t* W16(const uint16_t* w16, int64_t off) { return w16 + (size_t)PL * off; }
-inline uint16_t* W16(uint16_t* w16, int64_t off) { return w16 + (size_t)PL * off; }
-// bf16x3: bytes of operand-image scratch for GEMMs whose largest A image is rows x depth (x3_operand rounds each image up to 256 B)
-inline size_t x3_img(size_t rows, size_t depth) { return ((rows * 3 * depth * sizeof(op16_t)) + 255) & ~size_t(255); }
 // the Call of an entry point: its stream and the scratch of its carved workspace (MapperWS / Gpt2WS)
 template <class WS>
 inline Call call_of(hipStream_t st, const WS& w) { return Call{st, w.red, w.x3, w.x3_bytes}; }
@@ -72,44 +40,6 @@ inline Call call_of(hipStream_t st, const WS& w) { return Call{st, w.red, w.x3, 
 // ------------------------------------------------------------------------------------------------------------
 // mapper
 // ------------------------------------------------------------------------------------------------------------
-struct MapperOff {
-    int64_t lin_w, lin_b, prefix, pos;
-    struct Layer {
-        int64_t n1w, n1b, wq, wkv, wp, bp, n2w, n2b, w1, b1, w2, b2;
-    } layer[MAX_LAYERS];
-    int64_t total;
-};
-
-bool mapper_cfg_ok(const cc_mapper_cfg* c) {
-    return c && (c->op_dtype == CC_OP) && c->E > 0 && c->D > 0 && c->P > 0 && c->L > 0 && c->H > 0 && c->N >= 0 && c->N <= MAX_LAYERS && c->Hm > 0 && c->W >= 1 &&
-           (c->E % 8) == 0 && (c->D % 8) == 0 && (c->Hm % 8) == 0 && (c->D % c->H) == 0 && ((c->D / c->H) % 8) == 0;
-}
-
-void mapper_offsets(const cc_mapper_cfg* c, MapperOff& o) {
-    int64_t p = 0;
-    const int64_t D = c->D, E = c->E, PD = (int64_t)c->P * D, Hm = c->Hm;
-    o.lin_w = p; p += PD * E;
-    o.lin_b = p; p += PD;
-    o.prefix = p; p += (int64_t)c->L * D;
-    if (c->W > 1 && c->use_pos) { o.pos = p; p += (int64_t)c->W * PD; } else o.pos = -1;
-    for (int l = 0; l < c->N; l++) {
-        auto& y = o.layer[l];
-        y.n1w = p; p += D;
-        y.n1b = p; p += D;
-        y.wq = p; p += D * D;
-        y.wkv = p; p += 2 * D * D;
-        y.wp = p; p += D * D;
-        y.bp = p; p += D;
-        y.n2w = p; p += D;
-        y.n2b = p; p += D;
-        y.w1 = p; p += Hm * D;
-        y.b1 = p; p += Hm;
-        y.w2 = p; p += D * Hm;
-        y.b2 = p; p += D;
-    }
-    o.total = p;
-}
-
 constexpr int kDeferRows = 40960;      // cc_mapper_bwd_range defers the weight gradients of a call up to this many rows (and 8 layers)
 struct MapperWS {
     act_t* emb16;
@@ -147,24 +77,18 @@ void mapper_carve(const cc_mapper_cfg* c, int B, int save, void* ws, MapperWS& w
     for (int l = 0; l <= c->N; l++) w.x[l] = save ? xb[l] : xb[l & 1];
     const int nl = save ? c->N : 1;
     for (int l = 0; l < c->N; l++) {
-        const bool fresh = l < nl;
-        const int s = fresh ? l : 0;
-        if (fresh) {
-            w.x1[l] = cv.take<float>(M * D);
-            w.xn1[l] = cv.take<act_t>(M * D);
-            w.xn2[l] = cv.take<act_t>(M * D);
-            w.qkv[l] = cv.take<act_t>(M * 3 * D);
-            w.att[l] = cv.take<act_t>(M * D);
-            w.h[l] = cv.take<act_t>(M * c->Hm);
-            w.lse[l] = cv.take<float>((size_t)B * c->H * S);
-            w.mean1[l] = cv.take<float>(M);
-            w.rstd1[l] = cv.take<float>(M);
-            w.mean2[l] = cv.take<float>(M);
-            w.rstd2[l] = cv.take<float>(M);
-        } else {
-            w.x1[l] = w.x1[s]; w.xn1[l] = w.xn1[s]; w.xn2[l] = w.xn2[s]; w.qkv[l] = w.qkv[s]; w.att[l] = w.att[s]; w.h[l] = w.h[s];
-            w.lse[l] = w.lse[s]; w.mean1[l] = w.mean1[s]; w.rstd1[l] = w.rstd1[s]; w.mean2[l] = w.mean2[s]; w.rstd2[l] = w.rstd2[s];
-        }
+        const bool fresh = l < nl;      // (a pass that saves nothing reuses layer 0's buffers)
+        w.x1[l] = fresh ? cv.take<float>(M * D) : w.x1[0];
+        w.xn1[l] = fresh ? cv.take<act_t>(M * D) : w.xn1[0];
+        w.xn2[l] = fresh ? cv.take<act_t>(M * D) : w.xn2[0];
+        w.qkv[l] = fresh ? cv.take<act_t>(M * 3 * D) : w.qkv[0];
+        w.att[l] = fresh ? cv.take<act_t>(M * D) : w.att[0];
+        w.h[l] = fresh ? cv.take<act_t>(M * c->Hm) : w.h[0];
+        w.lse[l] = fresh ? cv.take<float>((size_t)B * c->H * S) : w.lse[0];
+        w.mean1[l] = fresh ? cv.take<float>(M) : w.mean1[0];
+        w.rstd1[l] = fresh ? cv.take<float>(M) : w.rstd1[0];
+        w.mean2[l] = fresh ? cv.take<float>(M) : w.mean2[0];
+        w.rstd2[l] = fresh ? cv.take<float>(M) : w.rstd2[0];
     }
     if (save) {
         w.dx32 = cv.take<float>(M * D);
@@ -211,50 +135,27 @@ void mapper_carve(const cc_mapper_cfg* c, int B, int save, void* ws, MapperWS& w
         w.x3_bytes = need;
         w.x3 = cv.take<char>(need);
     }
-    w.bytes = (cv.off + 255) & ~size_t(255);
+    w.bytes = cv.bytes();
 }
+
+// What every mapper pass starts from, built from the entry point's (already validated) arguments: the stream, the arena offsets, the carved
+// workspace, the Call and the derived dims.  A plain record on the entry point's stack: no state beyond the call, no allocation, no HIP call.
+struct MapperPass {
+    hipStream_t st;
+    MapperOff o;
+    MapperWS w;
+    Call cx;
+    int D, PP, S, M, H, hd, Hm, PD;      // PP = W*P projected prefix rows, S = rows per sample, M = B*S rows, PD = P*D
+    MapperPass(const cc_mapper_cfg* c, int B, int save, void* ws, void* stream)
+        : st(S_(stream)), o(c), D(c->D), PP(c->W * c->P), S(PP + c->L), M(B * S), H(c->H), hd(c->D / c->H), Hm(c->Hm), PD(c->P * c->D) {
+        mapper_carve(c, B, save, ws, w);
+        cx = call_of(st, w);
+    }
+};
 
 // ------------------------------------------------------------------------------------------------------------
 // GPT-2
 // ------------------------------------------------------------------------------------------------------------
-struct Gpt2Off {
-    int64_t wte, wpe, lnf_w, lnf_b;
-    struct Layer {
-        int64_t l1w, l1b, aw, ab, pw, pb, l2w, l2b, fw, fb, p2w, p2b;
-    } layer[MAX_LAYERS];
-    int64_t total;
-};
-
-bool gpt2_cfg_ok(const cc_gpt2_cfg* c) {
-    return c && (c->op_dtype == CC_OP) && c->D > 0 && c->H > 0 && c->NL > 0 && c->NL <= MAX_LAYERS && c->V > 0 && c->Vp >= c->V && (c->Vp % 128) == 0 &&
-           c->NPOS > 0 && (c->D % 8) == 0 && (c->D % c->H) == 0 && ((c->D / c->H) % 8) == 0;
-}
-
-void gpt2_offsets(const cc_gpt2_cfg* c, Gpt2Off& o) {
-    int64_t p = 0;
-    const int64_t D = c->D;
-    o.wte = p; p += (int64_t)c->Vp * D;
-    o.wpe = p; p += (int64_t)c->NPOS * D;
-    for (int l = 0; l < c->NL; l++) {
-        auto& y = o.layer[l];
-        y.l1w = p; p += D;
-        y.l1b = p; p += D;
-        y.aw = p; p += D * 3 * D;
-        y.ab = p; p += 3 * D;
-        y.pw = p; p += D * D;
-        y.pb = p; p += D;
-        y.l2w = p; p += D;
-        y.l2b = p; p += D;
-        y.fw = p; p += D * 4 * D;
-        y.fb = p; p += 4 * D;
-        y.p2w = p; p += 4 * D * D;
-        y.p2b = p; p += D;
-    }
-    o.lnf_w = p; p += D;
-    o.lnf_b = p; p += D;
-    o.total = p;
-}
-
 // bf16x3, frozen LM: c_fc's forward epilogue and the gelu' input-gradient epilogue write the [hi | hi | lo] operand image of their consumer
 // GEMM directly instead of an fp32 activation that a split pass re-reads (CC_X3_IMG=0: A/B switch)
 static bool x3_img_on() {
@@ -312,6 +213,8 @@ void gpt2_carve(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, int cap, void* ws,
     const int B = s->B, T = s->T, hd = c->D / c->H;
     const size_t M = (size_t)B * T, D = c->D, Mc = (size_t)B * cap;
     const bool keep = s->mode >= 1, full = s->mode >= 2;
+    // a 16-bit buffer of n elements that may hold a 1.5x operand image instead (bf16x3, frozen LM: 6 B per element)
+    const auto take_img = [&](size_t n) { return cv.take<act_t>(n * ((kX3 && !full) ? 3 : 2) / 2); };
     // bf16x3: which buffers are operand images (width of the operand, 0 = fp32 activations).  Frozen LM: no weight gradient reads the
     // normalised rows, the attention output, the MLP hidden or d u, so LayerNorm, attention and the c_fc / gelu' epilogues write what
     // the next GEMM reads; without dropout that also holds for the 16-bit copies of the residual gradient and for d qkv.  Attention
@@ -334,10 +237,10 @@ void gpt2_carve(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, int cap, void* ws,
         w.rstd1[l] = k0 ? cv.take<float>(M) : w.rstd1[0];
         w.mean2[l] = k0 ? cv.take<float>(M) : w.mean2[0];
         w.rstd2[l] = k0 ? cv.take<float>(M) : w.rstd2[0];
-        w.xn1[l] = f0 ? Act(cv.take<act_t>(M * D * ((kX3 && !full) ? 3 : 2) / 2), xw) : w.xn1[0];       // bf16x3, frozen LM: LayerNorm writes c_attn's / c_fc's operand image
-        w.xn2[l] = f0 ? Act(cv.take<act_t>(M * D * ((kX3 && !full) ? 3 : 2) / 2), xw) : w.xn2[0];
-        w.att[l] = k0 ? Act(cv.take<act_t>(M * D * ((kX3 && !full) ? 3 : 2) / 2), attw) : w.att[0];    // attention output: needed by the backward's delta = rowsum(dO*O) (bf16x3, frozen LM: attn.c_proj's operand image)
-        w.hact[l] = f0 ? Act(cv.take<act_t>(M * 4 * D * ((kX3 && !full) ? 3 : 2) / 2), hw) : w.hact[0];    // bf16x3, frozen LM: holds mlp.c_proj's operand IMAGE (6 B / element), written by c_fc's epilogue
+        w.xn1[l] = f0 ? Act(take_img(M * D), xw) : w.xn1[0];       // bf16x3, frozen LM: LayerNorm writes c_attn's / c_fc's operand image
+        w.xn2[l] = f0 ? Act(take_img(M * D), xw) : w.xn2[0];
+        w.att[l] = k0 ? Act(take_img(M * D), attw) : w.att[0];    // attention output: needed by the backward's delta = rowsum(dO*O) (bf16x3, frozen LM: attn.c_proj's operand image)
+        w.hact[l] = f0 ? Act(take_img(M * 4 * D), hw) : w.hact[0];    // bf16x3, frozen LM: holds mlp.c_proj's operand IMAGE (6 B / element), written by c_fc's epilogue
     }
     const size_t Mh = std::max(M, Mc);
     w.hf16 = cv.take<act_t>(Mh * D);
@@ -348,7 +251,7 @@ void gpt2_carve(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, int cap, void* ws,
     w.keep = nullptr;
     if (keep) {
         const int npart = c->Vp / 64;
-        w.logits16 = cv.take<act_t>(Mc * c->Vp * ((kX3 && !full) ? 3 : 2) / 2);               // bf16x3, frozen LM: room for E as an operand image (lm_logits)
+        w.logits16 = take_img(Mc * c->Vp);               // bf16x3, frozen LM: room for E as an operand image (lm_logits)
         w.pmax = cv.take<float>(Mc * npart);
         w.psum = cv.take<float>(Mc * npart);
         w.tgt_logit = cv.take<float>(Mc);
@@ -358,13 +261,13 @@ void gpt2_carve(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, int cap, void* ws,
         w.lmfac = cv.take<float>(2 * Mc);
         w.hfs16 = full ? cv.take<act_t>(Mc * D) : nullptr;
         w.dx32 = cv.take<float>(M * D);
-        w.dx16 = Act(cv.take<act_t>(M * D * ((kX3 && !full) ? 3 : 2) / 2), dxw);                  // bf16x3, frozen LM: operand images written by their producers (LayerNorm backward, attention backward)
+        w.dx16 = Act(take_img(M * D), dxw);                  // bf16x3, frozen LM: operand images written by their producers (LayerNorm backward, attention backward)
         w.dx16b = full ? Act(cv.take<act_t>(M * D)) : w.dx16;    // full finetune: second copy so a layer's weight gradients can run grouped
         w.dhf16 = cv.take<act_t>(Mc * D);
-        w.du16 = Act(cv.take<act_t>(M * 4 * D * ((kX3 && !full) ? 3 : 2) / 2), hw);              // likewise: c_fc's input-gradient operand image, written by the gelu' epilogue
+        w.du16 = Act(take_img(M * 4 * D), hw);              // likewise: c_fc's input-gradient operand image, written by the gelu' epilogue
         w.dxn16 = cv.take<act_t>(M * D);
         w.datt16 = cv.take<act_t>(M * D);
-        w.dqkv16 = Act(cv.take<act_t>(M * 3 * D * ((kX3 && !full) ? 3 : 2) / 2), dqw);
+        w.dqkv16 = Act(take_img(M * 3 * D), dqw);
         w.wg_scratch = full ? cv.take<float>(WGRAD_SCRATCH_BYTES / sizeof(float)) : nullptr;
         w.red = full ? cv.take<float>(RED_SCRATCH_FLOATS) : nullptr;      // only a full finetune reduces parameter gradients across blocks
         w.scat = full ? cv.take<char>(scatter_ws_bytes((int)Mc, (int)D)) : nullptr;
@@ -391,8 +294,22 @@ void gpt2_carve(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, int cap, void* ws,
         w.x3_bytes = need;
         w.x3 = cv.take<char>(need);
     }
-    w.bytes = (cv.off + 255) & ~size_t(255);
+    w.bytes = cv.bytes();
 }
+
+// The GPT-2 counterpart of MapperPass.  cap: caption rows per sample the loss side is carved for (gpt2_carve).  M = B*T rows.
+struct Gpt2Pass {
+    hipStream_t st;
+    Gpt2Off o;
+    Gpt2WS w;
+    Call cx;
+    int D, M, H, hd;
+    Gpt2Pass(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, int cap, void* ws, void* stream)
+        : st(S_(stream)), o(c), D(c->D), M(s->B * s->T), H(c->H), hd(c->D / c->H) {
+        gpt2_carve(c, s, cap, ws, w);
+        cx = call_of(st, w);
+    }
+};
 
 }  // namespace
 
@@ -406,22 +323,14 @@ int CC_API(cc_gpt2_bwd_range)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, cons
 // ---------------------------------------------------------------- mapper ----------------------------------------
 int64_t CC_API(cc_mapper_param_count)(const cc_mapper_cfg* cfg) {
     if (!mapper_cfg_ok(cfg)) return CC_ERR_SHAPE;
-    MapperOff o;
-    mapper_offsets(cfg, o);
-    return o.total;
+    return MapperOff(cfg).total;
 }
 
 int CC_API(cc_mapper_param_offsets)(const cc_mapper_cfg* cfg, int64_t* offs) {
     if (!mapper_cfg_ok(cfg) || !offs) return CC_ERR_SHAPE;
-    MapperOff o;
-    mapper_offsets(cfg, o);
-    int k = 0;
-    offs[k++] = o.lin_w; offs[k++] = o.lin_b; offs[k++] = o.prefix; offs[k++] = o.pos;
-    for (int l = 0; l < cfg->N; l++) {
-        const auto& y = o.layer[l];
-        const int64_t v[12] = {y.n1w, y.n1b, y.wq, y.wkv, y.wp, y.bp, y.n2w, y.n2b, y.w1, y.b1, y.w2, y.b2};
-        for (int i = 0; i < 12; i++) offs[k++] = v[i];
-    }
+    const MapperOff o(cfg);
+    *offs++ = o.lin_w; *offs++ = o.lin_b; *offs++ = o.prefix; *offs++ = o.pos;
+    for (int l = 0; l < cfg->N; l++) offs = put_layer(offs, o.layer(l));
     return CC_OK;
 }
 
@@ -435,13 +344,12 @@ int64_t CC_API(cc_mapper_ws_bytes)(const cc_mapper_cfg* cfg, int32_t B, int32_t 
 #if CC_OP == 2
 // bf16x3: [hi | lo | hi] images of every GEMM weight and of its transpose, straight from the fp32 master (W16 layout above)
 static int mapper_sync_x3(const cc_mapper_cfg* c, const float* w32, uint16_t* w16, hipStream_t st) {
-    MapperOff o;
-    mapper_offsets(c, o);
+    const MapperOff o(c);
     const int D = c->D, Hm = c->Hm;
     X3SplitBatch sb;
     sb.add(w32 + o.lin_w, W16(w16, o.lin_w), c->P * D, c->E, 0, 1);
     for (int l = 0; l < c->N; l++) {
-        const auto& y = o.layer[l];
+        const auto y = o.layer(l);
         const int64_t off[4] = {y.wq, y.wp, y.w1, y.w2};
         const int R[4] = {3 * D, D, Hm, D}, C[4] = {D, D, D, Hm};
         for (int i = 0; i < 4; i++) {
@@ -456,13 +364,12 @@ static int mapper_sync_x3(const cc_mapper_cfg* c, const float* w32, uint16_t* w1
 
 static int mapper_transposes(const cc_mapper_cfg* c, uint16_t* w16, hipStream_t st) {
     if (kX3) return CC_ERR_ARG;      // the operand images are made from the fp32 master (cc_mapper_sync_weights)
-    MapperOff o;
-    mapper_offsets(c, o);
+    const MapperOff o(c);
     op16_t* t = w16 + o.total;
     const int D = c->D, Hm = c->Hm;
     TransposeBatch tb;                      // 8 layers x 4 matrices: one launch per 32 matrices instead of one each
     for (int l = 0; l < c->N; l++) {
-        const auto& y = o.layer[l];
+        const auto y = o.layer(l);
         tb.add(w16 + y.wq, t + y.wq, 3 * D, D);   // fused [3D, D] -> [D, 3D]
         tb.add(w16 + y.wp, t + y.wp, D, D);
         tb.add(w16 + y.w1, t + y.w1, Hm, D);       // [Hm, D] -> [D, Hm]
@@ -479,9 +386,7 @@ int CC_API(cc_mapper_sync_weights)(const cc_mapper_cfg* c, const float* w32, uin
 #if CC_OP == 2
     return mapper_sync_x3(c, w32, w16, st);
 #else
-    MapperOff o;
-    mapper_offsets(c, o);
-    CC_TRY(f32_to_bf16(w32, w16, (size_t)o.total, st));
+    CC_TRY(f32_to_bf16(w32, w16, (size_t)MapperOff(c).total, st));
     return mapper_transposes(c, w16, st);
 #endif
 }
@@ -494,14 +399,8 @@ int CC_API(cc_mapper_transpose_weights)(const cc_mapper_cfg* c, uint16_t* w16, v
 int CC_API(cc_mapper_fwd)(const cc_mapper_cfg* c, int32_t B, const float* w32, const uint16_t* w16, const float* emb, void* ws, float* out,
                   int32_t save, void* stream) {
     if (!mapper_cfg_ok(c) || B <= 0 || !w32 || !w16 || !emb || !ws || !out) return CC_ERR_ARG;
-    hipStream_t st = S_(stream);
-    MapperOff o;
-    mapper_offsets(c, o);
-    MapperWS w;
-    mapper_carve(c, B, save, ws, w);
-    Call cx = call_of(st, w);
-    const int D = c->D, PP = c->W * c->P, S = PP + c->L, M = B * S, H = c->H, hd = D / H, Hm = c->Hm;
-    const int PD = c->P * D;
+    MapperPass ps(c, B, save, ws, stream);
+    auto& [st, o, w, cx, D, PP, S, M, H, hd, Hm, PD] = ps;
     // linear (mapper.py:123): [B*W, E] x [P*D, E]^T + b -> rows 0..PP-1 of every sample of x[0]
     CC_TRY(f32_to_act(emb, w.emb16, (size_t)B * c->W * c->E, st));
     if (c->W == 1) {
@@ -514,7 +413,7 @@ int CC_API(cc_mapper_fwd)(const cc_mapper_cfg* c, int32_t B, const float* w32, c
     // cat learned prefix_const (mapper.py:125-126)
     CC_TRY(broadcast_rows(w.x[0] + (size_t)PP * D, (size_t)S * D, w32 + o.prefix, c->L * D, B, st));
     for (int l = 0; l < c->N; l++) {
-        const auto& y = o.layer[l];
+        const auto y = o.layer(l);
         // x1 = x + project(attn(LN1 x))  (mapper.py:108, attention.py:17-43)
         CC_TRY(ln_fwd(w.x[l], D, nullptr, w32 + y.n1w, w32 + y.n1b, w.xn1[l], nullptr, w.mean1[l], w.rstd1[l], M, D, st));
         CC_TIMED(CC_SITE_MAPPER_QKV_FWD, st, gemm_bf16out(0, 0, w.xn1[l], D, W16(w16, y.wq), D, M, 3 * D, D, w.qkv[l], 3 * D, nullptr, 0, nullptr, cx));
@@ -532,10 +431,8 @@ int CC_API(cc_mapper_fwd)(const cc_mapper_cfg* c, int32_t B, const float* w32, c
 
 int CC_API(cc_mapper_attention_probs)(const cc_mapper_cfg* c, int32_t B, void* ws, int32_t layer, float* out, void* stream) {
     if (!mapper_cfg_ok(c) || B <= 0 || !ws || !out || layer < 0 || layer >= c->N) return CC_ERR_ARG;
-    MapperWS w;
-    mapper_carve(c, B, 1, ws, w);
-    const int S = c->W * c->P + c->L;
-    return attn_probs(w.qkv[layer], B, S, c->H, c->D / c->H, out, S_(stream));
+    MapperPass ps(c, B, 1, ws, stream);
+    return attn_probs(ps.w.qkv[layer], B, ps.S, ps.H, ps.hd, out, ps.st);
 }
 
 int CC_API(cc_mapper_bwd)(const cc_mapper_cfg* c, int32_t B, const float* w32, const uint16_t* w16, void* ws, const float* dout, float* g32,
@@ -547,14 +444,8 @@ int CC_API(cc_mapper_bwd)(const cc_mapper_cfg* c, int32_t B, const float* w32, c
 int CC_API(cc_mapper_bwd_range)(const cc_mapper_cfg* c, int32_t B, const float* w32, const uint16_t* w16, void* ws, const float* dout, float* g32,
                         int32_t l_hi, int32_t l_lo, void* stream) {
     if (!mapper_cfg_ok(c) || B <= 0 || !w32 || !w16 || !ws || !dout || !g32 || l_lo < 0 || l_hi > c->N || l_lo > l_hi) return CC_ERR_ARG;
-    hipStream_t st = S_(stream);
-    MapperOff o;
-    mapper_offsets(c, o);
-    MapperWS w;
-    mapper_carve(c, B, 1, ws, w);
-    Call cx = call_of(st, w);
-    const int D = c->D, PP = c->W * c->P, S = PP + c->L, M = B * S, H = c->H, hd = D / H, Hm = c->Hm;
-    const int PD = c->P * D;
+    MapperPass ps(c, B, 1, ws, stream);
+    auto& [st, o, w, cx, D, PP, S, M, H, hd, Hm, PD] = ps;
     const uint16_t* w16t = W16(w16, o.total);   // transposed weight copies: dgrad GEMMs are NT
     if (l_hi == c->N) {   // seed: d x[N][:, PP:, :] = dout, rows [0:PP] = 0
         if (hipMemsetAsync(w.dx32, 0, (size_t)M * D * sizeof(float), st) != hipSuccess) return CC_ERR_LAUNCH;
@@ -585,6 +476,7 @@ int CC_API(cc_mapper_bwd_range)(const cc_mapper_cfg* c, int32_t B, const float* 
     int g2rc = CC_OK;
     auto G2 = [&](const act_t* t, int width) -> ActIn {
         if (!share) return t;
+        auto& [st, o, w, cx, D, PP, S, M, H, hd, Hm, PD] = ps;      // (C++17 lambdas capture the pass, not its bindings)
         g2rc = x3_split_rows(t, (size_t)width, w.gimg, M, width, 0, st);
         return ActIn(reinterpret_cast<const act_t*>(w.gimg), width);
     };
@@ -593,7 +485,7 @@ int CC_API(cc_mapper_bwd_range)(const cc_mapper_cfg* c, int32_t B, const float* 
     const int g2rc = CC_OK;
 #endif
     for (int l = l_hi - 1; l >= l_lo; l--) {
-        const auto& y = o.layer[l];
+        const auto y = o.layer(l);
         act_t* dx16 = w.gdx[l];                                   // d x[l+1]: written by the seed / by the LN1 backward of layer l + 1
         act_t* dx16b = w.gdxb[l];
         act_t* dh16 = w.gdh[l];
@@ -633,7 +525,7 @@ int CC_API(cc_mapper_bwd_range)(const cc_mapper_cfg* c, int32_t B, const float* 
         // with the next layer's input gradient (with per-layer buffers nothing is overwritten and the flush waits for the end of the call)
         if (!defer_all) CC_TRY(wgrad_flush(wb, st));
         CC_TRY(ln_bwd(w.dxn16, w.x[l], D, nullptr, w.mean1[l], w.rstd1[l], w32 + y.n1w, w.dx32, w.dx32, dx16_below, g32 + y.n1w,
-                      g32 + y.n1b, M, D, cx, l > 0 ? g32 + o.layer[l - 1].b2 : nullptr));   // + fc2.bias gradient of the layer below
+                      g32 + y.n1b, M, D, cx, l > 0 ? g32 + o.layer(l - 1).b2 : nullptr));   // + fc2.bias gradient of the layer below
     }
     CC_TRY(wgrad_flush(wb, st));
     CC_TRY(colsum_bf16_multi(cs, Hm, M, Hm, cx));
@@ -662,23 +554,15 @@ static bool shape_ok(const cc_gpt2_cfg* c, const cc_gpt2_shape* s) {
 
 int64_t CC_API(cc_gpt2_param_count)(const cc_gpt2_cfg* cfg) {
     if (!gpt2_cfg_ok(cfg)) return CC_ERR_SHAPE;
-    Gpt2Off o;
-    gpt2_offsets(cfg, o);
-    return o.total;
+    return Gpt2Off(cfg).total;
 }
 
 int CC_API(cc_gpt2_param_offsets)(const cc_gpt2_cfg* cfg, int64_t* offs) {
     if (!gpt2_cfg_ok(cfg) || !offs) return CC_ERR_SHAPE;
-    Gpt2Off o;
-    gpt2_offsets(cfg, o);
-    int k = 0;
-    offs[k++] = o.wte; offs[k++] = o.wpe;
-    for (int l = 0; l < cfg->NL; l++) {
-        const auto& y = o.layer[l];
-        const int64_t v[12] = {y.l1w, y.l1b, y.aw, y.ab, y.pw, y.pb, y.l2w, y.l2b, y.fw, y.fb, y.p2w, y.p2b};
-        for (int i = 0; i < 12; i++) offs[k++] = v[i];
-    }
-    offs[k++] = o.lnf_w; offs[k++] = o.lnf_b;
+    const Gpt2Off o(cfg);
+    *offs++ = o.wte; *offs++ = o.wpe;
+    for (int l = 0; l < cfg->NL; l++) offs = put_layer(offs, o.layer(l));
+    *offs++ = o.lnf_w; *offs++ = o.lnf_b;
     return CC_OK;
 }
 
@@ -691,8 +575,7 @@ int64_t CC_API(cc_gpt2_ws_bytes)(const cc_gpt2_cfg* cfg, const cc_gpt2_shape* s)
 
 #if CC_OP == 2
 static int gpt2_sync_x3(const cc_gpt2_cfg* c, const float* w32, uint16_t* w16, hipStream_t st) {
-    Gpt2Off o;
-    gpt2_offsets(c, o);
+    const Gpt2Off o(c);
     const int D = c->D;
     X3SplitBatch sb;
     sb.add(w32 + o.wte, W16(w16, o.wte), c->Vp, D, 0, 1);                       // lm_head forward / logits / decode
@@ -700,7 +583,7 @@ static int gpt2_sync_x3(const cc_gpt2_cfg* c, const float* w32, uint16_t* w16, h
     CC_TRY(x3_split_multi(sb, st));
     sb.n = 0;
     for (int l = 0; l < c->NL; l++) {
-        const auto& y = o.layer[l];
+        const auto y = o.layer(l);
         const int64_t off[4] = {y.aw, y.pw, y.fw, y.p2w};
         const int R[4] = {D, D, D, 4 * D}, C[4] = {3 * D, D, 4 * D, D};          // Conv1D [in][out]
         for (int i = 0; i < 4; i++) {
@@ -715,14 +598,13 @@ static int gpt2_sync_x3(const cc_gpt2_cfg* c, const float* w32, uint16_t* w16, h
 
 static int gpt2_transposes(const cc_gpt2_cfg* c, uint16_t* w16, hipStream_t st) {
     if (kX3) return CC_ERR_ARG;      // the operand images are made from the fp32 master (cc_gpt2_sync_weights)
-    Gpt2Off o;
-    gpt2_offsets(c, o);
+    const Gpt2Off o(c);
     op16_t* t = w16 + o.total;
     const int D = c->D;
     CC_TRY(transpose_bf16(w16 + o.wte, t + o.wte, c->Vp, D, st));     // [Vp, D] -> [D, Vp]  (lm_head dgrad)
     TransposeBatch tb;
     for (int l = 0; l < c->NL; l++) {
-        const auto& y = o.layer[l];
+        const auto y = o.layer(l);
         tb.add(w16 + y.aw, t + y.aw, D, 3 * D);    // Conv1D [in,out] -> [out,in]: forward is NT on these
         tb.add(w16 + y.pw, t + y.pw, D, D);
         tb.add(w16 + y.fw, t + y.fw, D, 4 * D);
@@ -739,9 +621,7 @@ int CC_API(cc_gpt2_sync_weights)(const cc_gpt2_cfg* c, const float* w32, uint16_
 #if CC_OP == 2
     return gpt2_sync_x3(c, w32, w16, st);
 #else
-    Gpt2Off o;
-    gpt2_offsets(c, o);
-    CC_TRY(f32_to_bf16(w32, w16, (size_t)o.total, st));
+    CC_TRY(f32_to_bf16(w32, w16, (size_t)Gpt2Off(c).total, st));
     return gpt2_transposes(c, w16, st);
 #endif
 }
@@ -761,38 +641,27 @@ int CC_API(cc_dropout_mask)(uint64_t seed, int32_t site, int32_t layer, float p,
 int CC_API(cc_gpt2_embed)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const float* prefix, const int64_t* tokens, void* ws,
                   void* stream) {
     if (!gpt2_cfg_ok(c) || !shape_ok(c, s) || !w32 || !ws || (s->L > 0 && !prefix) || (s->T > s->L && !tokens)) return CC_ERR_ARG;
-    Gpt2Off o;
-    gpt2_offsets(c, o);
-    Gpt2WS w;
-    gpt2_carve(c, s, s->T - s->L, ws, w);
-    CC_TRY(embed_concat(prefix, reinterpret_cast<const long long*>(tokens), s->cap, w32 + o.wte, w32 + o.wpe, w.x[0], s->B, s->L, s->T,
-                        c->D, 0, S_(stream)));
+    Gpt2Pass ps(c, s, s->T - s->L, ws, stream);
+    auto& [st, o, w, cx, D, M, H, hd] = ps;
+    CC_TRY(embed_concat(prefix, reinterpret_cast<const long long*>(tokens), s->cap, w32 + o.wte, w32 + o.wpe, w.x[0], s->B, s->L, s->T, D, 0, st));
     // embd dropout on inputs_embeds + position_embeds (hf GPT2Model.forward: self.drop)
-    return dropout_f32(w.x[0], (size_t)s->B * s->T * c->D, make_drop(s->p_embd, s->drop_seed, DROP_EMBD, 0), S_(stream));
+    return dropout_f32(w.x[0], (size_t)s->B * s->T * D, make_drop(s->p_embd, s->drop_seed, DROP_EMBD, 0), st);
 }
 
 int CC_API(cc_gpt2_embed_from)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const float* inputs_embeds, void* ws,
                        void* stream) {
     if (!gpt2_cfg_ok(c) || !shape_ok(c, s) || !w32 || !ws || !inputs_embeds) return CC_ERR_ARG;
-    Gpt2Off o;
-    gpt2_offsets(c, o);
-    Gpt2WS w;
-    gpt2_carve(c, s, s->T - s->L, ws, w);
-    return embed_concat(inputs_embeds, nullptr, 0, w32 + o.wte, w32 + o.wpe, w.x[0], s->B, s->T, s->T, c->D, 0, S_(stream));
+    Gpt2Pass ps(c, s, s->T - s->L, ws, stream);
+    return embed_concat(inputs_embeds, nullptr, 0, w32 + ps.o.wte, w32 + ps.o.wpe, ps.w.x[0], s->B, s->T, s->T, ps.D, 0, ps.st);
 }
 
 int CC_API(cc_gpt2_fwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, void* stream) {
     if (!gpt2_cfg_ok(c) || !shape_ok(c, s) || !w32 || !w16 || !ws) return CC_ERR_ARG;
-    hipStream_t st = S_(stream);
-    Gpt2Off o;
-    gpt2_offsets(c, o);
-    Gpt2WS w;
-    gpt2_carve(c, s, s->T - s->L, ws, w);
-    Call cx = call_of(st, w);
-    const int D = c->D, M = s->B * s->T, H = c->H, hd = D / H;
+    Gpt2Pass ps(c, s, s->T - s->L, ws, stream);
+    auto& [st, o, w, cx, D, M, H, hd] = ps;
     const uint16_t* w16t = W16(w16, o.total);   // Conv1D weights transposed to [out,in]: every forward GEMM is NT
     for (int l = 0; l < c->NL; l++) {
-        const auto& y = o.layer[l];
+        const auto y = o.layer(l);
         // hf :262-310: x1 = x + c_proj(attn(c_attn(ln_1 x)))
         CC_TRY(ln_fwd(w.x[l], D, nullptr, w32 + y.l1w, w32 + y.l1b, w.xn1[l], nullptr, w.mean1[l], w.rstd1[l], M, D, st));
         CC_TRY(gemm_bf16out(0, 0, w.xn1[l], D, W16(w16t, y.aw), D, M, 3 * D, D, w.qkv[l], 3 * D, w32 + y.ab, 0, nullptr, cx));
@@ -827,13 +696,8 @@ int CC_API(cc_gpt2_logits)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const f
     if (!gpt2_cfg_ok(c) || !shape_ok(c, s) || !w32 || !w16 || !ws || !logits) return CC_ERR_ARG;
     const int Ns = std::min(c->Vp, rup(c->V, 8));
     if (ldl < Ns || (ldl & 3) || ldl > 0x7fffffff) return CC_ERR_SHAPE;
-    hipStream_t st = S_(stream);
-    Gpt2Off o;
-    gpt2_offsets(c, o);
-    Gpt2WS w;
-    gpt2_carve(c, s, s->T - s->L, ws, w);
-    Call cx = call_of(st, w);
-    const int D = c->D, M = s->B * s->T;
+    Gpt2Pass ps(c, s, s->T - s->L, ws, stream);
+    auto& [st, o, w, cx, D, M, H, hd] = ps;
     CC_TRY(ln_fwd(w.x[c->NL], D, nullptr, w32 + o.lnf_w, w32 + o.lnf_b, w.hf16, nullptr, w.meanf, w.rstdf, M, D, st));
     return gemm_f32out(0, 0, w.hf16, D, W16(w16, o.wte), D, M, Ns, D, logits, (int)ldl, nullptr, 0, 1.0f, 1, cx);
 }
@@ -841,15 +705,11 @@ int CC_API(cc_gpt2_logits)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const f
 int CC_API(cc_lmhead_ce_fwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const int64_t* tokens,
                      float* stats, void* stream) {
     if (!gpt2_cfg_ok(c) || !shape_ok(c, s) || s->mode < 1 || s->L < 1 || !w32 || !w16 || !ws || !tokens || !stats) return CC_ERR_ARG;
-    hipStream_t st = S_(stream);
-    Gpt2Off o;
-    gpt2_offsets(c, o);
-    Gpt2WS w;
     const int cap = s->T - s->L;
-    gpt2_carve(c, s, cap, ws, w);
-    Call cx = call_of(st, w);
-    const int D = c->D, Mc = s->B * cap, npart = c->Vp / 64;
     if (cap != s->cap) return CC_ERR_SHAPE;  // the loss consumes every token column (model.py:108-109)
+    Gpt2Pass ps(c, s, cap, ws, stream);
+    auto& [st, o, w, cx, D, M, H, hd] = ps;
+    const int Mc = s->B * cap, npart = c->Vp / 64;
     if (hipMemsetAsync(stats, 0, 2 * sizeof(float), st) != hipSuccess) return CC_ERR_LAUNCH;
     CC_TRY(ce_targets(reinterpret_cast<const long long*>(tokens), w.target, w.row_map, s->B, cap, s->L, s->T, st));
     // ln_f only on the rows the loss reads: L-1 .. T-2 of every sample (model.py:108)
@@ -869,13 +729,9 @@ int CC_API(cc_lmhead_score)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const 
         return CC_ERR_ARG;
     const int cap = s->T - s->L;
     if (cap < 1 || cap != s->cap) return CC_ERR_SHAPE;      // every token column is scored
-    hipStream_t st = S_(stream);
-    Gpt2Off o;
-    gpt2_offsets(c, o);
-    Gpt2WS w;
-    gpt2_carve(c, s, cap, ws, w);
-    Call cx = call_of(st, w);
-    const int D = c->D, Mc = s->B * cap, npart = c->Vp / 64;
+    Gpt2Pass ps(c, s, cap, ws, stream);
+    auto& [st, o, w, cx, D, M, H, hd] = ps;
+    const int Mc = s->B * cap, npart = c->Vp / 64;
     CC_TRY(ce_targets(reinterpret_cast<const long long*>(tokens), w.target, w.row_map, s->B, cap, s->L, s->T, st));
     CC_TRY(score_keep(reinterpret_cast<const long long*>(tokens), w.keep, Mc, ignore_zero, st));
     // ln_f only on the rows that predict a caption token: L-1 .. T-2 of every sample
@@ -887,14 +743,10 @@ int CC_API(cc_lmhead_score)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const 
 int CC_API(cc_lmhead_ce_bwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const float* denom,
                      const float* loss_scale, float* g32, void* stream) {
     if (!gpt2_cfg_ok(c) || !shape_ok(c, s) || s->mode < 1 || !w32 || !w16 || !ws || !denom || (s->mode == 2 && !g32)) return CC_ERR_ARG;
-    hipStream_t st = S_(stream);
-    Gpt2Off o;
-    gpt2_offsets(c, o);
-    Gpt2WS w;
     const int cap = s->T - s->L;
-    gpt2_carve(c, s, cap, ws, w);
-    Call cx = call_of(st, w);
-    const int D = c->D, Mc = s->B * cap, M = s->B * s->T;
+    Gpt2Pass ps(c, s, cap, ws, stream);
+    auto& [st, o, w, cx, D, M, H, hd] = ps;
+    const int Mc = s->B * cap;
     const bool full = s->mode == 2;
     // exponential form: logits16 holds E = exp(logit - cref); d logits = r E - w onehot is never written — the row factors go into the
     // GEMMs' finishing passes (EpiLMHead comment).  Otherwise: the in-place softmax-gradient pass over the stored logits.
@@ -911,6 +763,7 @@ int CC_API(cc_lmhead_ce_bwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const
     // d hf = dlogits · wte   ([Mc,Vp] x [Vp(k), D(n)])
     // K = Vp is deep and the output narrow: K slices over the idle CUs, slabs parked in du16 (free until the first layer's backward)
     const auto lm_dgrad = [&]() {
+        auto& [st, o, w, cx, D, M, H, hd] = ps;      // (C++17 lambdas capture the pass, not its bindings)
         const int rc = gemm_nt_deepk(dlog, c->Vp, W16(w16, o.total + o.wte), c->Vp, Mc, D, c->Vp, w.dhf16, D, reinterpret_cast<float*>(w.du16.p),
                                      (size_t)M * 4 * D * sizeof(act_t), cx, ef ? &fix : nullptr);
         if (rc != CC_ERR_SHAPE) return rc;
@@ -940,17 +793,16 @@ int CC_API(cc_lmhead_ce_bwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const
 // Test hooks around the lm_head / loss chain (tests/lm_ref.py): carve and copy, no kernels of their own.
 int CC_API(cc_lmhead_put_x)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, void* ws, const float* x, void* stream) {
     if (!gpt2_cfg_ok(c) || !shape_ok(c, s) || !ws || !x) return CC_ERR_ARG;
-    Gpt2WS w;
-    gpt2_carve(c, s, s->T - s->L, ws, w);
+    Gpt2Pass ps(c, s, s->T - s->L, ws, stream);
     const size_t bytes = (size_t)s->B * s->T * c->D * sizeof(float);
-    return hipMemcpyAsync(w.x[c->NL], x, bytes, hipMemcpyDeviceToDevice, S_(stream)) == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
+    return hipMemcpyAsync(ps.w.x[c->NL], x, bytes, hipMemcpyDeviceToDevice, ps.st) == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 
 int CC_API(cc_lmhead_get)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, void* ws, int32_t field, void* dst, int64_t dst_bytes, void* stream) {
     if (!gpt2_cfg_ok(c) || !shape_ok(c, s) || !ws || !dst || field < CC_LM_LSE || field > CC_LM_DX32) return CC_ERR_ARG;
     if (s->T - s->L < 1) return CC_ERR_SHAPE;      // no caption rows: the pass has no lm_head / loss side
-    Gpt2WS w;
-    gpt2_carve(c, s, s->T - s->L, ws, w);
+    Gpt2Pass ps(c, s, s->T - s->L, ws, stream);
+    const Gpt2WS& w = ps.w;
     const size_t Mc = (size_t)s->B * (s->T - s->L), M = (size_t)s->B * s->T, D = c->D;
     const void* src = nullptr;
     size_t bytes = 0;
@@ -964,20 +816,15 @@ int CC_API(cc_lmhead_get)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, void* ws
     }
     if (!src) return CC_ERR_STATE;      // this shape's mode does not carve the field
     if (dst_bytes < 0 || (size_t)dst_bytes != bytes) return CC_ERR_SHAPE;
-    return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, S_(stream)) == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ps.st) == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 
 int CC_API(cc_gpt2_logits_bwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const float* dlogits,
                        int64_t ldl, float* dx0, float* g32, void* stream) {
     if (!gpt2_cfg_ok(c) || !shape_ok(c, s) || s->mode < 1 || s->L != 0 || !w32 || !w16 || !ws || !dlogits || ldl < c->V || (s->mode == 2 && !g32))
         return CC_ERR_ARG;
-    hipStream_t st = S_(stream);
-    Gpt2Off o;
-    gpt2_offsets(c, o);
-    Gpt2WS w;
-    gpt2_carve(c, s, s->T, ws, w);      // L == 0: the loss-side buffers are sized for all B*T rows
-    Call cx = call_of(st, w);
-    const int D = c->D, M = s->B * s->T;
+    Gpt2Pass ps(c, s, s->T, ws, stream);      // L == 0: the loss-side buffers are sized for all B*T rows
+    auto& [st, o, w, cx, D, M, H, hd] = ps;
     const bool full = s->mode == 2;
     CC_TRY(f32_to_op16_pad(dlogits, ldl, c->V, w.logits16, c->Vp, M, st));
     // d hf = dlogits · wte ([M,Vp] x [Vp(k), D(n)]); tied lm_head: d wte += dlogits^T hf (hf16 = the rows cc_gpt2_logits normalised)
@@ -1002,13 +849,9 @@ int CC_API(cc_gpt2_bwd_range)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, cons
     if (!gpt2_cfg_ok(c) || !shape_ok(c, s) || s->mode < 1 || !w32 || !w16 || !ws || (s->L > 0 && !dprefix) || (s->mode == 2 && !g32) ||
         l_lo < 0 || l_hi > c->NL || l_lo > l_hi)
         return CC_ERR_ARG;
-    hipStream_t st = S_(stream);
-    Gpt2Off o;
-    gpt2_offsets(c, o);
-    Gpt2WS w;
-    gpt2_carve(c, s, s->T - s->L, ws, w);
-    Call cx = call_of(st, w);
-    const int D = c->D, M = s->B * s->T, H = c->H, hd = D / H, D3 = 3 * D, D4 = 4 * D;
+    Gpt2Pass ps(c, s, s->T - s->L, ws, stream);
+    auto& [st, o, w, cx, D, M, H, hd] = ps;
+    const int D3 = 3 * D, D4 = 4 * D;
     const bool full = s->mode == 2;
     WgradBatch wb;          // full finetune: a layer's four weight gradients as one grouped launch + one slab reduce
     wb.defer = full;
@@ -1019,7 +862,7 @@ int CC_API(cc_gpt2_bwd_range)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, cons
     // gradient is its column sum.  Both are produced by the LayerNorm backward that writes the copy (ln_bwd dmask / dcol) — except for
     // the top layer, whose copy comes from ln_f's row-mapped backward and is masked / summed by separate launches.
     for (int l = l_hi - 1; l >= l_lo; l--) {
-        const auto& y = o.layer[l];
+        const auto y = o.layer(l);
         const bool top = l == c->NL - 1;
         // mlp.c_proj (Conv1D [4D, D]): y = hact W + b
         if (top) CC_TRY(dropout_bf16(w.dx16.p, (size_t)M * D, make_drop(s->p_resid, s->drop_seed, DROP_RESID_MLP, l), st));
@@ -1055,7 +898,7 @@ int CC_API(cc_gpt2_bwd_range)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, cons
         // deferred weight gradients: dx16 (masked layer-input gradient), du16, dx16b, dqkv16 are all still intact here
         if (full) CC_TRY(wgrad_flush(wb, st));
         CC_TRY(ln_bwd(w.dxn16, w.x[l], D, nullptr, w.mean1[l], w.rstd1[l], w32 + y.l1w, w.dx32, w.dx32, w.dx16, full ? g32 + y.l1w : nullptr,
-                      full ? g32 + y.l1b : nullptr, M, D, cx, (full && l > 0) ? g32 + o.layer[l - 1].p2b : nullptr,
+                      full ? g32 + y.l1b : nullptr, M, D, cx, (full && l > 0) ? g32 + o.layer(l - 1).p2b : nullptr,
                       l > 0 ? make_drop(s->p_resid, s->drop_seed, DROP_RESID_MLP, l - 1) : Drop()));
     }
     if (l_lo > 0) return CC_OK;

@@ -10,6 +10,7 @@
 #include "kernels.h"
 #include "decode_pk.h"
 #include "decode_xt.h"
+#include "layout.h"
 
 using namespace CC_NS;
 
@@ -20,15 +21,7 @@ using namespace CC_NS;
 #define CC_DEC_PVU 4
 #endif
 
-#define CC_TRY(expr)                 \
-    do {                             \
-        int _e = (expr);             \
-        if (_e != CC_OK) return _e;  \
-    } while (0)
-
 namespace {
-
-inline hipStream_t S_(void* s) { return static_cast<hipStream_t>(s); }
 
 // x[r,t,:] += wpe[pos0+t,:]
 __global__ void k_add_wpe(const float* __restrict__ xin, const float* __restrict__ wpe, float* __restrict__ x, int R, int Tn, int D, int pos0) {
@@ -1040,42 +1033,42 @@ struct DecWS {
     size_t bytes;
 };
 void dec_carve(const cc_gpt2_cfg* c, int R, int Tn, void* ws, DecWS& w) {
-    char* base = static_cast<char*>(ws);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        off = (off + 255) & ~size_t(255);
-        char* r = base ? base + off : nullptr;
-        off += bytes;
-        return r;
-    };
+    Carver cv(ws);
     const size_t M = (size_t)R * Tn, D = c->D;
-    w.x = (float*)take(M * D * 4);
-    w.x1 = (float*)take(M * D * 4);
-    w.xn = (act_t*)take(M * D * sizeof(act_t));
-    w.qkv = (act_t*)take(M * 3 * D * sizeof(act_t));
-    w.att = (act_t*)take(M * D * sizeof(act_t));
-    w.hact = (act_t*)take(M * 4 * D * sizeof(act_t));
-    w.hf = (act_t*)take((size_t)R * D * sizeof(act_t));
-    w.meanf = (float*)take((size_t)R * 4);
-    w.rstdf = (float*)take((size_t)R * 4);
-    w.last = (int*)take((size_t)R * 4);
-    w.scratch_bytes = (size_t)8 * M * 4 * D * 4;   // up to 8 K-slices of the widest (4D) output
-    w.scratch = (float*)take(w.scratch_bytes);
-    w.pk_ctr = (unsigned*)take((size_t)PK_CTR_WORDS * 4);
-    w.pk_prof = (unsigned long long*)take((size_t)256 * 21 * 8);
-    w.xt_ctl = (unsigned*)take((size_t)(XT_CTL_WORDS + 16) * 4);
-    w.xt_prof = (unsigned long long*)take((size_t)256 * XT_PROF_WORDS * 8);
+    w.x = cv.take<float>(M * D);
+    w.x1 = cv.take<float>(M * D);
+    w.xn = cv.take<act_t>(M * D);
+    w.qkv = cv.take<act_t>(M * 3 * D);
+    w.att = cv.take<act_t>(M * D);
+    w.hact = cv.take<act_t>(M * 4 * D);
+    w.hf = cv.take<act_t>((size_t)R * D);
+    w.meanf = cv.take<float>(R);
+    w.rstdf = cv.take<float>(R);
+    w.last = cv.take<int>(R);
+    w.scratch_bytes = (size_t)8 * M * 4 * D * sizeof(float);   // up to 8 K-slices of the widest (4D) output
+    w.scratch = cv.take<float>(w.scratch_bytes / sizeof(float));
+    w.pk_ctr = cv.take<unsigned>(PK_CTR_WORDS);
+    w.pk_prof = cv.take<unsigned long long>((size_t)256 * 21);
+    w.xt_ctl = cv.take<unsigned>(XT_CTL_WORDS + 16);
+    w.xt_prof = cv.take<unsigned long long>((size_t)256 * XT_PROF_WORDS);
     w.grp_ents = Tn == 1 ? (size_t)R * c->NPOS + (size_t)R * 128 : 0;
-    w.grp_ent = (int2*)take(w.grp_ents * sizeof(int2));
-    w.grp_cnt = (int*)take((size_t)R * 4);
-    w.x3_bytes = kX3 ? ((M * 3 * 4 * D * sizeof(op16_t) + 255) & ~size_t(255)) : 0;      // the deepest A image: mlp.c_proj, K = 4D
-    w.x3 = kX3 ? take(w.x3_bytes) : nullptr;
-    w.bytes = (off + 255) & ~size_t(255);
+    w.grp_ent = cv.take<int2>(w.grp_ents);
+    w.grp_cnt = cv.take<int>(R);
+    w.x3_bytes = kX3 ? x3_img(M, 4 * D) : 0;      // the deepest A image: mlp.c_proj, K = 4D
+    w.x3 = kX3 ? cv.take<char>(w.x3_bytes) : nullptr;
+    w.bytes = cv.bytes();
 }
 
-bool cfg_ok(const cc_gpt2_cfg* c) {
-    return c && (c->op_dtype == CC_OP) && c->D > 0 && c->H > 0 && c->NL > 0 && c->V > 0 && c->Vp >= c->V && (c->Vp % 128) == 0 && (c->D % 8) == 0 && (c->D % c->H) == 0 &&
-           ((c->D / c->H) % 8) == 0;
+// the union list of one position's beam groups, for whichever attention form follows; the same launch clears `clear_words` control words
+// of the persistent launch that consumes the list (none for the per-op path)
+void launch_group_union(int group, int ngroups, hipStream_t st, const int* row_map, const DecWS& w, int pos0, int ctx_max, int cap, int append,
+                        unsigned* clear_ptr, int clear_words) {
+    switch (group) {
+#define CC_GU(G_) case G_: hipLaunchKernelGGL((k_group_union<G_>), dim3(ngroups), dim3(64), 0, st, row_map, w.grp_ent, w.grp_cnt, pos0, ctx_max, cap, append, clear_ptr, clear_words); break;
+        CC_GU(2) CC_GU(3) CC_GU(4) CC_GU(5) CC_GU(6) CC_GU(7) CC_GU(8)
+#undef CC_GU
+        default: break;
+    }
 }
 
 }  // namespace
@@ -1083,15 +1076,15 @@ bool cfg_ok(const cc_gpt2_cfg* c) {
 extern "C" {
 
 int64_t CC_API(cc_decode_ws_bytes)(const cc_gpt2_cfg* cfg, int32_t R, int32_t Tnew) {
-    if (!cfg_ok(cfg) || R <= 0 || Tnew <= 0) return CC_ERR_SHAPE;
+    if (!gpt2_dims_ok(cfg) || R <= 0 || Tnew <= 0) return CC_ERR_SHAPE;
     DecWS w;
     dec_carve(cfg, R, Tnew, nullptr, w);
     return (int64_t)w.bytes;
 }
 
 int64_t CC_API(cc_decode_part_floats)(const cc_gpt2_cfg* cfg, int32_t R) {
-    if (!cfg_ok(cfg) || R <= 0) return CC_ERR_SHAPE;
-    const int Ns = std::min(cfg->Vp, (cfg->V + 7) / 8 * 8);
+    if (!gpt2_dims_ok(cfg) || R <= 0) return CC_ERR_SHAPE;
+    const int Ns = std::min(cfg->Vp, rup(cfg->V, 8));
     return (int64_t)2 * R * ((Ns + 63) / 64);
 }
 
@@ -1117,42 +1110,36 @@ int CC_API(cc_decode_fwd_p)(const cc_gpt2_cfg* c, int32_t R, int32_t Tn, int32_t
 #ifdef CC_EXPERIMENTS      // ---- lab build only: the entry points of include/clipcap_hip_lab.h ----
 // fragment-ordered images of the four GEMM weights of every block, at their arena offsets
 int64_t CC_API(cc_decode_image_bytes)(const cc_gpt2_cfg* c) {
-    if (!cfg_ok(c) || kX3 || (c->D % 64)) return 0;
-    const int64_t D = c->D;
-    return 2 * ((int64_t)c->Vp * D + (int64_t)c->NPOS * D + (int64_t)c->NL * (12 * D * D + 13 * D) + 2 * D);
+    if (!gpt2_dims_ok(c) || kX3 || (c->D % 64)) return 0;
+    return 2 * Gpt2Off(c).total;
 }
 
 int CC_API(cc_decode_image)(const cc_gpt2_cfg* c, const uint16_t* w16, uint16_t* wimg, void* stream) {
-    if (!cfg_ok(c) || !w16 || !wimg) return CC_ERR_ARG;
+    if (!gpt2_dims_ok(c) || !w16 || !wimg) return CC_ERR_ARG;
     if (kX3 || (c->D % 64)) return CC_ERR_SHAPE;
-    const int64_t D = c->D;
-    const int64_t layer0 = (int64_t)c->Vp * D + (int64_t)c->NPOS * D;
-    const int64_t total = layer0 + (int64_t)c->NL * (12 * D * D + 13 * D) + 2 * D;
-    const op16_t* w16t = reinterpret_cast<const op16_t*>(w16) + total;       // transposed Conv1D weights: [N][K], K contiguous
+    const Gpt2Off o(c);
+    const op16_t* w16t = reinterpret_cast<const op16_t*>(w16) + o.total;       // transposed Conv1D weights: [N][K], K contiguous
     op16_t* img = reinterpret_cast<op16_t*>(wimg);
     for (int l = 0; l < c->NL; l++) {
-        const int64_t base = layer0 + (int64_t)l * (12 * D * D + 13 * D);
-        const int64_t aw = base + 2 * D, pw = aw + 3 * D * D + 3 * D, fw = pw + D * D + 3 * D, p2w = fw + 4 * D * D + 4 * D;
-        CC_TRY(skinny_image(w16t + aw, img + aw, 3 * c->D, c->D, S_(stream)));
-        CC_TRY(skinny_image(w16t + pw, img + pw, c->D, c->D, S_(stream)));
-        CC_TRY(skinny_image(w16t + fw, img + fw, 4 * c->D, c->D, S_(stream)));
-        CC_TRY(skinny_image(w16t + p2w, img + p2w, c->D, 4 * c->D, S_(stream)));
+        const auto y = o.layer(l);
+        CC_TRY(skinny_image(w16t + y.aw, img + y.aw, 3 * c->D, c->D, S_(stream)));
+        CC_TRY(skinny_image(w16t + y.pw, img + y.pw, c->D, c->D, S_(stream)));
+        CC_TRY(skinny_image(w16t + y.fw, img + y.fw, 4 * c->D, c->D, S_(stream)));
+        CC_TRY(skinny_image(w16t + y.p2w, img + y.p2w, c->D, 4 * c->D, S_(stream)));
     }
     return CC_OK;
 }
 
 int64_t CC_API(cc_decode_xt_image_bytes)(const cc_gpt2_cfg* c) {
-    if (!cfg_ok(c) || c->H * 64 != c->D) return 0;
+    if (!gpt2_dims_ok(c) || c->H * 64 != c->D) return 0;
     return xt_image_bytes(c->D, c->NL);
 }
 
 int CC_API(cc_decode_xt_image)(const cc_gpt2_cfg* c, const uint16_t* w16, uint16_t* wimg, void* stream) {
-    if (!cfg_ok(c) || !w16 || !wimg) return CC_ERR_ARG;
+    if (!gpt2_dims_ok(c) || !w16 || !wimg) return CC_ERR_ARG;
     if (c->H * 64 != c->D || !xt_image_bytes(c->D, c->NL)) return CC_ERR_SHAPE;
-    const int64_t D = c->D;
-    const int64_t layer0 = (int64_t)c->Vp * D + (int64_t)c->NPOS * D;
-    const int64_t total = layer0 + (int64_t)c->NL * (12 * D * D + 13 * D) + 2 * D;
-    return xt_build_image(c->D, c->NL, layer0, total, w16, wimg, S_(stream));
+    const Gpt2Off o(c);
+    return xt_build_image(c->D, c->NL, o.layer0, o.layer_stride, o.total, w16, wimg, S_(stream));
 }
 
 int CC_API(cc_decode_fwd_x)(const cc_gpt2_cfg* c, int32_t R, int32_t Tn, int32_t pos0, int32_t ctx_max, const float* w32, const uint16_t* w16, const uint16_t* wimg,
@@ -1166,31 +1153,26 @@ static int decode_fwd_impl(const cc_gpt2_cfg* c, int32_t R, int32_t Tn, int32_t 
                            const uint16_t* wteam, const float* x, uint16_t* kv, const int32_t* row_map, int32_t group, void* ws, float* logits, int64_t ldl, float* lpart,
                            void* stream) {
     if (group < 1 || (R > 0 && R % group)) return CC_ERR_ARG;
-    if (!cfg_ok(c) || R <= 0 || Tn <= 0 || pos0 < 0 || !w32 || !w16 || !x || !kv || !ws || !logits) return CC_ERR_ARG;
-    const int Ns = std::min(c->Vp, (c->V + 7) / 8 * 8);
+    if (!gpt2_dims_ok(c) || R <= 0 || Tn <= 0 || pos0 < 0 || !w32 || !w16 || !x || !kv || !ws || !logits) return CC_ERR_ARG;
+    const int Ns = std::min(c->Vp, rup(c->V, 8));
     if (pos0 + Tn > ctx_max || pos0 + Tn > c->NPOS || ldl < Ns || (ldl & 3) || ldl > 0x7fffffff) return CC_ERR_SHAPE;
     if ((size_t)4 * (2 * ctx_max + 8 * (c->D / c->H)) * sizeof(float) > 64 * 1024) return CC_ERR_SHAPE;
     hipStream_t st = S_(stream);
     DecWS w;
     dec_carve(c, R, Tn, ws, w);
     Call cx{st, nullptr, w.x3, w.x3_bytes};
-    constexpr int PL = kX3 ? 3 : 1;          // operand-arena addressing as in api.hip (W16): bf16x3 weights own 3x the elements at 3x the offset
+    const Gpt2Off o(c);
     const int D = c->D, M = R * Tn, H = c->H, hd = D / H;
-    // arena offsets (same order as api.hip::gpt2_offsets)
-    int64_t p = 0;
-    const int64_t wte = p; p += (int64_t)c->Vp * D;
-    const int64_t wpe = p; p += (int64_t)c->NPOS * D;
     // single-position step: positional add + layer 0's ln_1 in one launch; the last layer's finishing pass applies ln_f (below)
     const bool one = Tn == 1 && D <= 2048 && (D & 3) == 0;
     if (one) {
-        hipLaunchKernelGGL(k_add_wpe_ln, dim3((R + 3) / 4), dim3(256), 0, st, x, w32 + wpe, w.x, w32 + p, w32 + p + D, w.xn, R, D, pos0);   // p = layer 0's ln_1.weight
+        hipLaunchKernelGGL(k_add_wpe_ln, dim3((R + 3) / 4), dim3(256), 0, st, x, w32 + o.wpe, w.x, w32 + o.layer(0).l1w, w32 + o.layer(0).l1b, w.xn, R, D, pos0);
     } else {
         const size_t total = (size_t)M * (D >> 2);
-        hipLaunchKernelGGL(k_add_wpe, dim3((int)std::min<size_t>((total + 255) / 256, 2048)), dim3(256), 0, st, x, w32 + wpe, w.x, R, Tn, D, pos0);
+        hipLaunchKernelGGL(k_add_wpe, dim3((int)std::min<size_t>((total + 255) / 256, 2048)), dim3(256), 0, st, x, w32 + o.wpe, w.x, R, Tn, D, pos0);
     }
     const size_t cache_layer = (size_t)2 * R * ctx_max * D;
-    const int64_t total = (int64_t)c->Vp * D + (int64_t)c->NPOS * D + (int64_t)c->NL * (12 * (int64_t)D * D + 13 * (int64_t)D) + 2 * D;
-    const uint16_t* w16t = w16 + (size_t)PL * total;   // transposed Conv1D weights (cc_gpt2_sync_weights): forward GEMMs are NT
+    const uint16_t* w16t = W16(w16, o.total);   // transposed Conv1D weights (cc_gpt2_sync_weights): forward GEMMs are NT
     const float scale = 1.0f / sqrtf((float)hd);
     // beam-group attention (k_decode_attn_group): single-position steps of `group` consecutive rows that share ancestry (a perf hint only)
     const int grp_cap = (group * (pos0 + 1) + 127) & ~127;          // entries per group, whole passes of 128
@@ -1205,7 +1187,7 @@ static int decode_fwd_impl(const cc_gpt2_cfg* c, int32_t R, int32_t Tn, int32_t 
         // XCD-team engine (decode_xt.hip): every XCD runs the whole stack for its own captions; CC_ERR_SHAPE = not covered -> the paths below
         XtLaunch L{};
         L.w32 = w32; L.wimg = reinterpret_cast<const op16_t*>(wteam); L.D = D; L.H = H; L.NL = c->NL; L.M = M; L.group = group; L.pos0 = pos0; L.ctx_max = ctx_max;
-        L.layer0 = p; L.x = w.x; L.x1 = w.x1; L.qkv = w.qkv; L.att = w.att; L.hact = w.hact; L.hf = w.hf;
+        L.layer0 = o.layer0; L.layer_stride = o.layer_stride; L.x = w.x; L.x1 = w.x1; L.qkv = w.qkv; L.att = w.att; L.hact = w.hact; L.hf = w.hf;
         L.kv = reinterpret_cast<act_t*>(kv); L.cache_layer = cache_layer; L.ent = w.grp_ent; L.cnt = w.grp_cnt; L.cap = grp_cap;
         L.ctl = w.xt_ctl; L.sticky = w.xt_ctl + XT_CTL_WORDS;
         static const bool xt_prof = cc_lab_env("CC_XT_PROF") != nullptr;
@@ -1214,31 +1196,20 @@ static int decode_fwd_impl(const cc_gpt2_cfg* c, int32_t R, int32_t Tn, int32_t 
         XtLaunch probe = L;
         probe.ctl = nullptr;
         if (xt_covers(probe)) {
-            switch (group) {
-#define CC_GU(G_) case G_: hipLaunchKernelGGL((k_group_union<G_>), dim3(R / group), dim3(64), 0, st, row_map, w.grp_ent, w.grp_cnt, pos0, ctx_max, grp_cap, 1, w.xt_ctl, XT_CTL_WORDS); break;
-                CC_GU(2) CC_GU(3) CC_GU(4) CC_GU(5) CC_GU(6) CC_GU(7) CC_GU(8)
-#undef CC_GU
-                default: break;
-            }
+            launch_group_union(group, R / group, st, row_map, w, pos0, ctx_max, grp_cap, 1, w.xt_ctl, XT_CTL_WORDS);
             const int rc = decode_layers_xt(L, st);
             if (rc != CC_OK) return rc;
             cc_shared::g_decode_last_path = 2;
             l_first = c->NL;
-            p += (int64_t)c->NL * (12 * (int64_t)D * D + 13 * (int64_t)D);
             hf_ready = true;
         }
     }
     if (l_first == 0 && grp_attn && one && !kX3 && (cc_shared::g_decode_mode & 2)) {
         // the whole layer stack as ONE persistent launch (decode_pk.hip); CC_ERR_SHAPE = geometry not covered -> the per-op launches below
-        switch (group) {
-#define CC_GU(G_) case G_: hipLaunchKernelGGL((k_group_union<G_>), dim3(R / group), dim3(64), 0, st, row_map, w.grp_ent, w.grp_cnt, pos0, ctx_max, grp_cap, 1, w.pk_ctr, PK_CTR_WORDS); break;
-            CC_GU(2) CC_GU(3) CC_GU(4) CC_GU(5) CC_GU(6) CC_GU(7) CC_GU(8)
-#undef CC_GU
-            default: break;
-        }
+        launch_group_union(group, R / group, st, row_map, w, pos0, ctx_max, grp_cap, 1, w.pk_ctr, PK_CTR_WORDS);
         PkLaunch L{};
         L.w32 = w32; L.w16t = reinterpret_cast<const op16_t*>(w16t); L.D = D; L.H = H; L.NL = c->NL; L.M = M; L.group = group; L.pos0 = pos0; L.ctx_max = ctx_max;
-        L.layer0 = p; L.x = w.x; L.x1 = w.x1; L.xn = w.xn; L.qkv = w.qkv; L.att = w.att; L.hact = w.hact; L.hf = w.hf;
+        L.layer0 = o.layer0; L.layer_stride = o.layer_stride; L.x = w.x; L.x1 = w.x1; L.xn = w.xn; L.qkv = w.qkv; L.att = w.att; L.hact = w.hact; L.hf = w.hf;
         L.slab = w.scratch; L.slab_bytes = w.scratch_bytes; L.kv = reinterpret_cast<act_t*>(kv); L.cache_layer = cache_layer;
         L.ent = w.grp_ent; L.cnt = w.grp_cnt; L.cap = grp_cap; L.ctr = w.pk_ctr;
         static const bool pk_prof = cc_lab_env("CC_PK_PROF") != nullptr;
@@ -1247,7 +1218,6 @@ static int decode_fwd_impl(const cc_gpt2_cfg* c, int32_t R, int32_t Tn, int32_t 
         if (rc == CC_OK) {
             cc_shared::g_decode_last_path = 1;
             l_first = c->NL;
-            p += (int64_t)c->NL * (12 * (int64_t)D * D + 13 * (int64_t)D);
             hf_ready = true;
         } else if (rc != CC_ERR_SHAPE) {
             return rc;
@@ -1256,35 +1226,23 @@ static int decode_fwd_impl(const cc_gpt2_cfg* c, int32_t R, int32_t Tn, int32_t 
     // fragment-ordered weight image (cc_decode_image): the K-over-the-waves GEMMs then load the weight operand global -> VGPR
     const op16_t* bimg = (!kX3 && wimg && (cc_shared::g_decode_mode & 8)) ? reinterpret_cast<const op16_t*>(wimg) : nullptr;
     for (int l = l_first; l < c->NL; l++) {
-        const int64_t l1w = p; p += D;
-        const int64_t l1b = p; p += D;
-        const int64_t aw = p; p += (int64_t)D * 3 * D;
-        const int64_t ab = p; p += 3 * D;
-        const int64_t pw = p; p += (int64_t)D * D;
-        const int64_t pb = p; p += D;
-        const int64_t l2w = p; p += D;
-        const int64_t l2b = p; p += D;
-        const int64_t fw = p; p += (int64_t)D * 4 * D;
-        const int64_t fb = p; p += 4 * D;
-        const int64_t p2w = p; p += (int64_t)4 * D * D;
-        const int64_t p2b = p; p += D;
+        const auto y = o.layer(l);
         act_t* kc = reinterpret_cast<act_t*>(kv) + (size_t)l * cache_layer;     // (bf16x3: the cache holds fp32, twice the bytes)
         act_t* vc = kc + (size_t)R * ctx_max * D;
         // xn = ln_1(x): produced by the previous layer's fused finish when possible
-        if (!xn_ready) CC_TRY(ln_fwd(w.x, D, nullptr, w32 + l1w, w32 + l1b, w.xn, nullptr, nullptr, nullptr, M, D, st));
+        if (!xn_ready) CC_TRY(ln_fwd(w.x, D, nullptr, w32 + y.l1w, w32 + y.l1b, w.xn, nullptr, nullptr, nullptr, M, D, st));
         // c_attn (+ fused KV append into the cache)
         const bool f_qkv = gemm_nt_skinny_can_fuse(M, 3 * D, D, w.scratch_bytes) &&
                            ((M + 127) / 128) * ((3 * D + 127) / 128) < skinny_single_min_tiles();
         SkinnyFuse fq;
         if (f_qkv) { fq.kcache = kc; fq.vcache = vc; fq.Tn = Tn; fq.pos0 = pos0; fq.ctx_max = ctx_max; }
-        fq.bimg = bimg ? bimg + aw : nullptr;
-        CC_TRY(gemm_nt_skinny(w.xn, D, w16t + (size_t)PL * aw, D, M, 3 * D, D, w32 + ab, 0, nullptr, nullptr, w.qkv, 3 * D, w.scratch, w.scratch_bytes, cx, &fq));
+        fq.bimg = bimg ? bimg + y.aw : nullptr;
+        CC_TRY(gemm_nt_skinny(w.xn, D, W16(w16t, y.aw), D, M, 3 * D, D, w32 + y.ab, 0, nullptr, nullptr, w.qkv, 3 * D, w.scratch, w.scratch_bytes, cx, &fq));
         if (grp_attn) {
             const int ng = R / group, app = f_qkv ? 0 : 1;
+            if (l == 0) launch_group_union(group, ng, st, row_map, w, pos0, ctx_max, grp_cap, app, nullptr, 0);
 #define CC_GRP(G_)                                                                                                                            \
     case G_:                                                                                                                                  \
-        if (l == 0) hipLaunchKernelGGL((k_group_union<G_>), dim3(ng), dim3(64), 0, st, row_map, w.grp_ent, w.grp_cnt, pos0, ctx_max, grp_cap, app, \
-                                       (unsigned*)nullptr, 0);                                                                               \
         hipLaunchKernelGGL((k_decode_attn_group<G_>), dim3(ng * H), dim3(256), grp_shm, st, w.qkv, kc, vc, w.grp_ent, w.grp_cnt, w.att, H, pos0,  \
                            ctx_max, scale, grp_cap, app);                                                                                     \
         break;
@@ -1301,41 +1259,44 @@ static int decode_fwd_impl(const cc_gpt2_cfg* c, int32_t R, int32_t Tn, int32_t 
         // attn.c_proj + residual (+ fused ln_2)
         const bool f_d = gemm_nt_skinny_can_fuse(M, D, D, w.scratch_bytes) && gemm_nt_skinny_can_fuse(M, D, 4 * D, w.scratch_bytes);
         SkinnyFuse f2;
-        if (f_d) { f2.ln_gamma = w32 + l2w; f2.ln_beta = w32 + l2b; f2.ln_out16 = w.xn; }
-        f2.bimg = bimg ? bimg + pw : nullptr;
-        CC_TRY(gemm_nt_skinny(w.att, D, w16t + (size_t)PL * pw, D, M, D, D, w32 + pb, 0, w.x, w.x1, nullptr, D, w.scratch, w.scratch_bytes, cx, &f2));
-        if (!f_d) CC_TRY(ln_fwd(w.x1, D, nullptr, w32 + l2w, w32 + l2b, w.xn, nullptr, nullptr, nullptr, M, D, st));
+        if (f_d) { f2.ln_gamma = w32 + y.l2w; f2.ln_beta = w32 + y.l2b; f2.ln_out16 = w.xn; }
+        f2.bimg = bimg ? bimg + y.pw : nullptr;
+        CC_TRY(gemm_nt_skinny(w.att, D, W16(w16t, y.pw), D, M, D, D, w32 + y.pb, 0, w.x, w.x1, nullptr, D, w.scratch, w.scratch_bytes, cx, &f2));
+        if (!f_d) CC_TRY(ln_fwd(w.x1, D, nullptr, w32 + y.l2w, w32 + y.l2b, w.xn, nullptr, nullptr, nullptr, M, D, st));
         SkinnyFuse f3;
-        f3.bimg = bimg ? bimg + fw : nullptr;
-        CC_TRY(gemm_nt_skinny(w.xn, D, w16t + (size_t)PL * fw, D, M, 4 * D, D, w32 + fb, 2, nullptr, nullptr, w.hact, 4 * D, w.scratch, w.scratch_bytes, cx, &f3));
-        // mlp.c_proj + residual (+ fused ln_1 of the next layer: its parameters sit right behind this layer's in the arena)
-        // (after the LAST layer p points at ln_f: with one new position per row the finishing pass normalises straight into hf)
+        f3.bimg = bimg ? bimg + y.fw : nullptr;
+        CC_TRY(gemm_nt_skinny(w.xn, D, W16(w16t, y.fw), D, M, 4 * D, D, w32 + y.fb, 2, nullptr, nullptr, w.hact, 4 * D, w.scratch, w.scratch_bytes, cx, &f3));
+        // mlp.c_proj + residual (+ fused ln_1 of the next layer; after the LAST layer, ln_f: with one new position per row the finishing
+        // pass normalises straight into hf)
         const bool last = l + 1 == c->NL;
         const bool f_next = f_d && (!last || one);
         SkinnyFuse f1;
-        if (f_next) { f1.ln_gamma = w32 + p; f1.ln_beta = w32 + p + D; f1.ln_out16 = last ? w.hf : w.xn; }      // p now points at layer l+1's ln_1.weight (or ln_f)
-        f1.bimg = bimg ? bimg + p2w : nullptr;
-        CC_TRY(gemm_nt_skinny(w.hact, 4 * D, w16t + (size_t)PL * p2w, 4 * D, M, D, 4 * D, w32 + p2b, 0, w.x1, w.x, nullptr, D, w.scratch, w.scratch_bytes, cx, &f1));
+        if (f_next) {
+            f1.ln_gamma = w32 + (last ? o.lnf_w : o.layer(l + 1).l1w);
+            f1.ln_beta = w32 + (last ? o.lnf_b : o.layer(l + 1).l1b);
+            f1.ln_out16 = last ? w.hf : w.xn;
+        }
+        f1.bimg = bimg ? bimg + y.p2w : nullptr;
+        CC_TRY(gemm_nt_skinny(w.hact, 4 * D, W16(w16t, y.p2w), 4 * D, M, D, 4 * D, w32 + y.p2b, 0, w.x1, w.x, nullptr, D, w.scratch, w.scratch_bytes, cx, &f1));
         xn_ready = f_next && !last;
         hf_ready = f_next && last;
     }
-    const int64_t lnf_w = p, lnf_b = p + D;
     if (!hf_ready) {
         hipLaunchKernelGGL(k_last_rows, dim3((R + 255) / 256), dim3(256), 0, st, w.last, R, Tn);
-        CC_TRY(ln_fwd(w.x, D, w.last, w32 + lnf_w, w32 + lnf_b, w.hf, nullptr, w.meanf, w.rstdf, R, D, st));
+        CC_TRY(ln_fwd(w.x, D, w.last, w32 + o.lnf_w, w32 + o.lnf_b, w.hf, nullptr, w.meanf, w.rstdf, R, D, st));
     }
     if (lpart) {      // logits + per-(row, 64-column block) softmax partials for cc_beam_step_p
         const int npart = (Ns + 63) / 64;
-        CC_TRY(gemm_logits_part(w.hf, D, w16 + (size_t)PL * wte, D, R, Ns, c->V, D, logits, (int)ldl, lpart, lpart + (size_t)R * npart, npart, cx));
+        CC_TRY(gemm_logits_part(w.hf, D, W16(w16, o.wte), D, R, Ns, c->V, D, logits, (int)ldl, lpart, lpart + (size_t)R * npart, npart, cx));
     } else {
-        CC_TRY(gemm_f32out(0, 0, w.hf, D, w16 + (size_t)PL * wte, D, R, Ns, D, logits, (int)ldl, nullptr, 0, 1.0f, 1, cx));
+        CC_TRY(gemm_f32out(0, 0, w.hf, D, W16(w16, o.wte), D, R, Ns, D, logits, (int)ldl, nullptr, 0, 1.0f, 1, cx));
     }
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 
 #ifdef CC_EXPERIMENTS
 int CC_API(cc_decode_ws_check)(const cc_gpt2_cfg* c, int32_t R, int32_t Tn, const void* ws, void* stream) {
-    if (!cfg_ok(c) || R <= 0 || Tn <= 0 || !ws) return CC_ERR_ARG;
+    if (!gpt2_dims_ok(c) || R <= 0 || Tn <= 0 || !ws) return CC_ERR_ARG;
     DecWS w;
     dec_carve(c, R, Tn, const_cast<void*>(ws), w);
     unsigned e = 0;
@@ -1349,7 +1310,7 @@ int CC_API(cc_decode_ws_check)(const cc_gpt2_cfg* c, int32_t R, int32_t Tn, cons
 
 int CC_API(cc_decode_reorder)(const cc_gpt2_cfg* c, int32_t R_src, int32_t R_dst, int32_t ctx, int32_t ctx_max, const uint16_t* kv_src, uint16_t* kv_dst,
                       const int32_t* src, void* stream) {
-    if (!cfg_ok(c) || R_src <= 0 || R_dst <= 0 || ctx < 0 || ctx > ctx_max || !kv_src || !kv_dst || !src || kv_src == kv_dst) return CC_ERR_ARG;
+    if (!gpt2_dims_ok(c) || R_src <= 0 || R_dst <= 0 || ctx < 0 || ctx > ctx_max || !kv_src || !kv_dst || !src || kv_src == kv_dst) return CC_ERR_ARG;
     if (ctx == 0) return CC_OK;
     const size_t total = (size_t)c->NL * 2 * R_dst * ctx * (c->D * sizeof(act_t) / 16);
     hipLaunchKernelGGL(k_kv_reorder, dim3((int)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, S_(stream),
@@ -1424,35 +1385,35 @@ int CC_API(cc_beam_step_p)(int32_t S, int32_t beam, int32_t V, const float* logi
 }
 
 int CC_API(cc_embed_tokens)(const cc_gpt2_cfg* c, int32_t R, const float* w32, const int32_t* tokens, float* out, void* stream) {
-    if (!cfg_ok(c) || R <= 0 || !w32 || !tokens || !out) return CC_ERR_ARG;
+    if (!gpt2_dims_ok(c) || R <= 0 || !w32 || !tokens || !out) return CC_ERR_ARG;
     const size_t total = (size_t)R * (c->D >> 2);
     hipLaunchKernelGGL(k_embed_tokens, dim3((int)std::min<size_t>((total + 255) / 256, 2048)), dim3(256), 0, S_(stream), w32, tokens, out, R, c->D, c->Vp);
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 
 int CC_API(cc_embed_tokens_bwd)(const cc_gpt2_cfg* c, int32_t R, const float* dout, const int32_t* tokens, float* dwte, void* stream) {
-    if (!cfg_ok(c) || R <= 0 || !dout || !tokens || !dwte) return CC_ERR_ARG;
+    if (!gpt2_dims_ok(c) || R <= 0 || !dout || !tokens || !dwte) return CC_ERR_ARG;
     const size_t total = (size_t)R * c->D;
     hipLaunchKernelGGL(k_embed_tokens_bwd, dim3((int)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, S_(stream), dout, tokens, dwte, R, c->D, c->Vp);
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 
 int CC_API(cc_embed_tokens_bwd_ws)(const cc_gpt2_cfg* c, int32_t R, const float* dout, const int32_t* tokens, float* dwte, void* ws, void* stream) {
-    if (!cfg_ok(c) || R <= 0 || !dout || !tokens || !dwte) return CC_ERR_ARG;
+    if (!gpt2_dims_ok(c) || R <= 0 || !dout || !tokens || !dwte) return CC_ERR_ARG;
     ScatterSrc e;
     e.ids32 = tokens; e.f32 = dout; e.rpb = 1; e.bstride = (size_t)c->D;
     return scatter_rows(e, R, c->D, c->Vp, dwte, ws, S_(stream));
 }
 
 int64_t CC_API(cc_embed_tokens_bwd_ws_bytes)(const cc_gpt2_cfg* c, int32_t R) {
-    if (!cfg_ok(c) || R <= 0) return CC_ERR_ARG;
+    if (!gpt2_dims_ok(c) || R <= 0) return CC_ERR_ARG;
     return (int64_t)scatter_ws_bytes(R, c->D);
 }
 
 int CC_API(cc_beam_advance)(const cc_gpt2_cfg* c, int32_t R, int32_t beam, const float* w32, const int32_t* next_tokens, const int32_t* src_rows,
                     int32_t pos, int32_t ctx_max, const int32_t* row_map_in, int32_t* row_map_out, int32_t step, int32_t tok_ld,
                     const int32_t* tokens_in, int32_t* tokens_out, float* x_out, void* stream) {
-    if (!cfg_ok(c) || R <= 0 || beam <= 0 || (R % beam) || !w32 || !next_tokens || !x_out || pos < 0 || pos > ctx_max) return CC_ERR_ARG;
+    if (!gpt2_dims_ok(c) || R <= 0 || beam <= 0 || (R % beam) || !w32 || !next_tokens || !x_out || pos < 0 || pos > ctx_max) return CC_ERR_ARG;
     if ((row_map_out && (!row_map_in || row_map_in == row_map_out)) || (tokens_out && (step < 0 || step >= tok_ld || (step > 0 && !tokens_in) ||
                                                                                       tokens_in == tokens_out)))
         return CC_ERR_ARG;

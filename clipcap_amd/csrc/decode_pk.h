@@ -32,7 +32,7 @@ struct PkLaunch {
     const float* w32;
     const op16_t* w16t;
     int D, H, NL, M, group, pos0, ctx_max;
-    long long layer0;
+    long long layer0, layer_stride;      // as PkArgs, from the arena layout (layout.h)
     float *x, *x1;
     act_t *xn, *qkv, *att, *hact, *hf;
     float* slab;

@@ -588,7 +588,7 @@ int decode_layers_persistent(const PkLaunch& L, hipStream_t st) {
     const int nb = (std::min(n_cu, 256) / 8) * 8;        // one workgroup per CU; a multiple of 8 for the XCD-aware schedule
     if (nb < 8) return CC_ERR_SHAPE;
     PkArgs a{};
-    a.w32 = L.w32; a.w16t = L.w16t; a.D = D; a.H = H; a.NL = L.NL; a.layer0 = L.layer0; a.layer_stride = 12LL * D * D + 13LL * D;
+    a.w32 = L.w32; a.w16t = L.w16t; a.D = D; a.H = H; a.NL = L.NL; a.layer0 = L.layer0; a.layer_stride = L.layer_stride;
     a.M = M; a.NG = M / G; a.nrt = (M + 63) / 64; a.pos0 = L.pos0; a.ctx_max = L.ctx_max; a.scale = 0.125f;
     a.x = L.x; a.x1 = L.x1; a.xn = L.xn; a.qkv = L.qkv; a.att = L.att; a.hact = L.hact; a.hf = L.hf; a.slab = L.slab;
     a.prof = L.prof; a.kv = L.kv; a.cache_layer = L.cache_layer; a.ent = L.ent; a.cnt = L.cnt; a.cap = L.cap; a.ctr = L.ctr;

@@ -11,7 +11,8 @@ struct XtLaunch {
     const float* w32;            // fp32 parameter arena (biases, LayerNorm parameters)
     const op16_t* wimg;          // fragment-ordered weight image (cc_decode_xt_image)
     int D, H, NL, M, group, pos0, ctx_max;
-    long long layer0;            // element offset of layer 0's ln_1.weight in the arena
+    long long layer0;            // element offset of layer 0's ln_1.weight in the arena (layout.h)
+    long long layer_stride;      // elements per layer
     float *x, *x1;
     act_t *qkv, *att, *hact, *hf;
     act_t* kv;
@@ -25,7 +26,7 @@ struct XtLaunch {
 };
 // frags per wave and layer / image bytes; 0 when the width is not covered
 int64_t xt_image_bytes(int D, int NL);
-int xt_build_image(int D, int NL, long long layer0, long long total, const op16_t* w16, op16_t* img, hipStream_t st);
+int xt_build_image(int D, int NL, long long layer0, long long layer_stride, long long total, const op16_t* w16, op16_t* img, hipStream_t st);
 // true when decode_layers_xt would launch for this geometry on this device (nothing is launched)
 bool xt_covers(const XtLaunch& L);
 // CC_OK, or CC_ERR_SHAPE when the geometry / build / device is not covered (the caller then takes the launch-per-op path)

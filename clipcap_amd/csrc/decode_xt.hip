@@ -725,10 +725,9 @@ int64_t xt_image_bytes(int D, int NL) {
     return ((int64_t)XT_TEAM * 4 * NL * fr + XT_RING_MAX) * 1024;
 }
 
-int xt_build_image(int D, int NL, long long layer0, long long total, const op16_t* w16, op16_t* img, hipStream_t st) {
+int xt_build_image(int D, int NL, long long layer0, long long stride, long long total, const op16_t* w16, op16_t* img, hipStream_t st) {
     if (!xt_image_bytes(D, NL)) return CC_ERR_SHAPE;
     const op16_t* w16t = w16 + total;            // transposed Conv1D weights: [N][K], K contiguous (cc_gpt2_sync_weights)
-    const long long stride = 12LL * D * D + 13LL * D;
     if (hipMemsetAsync(reinterpret_cast<char*>(img) + xt_image_bytes(D, NL) - (int64_t)XT_RING_MAX * 1024, 0, (size_t)XT_RING_MAX * 1024, st) != hipSuccess) return CC_ERR_LAUNCH;
     if (D == 1024) hipLaunchKernelGGL((k_xt_image<1024>), dim3(2048), dim3(256), 0, st, w16t, layer0, stride, NL, reinterpret_cast<u32x4*>(img));
     else hipLaunchKernelGGL((k_xt_image<512>), dim3(2048), dim3(256), 0, st, w16t, layer0, stride, NL, reinterpret_cast<u32x4*>(img));
@@ -748,7 +747,7 @@ static bool xt_prepare(const XtLaunch& L, XtArgs& a, size_t& lds) {
     if (n_cu != 8 * XT_TEAM) return false;
     a = XtArgs{};
     a.w32 = L.w32; a.wimg = reinterpret_cast<const u32x4*>(L.wimg); a.NL = L.NL; a.M = M; a.NG = M / G; a.cpt = (a.NG + 7) / 8;
-    a.pos0 = L.pos0; a.ctx_max = L.ctx_max; a.cap = L.cap; a.scale = 0.125f; a.layer0 = L.layer0; a.layer_stride = 12LL * D * D + 13LL * D;
+    a.pos0 = L.pos0; a.ctx_max = L.ctx_max; a.cap = L.cap; a.scale = 0.125f; a.layer0 = L.layer0; a.layer_stride = L.layer_stride;
     a.x = L.x; a.x1 = L.x1; a.qkv = L.qkv; a.att = L.att; a.hact = L.hact; a.hf = L.hf; a.kv = L.kv; a.cache_layer = L.cache_layer;
     a.ent = L.ent; a.cnt = L.cnt; a.ctl = L.ctl; a.sticky = L.sticky; a.prof = L.prof;
     a.rt_max = a.cpt * G;
@@ -786,7 +785,7 @@ int decode_layers_xt(const XtLaunch& L, hipStream_t st) {
 }
 #else
 int64_t xt_image_bytes(int, int) { return 0; }
-int xt_build_image(int, int, long long, long long, const op16_t*, op16_t*, hipStream_t) { return CC_ERR_SHAPE; }
+int xt_build_image(int, int, long long, long long, long long, const op16_t*, op16_t*, hipStream_t) { return CC_ERR_SHAPE; }
 bool xt_covers(const XtLaunch&) { return false; }
 int decode_layers_xt(const XtLaunch&, hipStream_t) { return CC_ERR_SHAPE; }
 #endif
