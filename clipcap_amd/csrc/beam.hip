@@ -1,0 +1,621 @@
+// Device-side beam-search update of the caption decoders (reference: clipcap/inference/base.py:84-119): from one step's logits to the next
+// tokens, source rows, scores, lengths and stop flags.  fp32 / integer work only, so this unit is built once (Makefile).
+#include "layout.h"
+
+using namespace CC_NS;
+
+namespace {
+
+// ---- beam step (base.py:84-119) in three small kernels so that all CUs take part --------------------------------
+//   k_beam_rowstats : one block per (sample, beam row): max and sum(exp) of logits/temperature
+//   k_beam_partial  : grid (sample, chunk): top-`beam` of the length-normalised candidate scores inside one slice of the
+//                     flattened beam*V candidate space (thread-local insertion lists + block-wide selection)
+//   k_beam_final    : one block per sample merges the chunk winners, then gathers / updates scores, lengths, stopped flags
+// Ties resolve to the lowest flat index b*V + v.
+constexpr int BEAM_MAX = 16;
+constexpr int BEAM_CHUNKS = 16;
+
+__device__ __forceinline__ bool cand_better(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
+
+template <bool VEC>   // VEC: rows are 16-B aligned (ldl % 4 == 0, aligned base) -> float4 loads
+__global__ __launch_bounds__(512) void k_beam_rowstats(const float* __restrict__ logits, size_t ldl, int V, float inv_temp, float* __restrict__ rs) {
+    // one pass: every thread keeps a running (max, sum of exp(x - max)) pair, rescaling the sum when its max moves; pairs are merged
+    // the same way across lanes and waves (the logits matrix, 64 MB at 320 x 50257, is read once instead of twice)
+    __shared__ float redm[8], reds[8];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const float* lg = logits + (size_t)row * ldl;
+    const int V4 = VEC ? (V >> 2) : 0;
+    float m = -INFINITY, sum = 0.f;
+    auto add4 = [&](float a, float b, float c, float d) {
+        const float mx = fmaxf(fmaxf(a, b), fmaxf(c, d));
+        if (mx > m) { sum *= expf(m - mx); m = mx; }              // expf(-inf) = 0 on the first group
+        sum += expf(a - m) + expf(b - m) + expf(c - m) + expf(d - m);
+    };
+    for (int v = tid; v < V4; v += 512) {
+        const float4 x = reinterpret_cast<const float4*>(lg)[v];
+        add4(x.x * inv_temp, x.y * inv_temp, x.z * inv_temp, x.w * inv_temp);
+    }
+    for (int v = V4 * 4 + tid; v < V; v += 512) {
+        const float x = lg[v] * inv_temp;
+        if (x > m) { sum *= expf(m - x); m = x; }
+        sum += expf(x - m);
+    }
+    auto merge = [&](float om, float os) {
+        const float mx = fmaxf(m, om);
+        if (mx == -INFINITY) return;                               // both empty
+        sum = sum * expf(m - mx) + os * expf(om - mx);
+        m = mx;
+    };
+    for (int o = 32; o > 0; o >>= 1) {
+        const float om = __shfl_xor(m, o, 64), os = __shfl_xor(sum, o, 64);
+        merge(om, os);
+    }
+    if ((tid & 63) == 0) { redm[tid >> 6] = m; reds[tid >> 6] = sum; }
+    __syncthreads();
+    if (tid == 0) {
+        m = redm[0]; sum = reds[0];
+        for (int i = 1; i < 8; i++) merge(redm[i], reds[i]);
+        rs[2 * row] = m;
+        rs[2 * row + 1] = sum;
+    }
+}
+
+// ---- the pieces the selection kernels share ----------------------------------------------------------------------------------------
+// One round of block arg-max under cand_better, for blocks of NW full waves: wave arg-max by shuffles, the wave winners meet in LDS
+// (red / redi hold 2 NW entries, double-buffered on k, so a round costs one barrier), every thread merges them.  On return every thread
+// holds the block's best (bv, bi), and thread 0 has recorded it as pick k (no candidate left: -inf, 0x7fffffff).
+template <int NW>
+__device__ __forceinline__ void argmax_round(int k, float& bv, int& bi, float* red, int* redi, float* sel_v, int* sel_i) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (cand_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    if (lane == 0) { red[(k & 1) * NW + wv] = bv; redi[(k & 1) * NW + wv] = bi; }
+    __syncthreads();
+    bv = red[(k & 1) * NW]; bi = redi[(k & 1) * NW];
+#pragma unroll
+    for (int w = 1; w < NW; w++) {
+        const float ov = red[(k & 1) * NW + w];
+        const int oi = redi[(k & 1) * NW + w];
+        if (cand_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    if (threadIdx.x == 0) { sel_v[k] = bi != 0x7fffffff ? bv : -INFINITY; sel_i[k] = bi; }
+}
+
+// The `beam` best of the n (value, flat index) candidates of an LDS list, best first, into sel_v / sel_i: one arg-max round per pick; the
+// winner is retired by its flat index (unique: one owner; visible after the round's closing barrier).  Blocks of NT threads.
+template <int NT>
+__device__ __forceinline__ void pick_from_list(const float* cv, int* ci, int n, int beam, float* red, int* redi, float* sel_v, int* sel_i) {
+    const int tid = threadIdx.x;
+    for (int k = 0; k < beam; k++) {
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+        for (int c = tid; c < n; c += NT)
+            if (ci[c] != 0x7fffffff && cand_better(cv[c], ci[c], bv, bi)) { bv = cv[c]; bi = ci[c]; }
+        argmax_round<NT / 64>(k, bv, bi, red, redi, sel_v, sel_i);
+        for (int c = tid; c < n; c += NT)
+            if (ci[c] == bi) ci[c] = 0x7fffffff;
+        __syncthreads();
+    }
+}
+
+// The TB-th largest of the 256 threads' maxima: a lower bound of the block's TB-th best key (equal maxima leave together: the bound only
+// gets lower, which is still valid).  red: 8 floats.
+template <int TB>
+__device__ __forceinline__ float kth_bound(float tmax, float* red) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    float thr = -INFINITY;
+    for (int k = 0; k < TB; k++) {
+        float bv = wave_max(tmax);
+        if (lane == 0) red[(k & 1) * 4 + wv] = bv;
+        __syncthreads();
+        thr = fmaxf(fmaxf(red[(k & 1) * 4], red[(k & 1) * 4 + 1]), fmaxf(red[(k & 1) * 4 + 2], red[(k & 1) * 4 + 3]));
+        if (tmax == thr) tmax = -INFINITY;
+    }
+    return thr;
+}
+
+// What a candidate's value needs of its beam row: the stop flag, max and sum(exp) of the row's logits (over the temperature), log(sum),
+// the beam's score so far and the length the candidate would have (seq_len + 1; a stopped beam keeps its length).  First step: sc = 0,
+// len = 1, nothing stopped.
+struct BeamRow {
+    int st;
+    float m, sum, lsum, sc, len;
+};
+// base.py:96-101: only token 0 continues a stopped beam, at the beam's own average
+__device__ __forceinline__ float beam_stopped(const BeamRow& g, int v, int first) { return v == 0 ? (first ? 0.f : (g.sc + 0.f) / g.len) : -INFINITY; }
+// Cheap image of a candidate's value, monotone in the logit: exact for stopped beams, within ~1e-6 of beam_val otherwise
+// (x t - m - log(sum) instead of log(exp(x t - m) / sum)).  TEMP = false: temperature 1, no multiply.
+template <bool TEMP>
+__device__ __forceinline__ float beam_key(const BeamRow& g, int v, float xraw, float inv_temp, int first) {
+    if (g.st) return beam_stopped(g, v, first);
+    const float d = ((TEMP ? xraw * inv_temp : xraw) - g.m) - g.lsum;
+    return first ? d : (g.sc + d) * (1.0f / g.len);
+}
+// The candidate's value in the reference's arithmetic: softmax().log(), then the length-normalised sum (base.py:99-101)
+template <bool TEMP>
+__device__ __forceinline__ float beam_val(const BeamRow& g, int v, float xraw, float inv_temp, int first) {
+    if (g.st) return beam_stopped(g, v, first);
+    const float lp = logf(expf((TEMP ? xraw * inv_temp : xraw) - g.m) / g.sum);
+    return first ? lp : (g.sc + lp) / g.len;
+}
+
+// State update of base.py:86-119 for output slot o: the pick (val, token v) continues a source beam of length len (as BeamRow::len) and
+// stop flag st; both are read by the caller before any slot is written.  scores = scores_sum_average * seq_lengths (base.py:114).
+__device__ __forceinline__ void beam_commit(int o, float val, int b, int v, int first, int stop_token, float len, int st, float* scores,
+                                            float* seq_len, unsigned char* stopped, int* next_tok, int* src_row) {
+    float nl, nsc;
+    int hs;
+    if (first) { nl = 1.f; nsc = val; hs = 0; }
+    else { nl = len; nsc = val * nl; hs = st; }
+    hs |= (v == stop_token) ? 1 : 0;
+    next_tok[o] = v;
+    src_row[o] = b;
+    scores[o] = nsc;
+    seq_len[o] = nl;
+    stopped[o] = (unsigned char)hs;
+}
+
+// TB = compile-time beam width (0: run-time width, lists in scratch memory — the slow fallback for beam > 8).
+// Each candidate's exact value needs expf + divide + logf (the reference's softmax().log() arithmetic); almost all of the 250 k
+// candidates lose against the thread's current worst kept value, so a cheap bound (x t - m - log(sum), equal up to ~1e-6) with a
+// 1e-3 margin decides whether the exact value is evaluated at all.
+template <int TB>
+__global__ __launch_bounds__(256) void k_beam_partial(const float* __restrict__ logits, size_t ldl, int beam_rt, int V, float inv_temp, int first,
+                                                      const float* __restrict__ rs, const float* __restrict__ scores,
+                                                      const float* __restrict__ seq_len, const unsigned char* __restrict__ stopped,
+                                                      float* __restrict__ pval, int* __restrict__ pidx) {
+    __shared__ float red[8];
+    __shared__ int redi[8];
+    __shared__ float cval[TB > 0 ? 1 : 256 * BEAM_MAX];          // candidate arrays: run-time-width fallback only
+    __shared__ int cidx[TB > 0 ? 1 : 256 * BEAM_MAX];
+    __shared__ float sel_v[BEAM_MAX];
+    __shared__ int sel_i[BEAM_MAX];
+    constexpr int LB = TB > 0 ? TB : BEAM_MAX;
+    const int beam = TB > 0 ? TB : beam_rt;
+    const int s = blockIdx.x, ch = blockIdx.y, tid = threadIdx.x;
+    const int nrows = first ? 1 : beam;
+    const int total = nrows * V;
+    const int per = (total + BEAM_CHUNKS - 1) / BEAM_CHUNKS;
+    const int lo = ch * per, hi = min(total, lo + per);
+    const float* lg = logits + (size_t)s * beam * ldl;
+    // a chunk (total / 16 candidates) spans at most two beam rows when V >= per; handled generally by walking row segments.
+    // scan(f): f(idx, v, row record, raw logit) for every candidate of the chunk, SU logits fetched per thread before any is looked at
+    auto scan = [&](auto&& f) {
+        for (int b = lo / V; b < nrows && b * V < hi; b++) {
+            const int seg_lo = max(lo, b * V), seg_hi = min(hi, (b + 1) * V);
+            BeamRow g;
+            g.st = !first && stopped[s * beam + b];
+            g.m = rs[2 * (s * beam + b)]; g.sum = rs[2 * (s * beam + b) + 1];
+            g.lsum = logf(g.sum);
+            g.sc = first ? 0.f : scores[s * beam + b];
+            g.len = first ? 1.f : (seq_len[s * beam + b] + (g.st ? 0.f : 1.f));
+            const float* row = lg + (size_t)b * ldl - (size_t)b * V;      // row[idx] = lg[b * ldl + (idx - b V)]
+            constexpr int SU = 8;
+            for (int idx0 = seg_lo + tid; idx0 < seg_hi; idx0 += 256 * SU) {
+                float xs[SU];
+#pragma unroll
+                for (int u = 0; u < SU; u++) xs[u] = g.st ? 0.f : row[min(idx0 + u * 256, seg_hi - 1)];
+#pragma unroll
+                for (int u = 0; u < SU; u++) {
+                    const int idx = idx0 + u * 256;
+                    if (idx < seg_hi) f(idx, idx - b * V, g, xs[u]);
+                }
+            }
+        }
+    };
+    bool done = false;
+    if constexpr (TB > 0) {
+        // Two passes instead of a sorted list per thread (with per-thread lists some lane of a wave inserts in almost every iteration,
+        // so every wave ran the ~100-instruction exact-value + insertion path for all of its candidates):
+        //   1. thread maxima of the cheap key; the TB-th largest thread maximum is a lower bound of the chunk's TB-th best value;
+        //   2. only candidates within 1e-3 of that bound get the exact value and go to a small LDS list (a handful per block);
+        //   3. TB picks from the list (ties -> lowest flat index).
+        constexpr int FCAP = 1024;
+        __shared__ float fcv[FCAP];
+        __shared__ int fci[FCAP];
+        __shared__ int fcount;
+        float tmax = -INFINITY;
+        scan([&](int, int v, const BeamRow& g, float xraw) { tmax = fmaxf(tmax, beam_key<true>(g, v, xraw, inv_temp, first)); });
+        if (tid == 0) fcount = 0;
+        const float thr = kth_bound<TB>(tmax, red);
+        scan([&](int idx, int v, const BeamRow& g, float xraw) {
+            const float key = beam_key<true>(g, v, xraw, inv_temp, first);
+            if (key > -INFINITY && key + 1e-3f >= thr) {
+                const int pos = atomicAdd(&fcount, 1);
+                if (pos < FCAP) { fcv[pos] = beam_val<true>(g, v, xraw, inv_temp, first); fci[pos] = idx; }
+            }
+        });
+        __syncthreads();
+        if (fcount <= FCAP) {
+            pick_from_list<256>(fcv, fci, fcount, TB, red, redi, sel_v, sel_i);
+            done = true;
+        }
+    }
+    if (!done) {
+        // sorted insertion list per thread: any width (TB = 0: run-time width), and the overflow path of the list above (e.g. all logits equal)
+        float lv[LB];
+        int li[LB];
+#pragma unroll
+        for (int k = 0; k < LB; k++) { lv[k] = -INFINITY; li[k] = 0x7fffffff; }
+        scan([&](int idx, int v, const BeamRow& g, float xraw) {
+            if (!g.st) {
+                const float worst = TB > 0 ? lv[LB - 1] : lv[beam - 1];
+                if (beam_key<true>(g, v, xraw, inv_temp, first) + 1e-3f < worst) return;
+            }
+            const float val = beam_val<true>(g, v, xraw, inv_temp, first);
+            if constexpr (TB > 0) {
+                if (cand_better(val, idx, lv[LB - 1], li[LB - 1])) {
+                    lv[LB - 1] = val; li[LB - 1] = idx;
+#pragma unroll
+                    for (int k = LB - 1; k > 0; k--) {
+                        if (cand_better(lv[k], li[k], lv[k - 1], li[k - 1])) {
+                            const float tv = lv[k]; lv[k] = lv[k - 1]; lv[k - 1] = tv;
+                            const int ti = li[k]; li[k] = li[k - 1]; li[k - 1] = ti;
+                        }
+                    }
+                }
+            } else {
+                if (cand_better(val, idx, lv[beam - 1], li[beam - 1])) {
+                    int k = beam - 1;
+                    while (k > 0 && cand_better(val, idx, lv[k - 1], li[k - 1])) { lv[k] = lv[k - 1]; li[k] = li[k - 1]; k--; }
+                    lv[k] = val; li[k] = idx;
+                }
+            }
+        });
+        if constexpr (TB > 0) {
+            // every thread's list is sorted, so the block's next best is the best list HEAD; the owner pops its list
+            for (int k = 0; k < TB; k++) {
+                float bv = lv[0];
+                int bi = li[0];
+                argmax_round<4>(k, bv, bi, red, redi, sel_v, sel_i);
+                if (li[0] == bi && bi != 0x7fffffff) {              // flat indices are unique: exactly one owner
+#pragma unroll
+                    for (int q = 0; q + 1 < LB; q++) { lv[q] = lv[q + 1]; li[q] = li[q + 1]; }
+                    lv[LB - 1] = -INFINITY; li[LB - 1] = 0x7fffffff;
+                }
+            }
+            __syncthreads();
+        } else {
+            for (int k = 0; k < beam; k++) { cval[tid * beam + k] = lv[k]; cidx[tid * beam + k] = li[k]; }
+            __syncthreads();
+            pick_from_list<256>(cval, cidx, 256 * beam, beam, red, redi, sel_v, sel_i);
+        }
+    }
+    if (tid < beam) {
+        pval[((size_t)s * BEAM_CHUNKS + ch) * beam + tid] = sel_v[tid];
+        pidx[((size_t)s * BEAM_CHUNKS + ch) * beam + tid] = sel_i[tid];
+    }
+}
+
+__global__ __launch_bounds__(64) void k_beam_final(int beam, int V, int first, int stop_token, const float* __restrict__ pval,
+                                                   const int* __restrict__ pidx, float* __restrict__ scores, float* __restrict__ seq_len,
+                                                   unsigned char* __restrict__ stopped, int* __restrict__ next_tok, int* __restrict__ src_row) {
+    __shared__ float red[2];
+    __shared__ int redi[2];
+    __shared__ float cval[BEAM_CHUNKS * BEAM_MAX];
+    __shared__ int cidx[BEAM_CHUNKS * BEAM_MAX];
+    __shared__ float sel_v[BEAM_MAX];
+    __shared__ int sel_i[BEAM_MAX];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const int ncand = BEAM_CHUNKS * beam;
+    for (int c = tid; c < ncand; c += 64) { cval[c] = pval[(size_t)s * ncand + c]; cidx[c] = pidx[(size_t)s * ncand + c]; }
+    __syncthreads();
+    pick_from_list<64>(cval, cidx, ncand, beam, red, redi, sel_v, sel_i);
+    // the source beams' state goes to registers before the barrier, the slots are written after it
+    const int idx = tid < beam ? sel_i[tid] : 0;
+    const int b = idx / V, v = idx % V;
+    int st = 0;
+    float len = 1.f;
+    if (tid < beam && !first) {
+        st = stopped[s * beam + b];
+        len = seq_len[s * beam + b] + (st ? 0.f : 1.f);
+    }
+    __syncthreads();
+    if (tid < beam) beam_commit(s * beam + tid, sel_v[tid], b, v, first, stop_token, len, st, scores, seq_len, stopped, next_tok, src_row);
+}
+
+// ---- beam step in ONE kernel, fed by the lm_head epilogue's partials (gemm.hip.h EpiLogits) ----------------------------------
+// One block per sample.  The row statistics (max, sum of exp) come from the per-(row, 64-column block) partials — no pass over the
+// logits; every 64-column block is bounded by the key of its maximum, the TB-th largest bound is a lower bound of the sample's TB-th
+// best candidate, and only the blocks whose bound reaches it (a handful) are read from the logits matrix at all.  Same arithmetic
+// (softmax().log() as the reference writes it), same tie rule (lowest flat index) and same state update as the three-kernel path,
+// which stays as the fallback for temperature != 1, run-time beam widths and candidate-list overflow (e.g. all logits equal).
+// This is the product's kernel (all but the first steps of a decode batch), and its compiled code is held fixed: routed through the
+// shared pieces above (argmax_round, pick_from_list, kth_bound, BeamRow / beam_key / beam_val, beam_commit), each tried alone, every
+// instantiation compiles differently (profiles/r12_a_beam_refactor.md), so it keeps these five idioms written out.  A change to the tie
+// rule, the stopped-beam rule or the length normalisation is made in the shared pieces AND here.
+template <int TB, int PER>      // PER: (row, block) partials per thread = ceil(TB * ceil(V / 64) / 256) at most (checked by the host)
+__global__ __launch_bounds__(256) void k_beam_fused(const float* __restrict__ logits, size_t ldl, int V, int npart, const float* __restrict__ pmax,
+                                                    const float* __restrict__ psum, int first, int stop_token, float* __restrict__ scores,
+                                                    float* __restrict__ seq_len, unsigned char* __restrict__ stopped, int* __restrict__ next_tok,
+                                                    int* __restrict__ src_row) {
+    constexpr int FCAP = 1024, SCAP = 512;
+    __shared__ float red[8];
+    __shared__ int redi[8];
+    __shared__ float rowred[4][TB];
+    __shared__ float s_m[TB], s_lsum[TB], s_sum[TB], s_sc[TB], s_len[TB];
+    __shared__ int s_st[TB];
+    __shared__ float fcv[FCAP];
+    __shared__ int fci[FCAP];
+    __shared__ int surv[SCAP];
+    __shared__ int fcount, scount;
+    __shared__ float sel_v[TB];
+    __shared__ int sel_i[TB];
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int nrows = first ? 1 : TB;
+    const int nblk = (V + 63) >> 6;
+    // 1. every partial of the sample's rows is requested up front (entry i = tid + 256 e: row i / nblk, block i % nblk) — one round trip
+    //    instead of two dependent ones per row — and the row statistics m = max_j pmax, sum = sum_j psum exp(pmax - m) come from registers
+    const int total = nrows * nblk;
+    float pm[PER], ps[PER];
+#pragma unroll
+    for (int e = 0; e < PER; e++) {
+        const int i = tid + 256 * e;
+        const int b = min(i, total - 1) / nblk, j = min(i, total - 1) - b * nblk;
+        const size_t at = (size_t)(s * TB + b) * npart + j;
+        const float a = pmax[at], c = psum[at];
+        pm[e] = i < total ? a : -INFINITY;
+        ps[e] = i < total ? c : 0.f;
+    }
+    float lm[TB];
+#pragma unroll
+    for (int b = 0; b < TB; b++) lm[b] = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < PER; e++) {
+        const int b = min(tid + 256 * e, total - 1) / nblk;
+#pragma unroll
+        for (int q = 0; q < TB; q++) lm[q] = (q == b) ? fmaxf(lm[q], pm[e]) : lm[q];
+    }
+#pragma unroll
+    for (int b = 0; b < TB; b++) {
+        const float m = wave_max(lm[b]);
+        if (lane == 0) rowred[wv][b] = m;
+    }
+    __syncthreads();
+    float ls[TB];
+#pragma unroll
+    for (int b = 0; b < TB; b++) {
+        lm[b] = fmaxf(fmaxf(rowred[0][b], rowred[1][b]), fmaxf(rowred[2][b], rowred[3][b]));
+        ls[b] = 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < PER; e++) {
+        const int b = min(tid + 256 * e, total - 1) / nblk;
+        float mb = -INFINITY;
+#pragma unroll
+        for (int q = 0; q < TB; q++) mb = (q == b) ? lm[q] : mb;
+        const float t = pm[e] != -INFINITY ? ps[e] * expf(pm[e] - mb) : 0.f;
+#pragma unroll
+        for (int q = 0; q < TB; q++) ls[q] += (q == b) ? t : 0.f;
+    }
+#pragma unroll
+    for (int b = 0; b < TB; b++) {
+        const float t = wave_sum(ls[b]);
+        if (lane == 0) rowred[wv][b] = t;
+    }
+    __syncthreads();
+    if (tid < nrows) {
+        const int b = tid;
+        const float t = (rowred[0][b] + rowred[1][b]) + (rowred[2][b] + rowred[3][b]);
+        const bool st = !first && stopped[s * TB + b];
+        float mb = -INFINITY;
+#pragma unroll
+        for (int q = 0; q < TB; q++) mb = (q == b) ? lm[q] : mb;
+        s_m[b] = mb; s_sum[b] = t; s_lsum[b] = logf(t); s_st[b] = st;
+        s_sc[b] = first ? 0.f : scores[s * TB + b];
+        s_len[b] = first ? 1.f : (seq_len[s * TB + b] + (st ? 0.f : 1.f));
+    }
+    if (tid == 0) { fcount = 0; scount = 0; }
+    __syncthreads();
+    // cheap image of a candidate's value (monotone in the logit), and the exact value (base.py:96-101)
+    auto key_of = [&](int b, int v, float x) -> float {
+        if (s_st[b]) return v == 0 ? (first ? 0.f : (s_sc[b] + 0.f) / s_len[b]) : -INFINITY;
+        const float d = (x - s_m[b]) - s_lsum[b];
+        return first ? d : (s_sc[b] + d) * (1.0f / s_len[b]);
+    };
+    auto val_of = [&](int b, int v, float x) -> float {
+        if (s_st[b]) return v == 0 ? (first ? 0.f : (s_sc[b] + 0.f) / s_len[b]) : -INFINITY;
+        const float lp = logf(expf(x - s_m[b]) / s_sum[b]);
+        return first ? lp : (s_sc[b] + lp) / s_len[b];
+    };
+    // 2. bound of every (row, block): key of the block maximum (a stopped row: only token 0, i.e. block 0)
+    float bk[PER];
+    float tmax = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < PER; e++) {
+        const int i = tid + 256 * e;
+        const int b = min(i, total - 1) / nblk, j = min(i, total - 1) - b * nblk;
+        const float k = s_st[b] ? (j == 0 ? key_of(b, 0, 0.f) : -INFINITY) : key_of(b, 1, pm[e]);
+        bk[e] = i < total ? k : -INFINITY;
+        tmax = fmaxf(tmax, bk[e]);
+    }
+    float thr = -INFINITY;
+    for (int k = 0; k < TB; k++) {
+        float bv = wave_max(tmax);
+        if (lane == 0) red[(k & 1) * 4 + wv] = bv;
+        __syncthreads();
+        thr = fmaxf(fmaxf(red[(k & 1) * 4], red[(k & 1) * 4 + 1]), fmaxf(red[(k & 1) * 4 + 2], red[(k & 1) * 4 + 3]));
+        if (tmax == thr) tmax = -INFINITY;            // equal maxima leave together: the bound only gets lower (still valid)
+    }
+    // 3. surviving blocks -> LDS list
+#pragma unroll
+    for (int e = 0; e < PER; e++) {
+        if (bk[e] > -INFINITY && bk[e] + 1e-3f >= thr) {
+            const int pos = atomicAdd(&scount, 1);
+            if (pos < SCAP) surv[pos] = tid + 256 * e;
+        }
+    }
+    __syncthreads();
+    const int ns = scount;
+    bool ok = ns <= SCAP;
+    if (ok) {       // 4. one wave per surviving block: its 64 logits, exact values of the candidates within 1e-3 of the bound
+        for (int q = wv; q < ns; q += 4) {
+            const int i = surv[q], b = i / nblk, j = i - b * nblk, v = j * 64 + lane;
+            if (v < V) {
+                const float x = s_st[b] ? 0.f : logits[(size_t)(s * TB + b) * ldl + v];
+                const float key = key_of(b, v, x);
+                if (key > -INFINITY && key + 1e-3f >= thr) {
+                    const int pos = atomicAdd(&fcount, 1);
+                    if (pos < FCAP) { fcv[pos] = val_of(b, v, x); fci[pos] = b * V + v; }
+                }
+            }
+        }
+        __syncthreads();
+        ok = fcount <= FCAP;
+    }
+    if (!ok) {
+        // block-uniform overflow path (degenerate inputs, e.g. all logits equal): TB rounds of a full scan, each picking the best candidate
+        // that comes strictly after the previous pick in the (value descending, flat index ascending) order.  Slow and exact.
+        float pv = INFINITY;
+        int pi = -1;
+        for (int k = 0; k < TB; k++) {
+            float bv = -INFINITY;
+            int bi = 0x7fffffff;
+            for (int b = 0; b < nrows; b++)
+                for (int v = tid; v < V; v += 256) {
+                    const float x = s_st[b] ? 0.f : logits[(size_t)(s * TB + b) * ldl + v];
+                    const float val = val_of(b, v, x);
+                    const int idx = b * V + v;
+                    if ((pi < 0 || cand_better(pv, pi, val, idx)) && cand_better(val, idx, bv, bi)) { bv = val; bi = idx; }
+                }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float ov = __shfl_xor(bv, o, 64);
+                const int oi = __shfl_xor(bi, o, 64);
+                if (cand_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+            }
+            if (lane == 0) { red[(k & 1) * 4 + wv] = bv; redi[(k & 1) * 4 + wv] = bi; }
+            __syncthreads();
+            bv = red[(k & 1) * 4]; bi = redi[(k & 1) * 4];
+#pragma unroll
+            for (int w = 1; w < 4; w++) {
+                const float ov = red[(k & 1) * 4 + w];
+                const int oi = redi[(k & 1) * 4 + w];
+                if (cand_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+            }
+            pv = bv; pi = bi;
+            if (tid == 0) { sel_v[k] = bi != 0x7fffffff ? bv : -INFINITY; sel_i[k] = bi; }
+        }
+        __syncthreads();
+    }
+    const int n = ok ? fcount : 0;
+    for (int k = 0; ok && k < TB; k++) {      // 5. TB rounds of block arg-max over the list (ties -> lowest flat index)
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+        for (int c = tid; c < n; c += 256)
+            if (fci[c] != 0x7fffffff && cand_better(fcv[c], fci[c], bv, bi)) { bv = fcv[c]; bi = fci[c]; }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(bv, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            if (cand_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+        }
+        if (lane == 0) { red[(k & 1) * 4 + wv] = bv; redi[(k & 1) * 4 + wv] = bi; }
+        __syncthreads();
+        bv = red[(k & 1) * 4]; bi = redi[(k & 1) * 4];
+#pragma unroll
+        for (int w = 1; w < 4; w++) {
+            const float ov = red[(k & 1) * 4 + w];
+            const int oi = redi[(k & 1) * 4 + w];
+            if (cand_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+        }
+        for (int c = tid; c < n; c += 256)
+            if (fci[c] == bi) fci[c] = 0x7fffffff;
+        if (tid == 0) { sel_v[k] = bi != 0x7fffffff ? bv : -INFINITY; sel_i[k] = bi; }
+        __syncthreads();
+    }
+    if (tid < TB) {      // 6. gather / update state (base.py:86-119), as k_beam_final
+        const int idx = sel_i[tid];
+        const int b = idx / V, v = idx % V;
+        float nl, nsc;
+        int hs;
+        if (first) { nl = 1.f; nsc = sel_v[tid]; hs = 0; }
+        else {
+            nl = s_len[b];                          // = seq_len[b] + (stopped ? 0 : 1), read before any state was written
+            nsc = sel_v[tid] * nl;                  // scores = scores_sum_average * seq_lengths (base.py:114)
+            hs = s_st[b];
+        }
+        hs |= (v == stop_token) ? 1 : 0;
+        next_tok[s * TB + tid] = v;
+        src_row[s * TB + tid] = b;
+        scores[s * TB + tid] = nsc;
+        seq_len[s * TB + tid] = nl;
+        stopped[s * TB + tid] = (unsigned char)hs;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t CC_API(cc_beam_ws_bytes)(int32_t S, int32_t beam, int32_t V) {
+    (void)V;
+    if (S <= 0 || beam <= 0 || beam > BEAM_MAX) return CC_ERR_SHAPE;
+    return (int64_t)S * beam * 2 * sizeof(float) + (int64_t)S * BEAM_CHUNKS * beam * (sizeof(float) + sizeof(int)) + 512;
+}
+
+int CC_API(cc_beam_step_p)(int32_t S, int32_t beam, int32_t V, const float* logits, int64_t ldl, const float* lpart, int32_t npart, float temperature,
+                   int32_t first, int32_t stop_token, float* scores, float* seq_lengths, uint8_t* has_stopped, int32_t* next_tokens,
+                   int32_t* src_rows, void* ws, void* stream);
+
+int CC_API(cc_beam_step)(int32_t S, int32_t beam, int32_t V, const float* logits, int64_t ldl, float temperature, int32_t first, int32_t stop_token,
+                 float* scores, float* seq_lengths, uint8_t* has_stopped, int32_t* next_tokens, int32_t* src_rows, void* ws, void* stream) {
+    return CC_API(cc_beam_step_p)(S, beam, V, logits, ldl, nullptr, 0, temperature, first, stop_token, scores, seq_lengths, has_stopped, next_tokens,
+                                  src_rows, ws, stream);
+}
+
+int CC_API(cc_beam_step_p)(int32_t S, int32_t beam, int32_t V, const float* logits, int64_t ldl, const float* lpart, int32_t npart, float temperature,
+                   int32_t first, int32_t stop_token, float* scores, float* seq_lengths, uint8_t* has_stopped, int32_t* next_tokens,
+                   int32_t* src_rows, void* ws, void* stream) {
+    if (S <= 0 || beam <= 0 || beam > BEAM_MAX || V <= 0 || !logits || ldl < V || !scores || !seq_lengths || !has_stopped || !next_tokens ||
+        !src_rows || !ws || (lpart && npart * 64 < V))
+        return CC_ERR_ARG;
+    hipStream_t st = S_(stream);
+    // partials from the lm_head epilogue (cc_decode_fwd_p), temperature 1: the whole update in one launch (k_beam_fused)
+    constexpr int FUSED_VMAX = 51200;      // the fused kernel's per-thread register image of the partials is sized for vocabularies up to this
+    if (lpart && (temperature <= 0.f || temperature == 1.0f) && (beam <= 5 || beam == 8) && V <= FUSED_VMAX) {
+        const float* pmax = lpart;
+        const float* psum = lpart + (size_t)S * beam * npart;
+#define BEAM_FUSED(TB) hipLaunchKernelGGL((k_beam_fused<TB, (TB * (FUSED_VMAX / 64) + 255) / 256>), dim3(S), dim3(256), 0, st, logits, (size_t)ldl, V, npart, pmax, psum, first, stop_token, scores, seq_lengths, has_stopped, next_tokens, src_rows)
+        switch (beam) {
+            case 1: BEAM_FUSED(1); break;
+            case 2: BEAM_FUSED(2); break;
+            case 3: BEAM_FUSED(3); break;
+            case 4: BEAM_FUSED(4); break;
+            case 5: BEAM_FUSED(5); break;
+            default: BEAM_FUSED(8); break;
+        }
+#undef BEAM_FUSED
+        return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
+    }
+    const float inv_temp = 1.0f / (temperature > 0.f ? temperature : 1.0f);   // base.py:83
+    float* rs = static_cast<float*>(ws);
+    float* pval = rs + (size_t)S * beam * 2;
+    int* pidx = reinterpret_cast<int*>(pval + (size_t)S * BEAM_CHUNKS * beam);
+    // step 0 reads only row 0 of every sample's block of `beam` rows, but computing all rows' statistics is harmless and uniform
+    if ((ldl & 3) || ((uintptr_t)logits & 15))
+        hipLaunchKernelGGL(k_beam_rowstats<false>, dim3(S * beam), dim3(512), 0, st, logits, (size_t)ldl, V, inv_temp, rs);
+    else
+        hipLaunchKernelGGL(k_beam_rowstats<true>, dim3(S * beam), dim3(512), 0, st, logits, (size_t)ldl, V, inv_temp, rs);
+#define BEAM_PARTIAL(TB) hipLaunchKernelGGL(k_beam_partial<TB>, dim3(S, BEAM_CHUNKS), dim3(256), 0, st, logits, (size_t)ldl, beam, V, inv_temp, first, rs, scores, seq_lengths, has_stopped, pval, pidx)
+    switch (beam) {
+        case 1: BEAM_PARTIAL(1); break;
+        case 2: BEAM_PARTIAL(2); break;
+        case 3: BEAM_PARTIAL(3); break;
+        case 4: BEAM_PARTIAL(4); break;
+        case 5: BEAM_PARTIAL(5); break;
+        case 8: BEAM_PARTIAL(8); break;
+        default: BEAM_PARTIAL(0); break;
+    }
+#undef BEAM_PARTIAL
+    hipLaunchKernelGGL(k_beam_final, dim3(S), dim3(64), 0, st, beam, V, first, stop_token, pval, pidx, scores, seq_lengths, has_stopped, next_tokens,
+                       src_rows);
+    return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
+}
+
+}  // extern "C"

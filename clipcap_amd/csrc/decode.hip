@@ -1,5 +1,6 @@
 // KV-cached caption decode for gfx950: replaces the reference's full GPT-2 re-forward per generated token
-// (clipcap/inference/base.py:81) with an O(ctx) step, plus the device-side beam-search update of base.py:84-119.
+// (clipcap/inference/base.py:81) with an O(ctx) step, plus the bookkeeping between two beam steps (k_beam_advance; the beam update
+// itself is beam.hip).
 // Decode is HBM-bound (every weight byte is read once per step); the GEMMs reuse gemm.hip.h, attention over the
 // cache is one wave per (row, head, new position).
 #include "../../include/clipcap_hip.h"
@@ -472,548 +473,6 @@ __global__ __launch_bounds__(256) void k_beam_advance(int beam, int D, const flo
     for (int c = tid; c < (D >> 2); c += 256) reinterpret_cast<float4*>(x_out + (size_t)r * D)[c] = w[c];
 }
 
-// ---- beam step (base.py:84-119) in three small kernels so that all CUs take part --------------------------------
-//   k_beam_rowstats : one block per (sample, beam row): max and sum(exp) of logits/temperature
-//   k_beam_partial  : grid (sample, chunk): top-`beam` of the length-normalised candidate scores inside one slice of the
-//                     flattened beam*V candidate space (thread-local insertion lists + block-wide selection)
-//   k_beam_final    : one block per sample merges the chunk winners, then gathers / updates scores, lengths, stopped flags
-// Ties resolve to the lowest flat index b*V + v.
-constexpr int BEAM_MAX = 16;
-constexpr int BEAM_CHUNKS = 16;
-
-__device__ __forceinline__ bool cand_better(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
-
-template <bool VEC>   // VEC: rows are 16-B aligned (ldl % 4 == 0, aligned base) -> float4 loads
-__global__ __launch_bounds__(512) void k_beam_rowstats(const float* __restrict__ logits, size_t ldl, int V, float inv_temp, float* __restrict__ rs) {
-    // one pass: every thread keeps a running (max, sum of exp(x - max)) pair, rescaling the sum when its max moves; pairs are merged
-    // the same way across lanes and waves (the logits matrix, 64 MB at 320 x 50257, is read once instead of twice)
-    __shared__ float redm[8], reds[8];
-    const int row = blockIdx.x, tid = threadIdx.x;
-    const float* lg = logits + (size_t)row * ldl;
-    const int V4 = VEC ? (V >> 2) : 0;
-    float m = -INFINITY, sum = 0.f;
-    auto add4 = [&](float a, float b, float c, float d) {
-        const float mx = fmaxf(fmaxf(a, b), fmaxf(c, d));
-        if (mx > m) { sum *= expf(m - mx); m = mx; }              // expf(-inf) = 0 on the first group
-        sum += expf(a - m) + expf(b - m) + expf(c - m) + expf(d - m);
-    };
-    for (int v = tid; v < V4; v += 512) {
-        const float4 x = reinterpret_cast<const float4*>(lg)[v];
-        add4(x.x * inv_temp, x.y * inv_temp, x.z * inv_temp, x.w * inv_temp);
-    }
-    for (int v = V4 * 4 + tid; v < V; v += 512) {
-        const float x = lg[v] * inv_temp;
-        if (x > m) { sum *= expf(m - x); m = x; }
-        sum += expf(x - m);
-    }
-    auto merge = [&](float om, float os) {
-        const float mx = fmaxf(m, om);
-        if (mx == -INFINITY) return;                               // both empty
-        sum = sum * expf(m - mx) + os * expf(om - mx);
-        m = mx;
-    };
-    for (int o = 32; o > 0; o >>= 1) {
-        const float om = __shfl_xor(m, o, 64), os = __shfl_xor(sum, o, 64);
-        merge(om, os);
-    }
-    if ((tid & 63) == 0) { redm[tid >> 6] = m; reds[tid >> 6] = sum; }
-    __syncthreads();
-    if (tid == 0) {
-        m = redm[0]; sum = reds[0];
-        for (int i = 1; i < 8; i++) merge(redm[i], reds[i]);
-        rs[2 * row] = m;
-        rs[2 * row + 1] = sum;
-    }
-}
-
-// block-wide selection of the `beam` best of ncand (value, index) candidates held in LDS; results in sel_v / sel_i
-__device__ __forceinline__ void select_top(float* cval, int* cidx, int ncand, int beam, float* red, int* redi, float* sel_v, int* sel_i, int tid,
-                                           int nthreads) {
-    for (int k = 0; k < beam; k++) {
-        float bv = -INFINITY;
-        int bi = 0x7fffffff, bp = -1;
-        for (int c = tid; c < ncand; c += nthreads)
-            if (cidx[c] != 0x7fffffff && (bp < 0 || cand_better(cval[c], cidx[c], bv, bi))) { bv = cval[c]; bi = cidx[c]; bp = c; }
-        red[tid] = bv; redi[tid] = bp;
-        __syncthreads();
-        for (int o = nthreads >> 1; o > 0; o >>= 1) {
-            if (tid < o) {
-                const int pa = redi[tid], pb = redi[tid + o];
-                if (pb >= 0 && (pa < 0 || cand_better(red[tid + o], cidx[pb], red[tid], cidx[pa]))) { red[tid] = red[tid + o]; redi[tid] = pb; }
-            }
-            __syncthreads();
-        }
-        if (tid == 0) {
-            const int pos = redi[0];
-            if (pos >= 0) { sel_v[k] = cval[pos]; sel_i[k] = cidx[pos]; cidx[pos] = 0x7fffffff; }
-            else { sel_v[k] = -INFINITY; sel_i[k] = 0x7fffffff; }
-        }
-        __syncthreads();
-    }
-}
-
-// TB = compile-time beam width (0: run-time width, lists in scratch memory — the slow fallback for beam > 8).
-// Each candidate's exact value needs expf + divide + logf (the reference's softmax().log() arithmetic); almost all of the 250 k
-// candidates lose against the thread's current worst kept value, so a cheap bound (x t - m - log(sum), equal up to ~1e-6) with a
-// 1e-3 margin decides whether the exact value is evaluated at all.
-template <int TB>
-__global__ __launch_bounds__(256) void k_beam_partial(const float* __restrict__ logits, size_t ldl, int beam_rt, int V, float inv_temp, int first,
-                                                      const float* __restrict__ rs, const float* __restrict__ scores,
-                                                      const float* __restrict__ seq_len, const unsigned char* __restrict__ stopped,
-                                                      float* __restrict__ pval, int* __restrict__ pidx) {
-    __shared__ float red[256];
-    __shared__ int redi[256];
-    __shared__ float cval[TB > 0 ? 1 : 256 * BEAM_MAX];          // candidate arrays: run-time-width fallback only
-    __shared__ int cidx[TB > 0 ? 1 : 256 * BEAM_MAX];
-    __shared__ float sel_v[BEAM_MAX];
-    __shared__ int sel_i[BEAM_MAX];
-    constexpr int LB = TB > 0 ? TB : BEAM_MAX;
-    const int beam = TB > 0 ? TB : beam_rt;
-    const int s = blockIdx.x, ch = blockIdx.y, tid = threadIdx.x;
-    const int nrows = first ? 1 : beam;
-    const int total = nrows * V;
-    const int per = (total + BEAM_CHUNKS - 1) / BEAM_CHUNKS;
-    const int lo = ch * per, hi = min(total, lo + per);
-    const float* lg = logits + (size_t)s * beam * ldl;
-    // a chunk (total / 16 candidates) spans at most two beam rows when V >= per; handled generally by walking row segments.
-    // scan(f): f(idx, v, seg, raw logit) for every candidate of the chunk, SU logits fetched per thread before any is looked at
-    struct Seg { bool st; float m, sum, lsum, sc, inv_len, len; };
-    auto scan = [&](auto&& f) {
-        for (int b = lo / V; b < nrows && b * V < hi; b++) {
-            const int seg_lo = max(lo, b * V), seg_hi = min(hi, (b + 1) * V);
-            Seg g;
-            g.st = !first && stopped[s * beam + b];
-            g.m = rs[2 * (s * beam + b)]; g.sum = rs[2 * (s * beam + b) + 1];
-            g.lsum = logf(g.sum);
-            g.sc = first ? 0.f : scores[s * beam + b];
-            g.len = first ? 1.f : (seq_len[s * beam + b] + (g.st ? 0.f : 1.f));
-            g.inv_len = 1.0f / g.len;
-            const float* row = lg + (size_t)b * ldl - (size_t)b * V;      // row[idx] = lg[b * ldl + (idx - b V)]
-            constexpr int SU = 8;
-            for (int idx0 = seg_lo + tid; idx0 < seg_hi; idx0 += 256 * SU) {
-                float xs[SU];
-#pragma unroll
-                for (int u = 0; u < SU; u++) xs[u] = g.st ? 0.f : row[min(idx0 + u * 256, seg_hi - 1)];
-#pragma unroll
-                for (int u = 0; u < SU; u++) {
-                    const int idx = idx0 + u * 256;
-                    if (idx < seg_hi) f(idx, idx - b * V, g, xs[u]);
-                }
-            }
-        }
-    };
-    // cheap image of a candidate's value: exact for stopped beams (base.py:96-101: only token 0 continues a stopped beam), within
-    // ~1e-6 of the reference's softmax().log() arithmetic otherwise (x t - m - log(sum) instead of log(exp(x t - m) / sum))
-    auto key_of = [&](int v, const Seg& g, float xraw) -> float {
-        if (g.st) return v == 0 ? (first ? 0.f : (g.sc + 0.f) / g.len) : -INFINITY;
-        const float x = xraw * inv_temp - g.m;
-        return first ? (x - g.lsum) : (g.sc + (x - g.lsum)) * g.inv_len;
-    };
-    auto val_of = [&](int v, const Seg& g, float xraw) -> float {
-        if (g.st) return v == 0 ? (first ? 0.f : (g.sc + 0.f) / g.len) : -INFINITY;
-        const float lp = logf(expf(xraw * inv_temp - g.m) / g.sum);                                           // softmax().log()
-        return first ? lp : (g.sc + lp) / g.len;                                                               // base.py:99-101
-    };
-    const int lane = tid & 63, wv = tid >> 6;
-    bool done = false;
-    if constexpr (TB > 0) {
-        // Two passes instead of a sorted list per thread (with per-thread lists some lane of a wave inserts in almost every iteration,
-        // so every wave ran the ~100-instruction exact-value + insertion path for all of its candidates):
-        //   1. thread maxima of the cheap key; the TB-th largest thread maximum is a lower bound of the chunk's TB-th best value;
-        //   2. only candidates within 1e-3 of that bound get the exact value and go to a small LDS list (a handful per block);
-        //   3. TB rounds of block arg-max over the list (ties -> lowest flat index).
-        constexpr int FCAP = 1024;
-        __shared__ float fcv[FCAP];
-        __shared__ int fci[FCAP];
-        __shared__ int fcount;
-        float tmax = -INFINITY;
-        scan([&](int, int v, const Seg& g, float xraw) { tmax = fmaxf(tmax, key_of(v, g, xraw)); });
-        float thr = -INFINITY;
-        if (tid == 0) fcount = 0;
-        for (int k = 0; k < TB; k++) {
-            float bv = tmax;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) bv = fmaxf(bv, __shfl_xor(bv, o, 64));
-            if (lane == 0) red[(k & 1) * 4 + wv] = bv;
-            __syncthreads();
-            thr = fmaxf(fmaxf(red[(k & 1) * 4], red[(k & 1) * 4 + 1]), fmaxf(red[(k & 1) * 4 + 2], red[(k & 1) * 4 + 3]));
-            if (tmax == thr) tmax = -INFINITY;            // equal maxima leave together: the bound only gets lower (still valid)
-        }
-        scan([&](int idx, int v, const Seg& g, float xraw) {
-            const float key = key_of(v, g, xraw);
-            if (key > -INFINITY && key + 1e-3f >= thr) {
-                const int pos = atomicAdd(&fcount, 1);
-                if (pos < FCAP) { fcv[pos] = val_of(v, g, xraw); fci[pos] = idx; }
-            }
-        });
-        __syncthreads();
-        const int n = fcount;
-        if (n <= FCAP) {
-            for (int k = 0; k < TB; k++) {
-                float bv = -INFINITY;
-                int bi = 0x7fffffff;
-                for (int c = tid; c < n; c += 256)
-                    if (fci[c] != 0x7fffffff && cand_better(fcv[c], fci[c], bv, bi)) { bv = fcv[c]; bi = fci[c]; }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const float ov = __shfl_xor(bv, o, 64);
-                    const int oi = __shfl_xor(bi, o, 64);
-                    if (cand_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-                }
-                if (lane == 0) { red[(k & 1) * 4 + wv] = bv; redi[(k & 1) * 4 + wv] = bi; }
-                __syncthreads();
-                bv = red[(k & 1) * 4]; bi = redi[(k & 1) * 4];
-#pragma unroll
-                for (int w = 1; w < 4; w++) {
-                    const float ov = red[(k & 1) * 4 + w];
-                    const int oi = redi[(k & 1) * 4 + w];
-                    if (cand_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-                }
-                for (int c = tid; c < n; c += 256)
-                    if (fci[c] == bi) fci[c] = 0x7fffffff;                  // flat indices are unique: one owner; visible after the next barrier
-                if (tid == 0) { sel_v[k] = bi != 0x7fffffff ? bv : -INFINITY; sel_i[k] = bi; }
-                __syncthreads();
-            }
-            done = true;
-        }
-    }
-    if (!done) {
-        // sorted insertion list per thread: any width (TB = 0: run-time width), and the overflow path of the list above (e.g. all logits equal)
-        float lv[LB];
-        int li[LB];
-#pragma unroll
-        for (int k = 0; k < LB; k++) { lv[k] = -INFINITY; li[k] = 0x7fffffff; }
-        scan([&](int idx, int v, const Seg& g, float xraw) {
-            if (!g.st) {
-                const float worst = TB > 0 ? lv[LB - 1] : lv[beam - 1];
-                if (key_of(v, g, xraw) + 1e-3f < worst) return;
-            }
-            const float val = val_of(v, g, xraw);
-            if constexpr (TB > 0) {
-                if (cand_better(val, idx, lv[LB - 1], li[LB - 1])) {
-                    lv[LB - 1] = val; li[LB - 1] = idx;
-#pragma unroll
-                    for (int k = LB - 1; k > 0; k--) {
-                        if (cand_better(lv[k], li[k], lv[k - 1], li[k - 1])) {
-                            const float tv = lv[k]; lv[k] = lv[k - 1]; lv[k - 1] = tv;
-                            const int ti = li[k]; li[k] = li[k - 1]; li[k - 1] = ti;
-                        }
-                    }
-                }
-            } else {
-                if (cand_better(val, idx, lv[beam - 1], li[beam - 1])) {
-                    int k = beam - 1;
-                    while (k > 0 && cand_better(val, idx, lv[k - 1], li[k - 1])) { lv[k] = lv[k - 1]; li[k] = li[k - 1]; k--; }
-                    lv[k] = val; li[k] = idx;
-                }
-            }
-        });
-        if constexpr (TB > 0) {
-            // every thread's list is sorted, so the block's next best is the best list HEAD: wave arg-max by shuffles, the four wave
-            // winners meet in LDS (one barrier per round), the owner pops its list
-            for (int k = 0; k < TB; k++) {
-                float bv = lv[0];
-                int bi = li[0];
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const float ov = __shfl_xor(bv, o, 64);
-                    const int oi = __shfl_xor(bi, o, 64);
-                    if (cand_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-                }
-                if (lane == 0) { red[(k & 1) * 4 + wv] = bv; redi[(k & 1) * 4 + wv] = bi; }
-                __syncthreads();
-                bv = red[(k & 1) * 4]; bi = redi[(k & 1) * 4];
-#pragma unroll
-                for (int w = 1; w < 4; w++) {
-                    const float ov = red[(k & 1) * 4 + w];
-                    const int oi = redi[(k & 1) * 4 + w];
-                    if (cand_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-                }
-                if (li[0] == bi && bi != 0x7fffffff) {              // flat indices are unique: exactly one owner
-#pragma unroll
-                    for (int q = 0; q + 1 < LB; q++) { lv[q] = lv[q + 1]; li[q] = li[q + 1]; }
-                    lv[LB - 1] = -INFINITY; li[LB - 1] = 0x7fffffff;
-                }
-                if (tid == 0) { sel_v[k] = bi != 0x7fffffff ? bv : -INFINITY; sel_i[k] = bi; }
-            }
-            __syncthreads();
-        } else {
-            for (int k = 0; k < beam; k++) { cval[tid * beam + k] = lv[k]; cidx[tid * beam + k] = li[k]; }
-            __syncthreads();
-            select_top(cval, cidx, 256 * beam, beam, red, redi, sel_v, sel_i, tid, 256);
-        }
-    }
-    if (tid < beam) {
-        pval[((size_t)s * BEAM_CHUNKS + ch) * beam + tid] = sel_v[tid];
-        pidx[((size_t)s * BEAM_CHUNKS + ch) * beam + tid] = sel_i[tid];
-    }
-}
-
-__global__ __launch_bounds__(64) void k_beam_final(int beam, int V, int first, int stop_token, const float* __restrict__ pval,
-                                                   const int* __restrict__ pidx, float* __restrict__ scores, float* __restrict__ seq_len,
-                                                   unsigned char* __restrict__ stopped, int* __restrict__ next_tok, int* __restrict__ src_row) {
-    __shared__ float red[64];
-    __shared__ int redi[64];
-    __shared__ float cval[BEAM_CHUNKS * BEAM_MAX];
-    __shared__ int cidx[BEAM_CHUNKS * BEAM_MAX];
-    __shared__ float sel_v[BEAM_MAX];
-    __shared__ int sel_i[BEAM_MAX];
-    __shared__ float ns_[BEAM_MAX], nl_[BEAM_MAX];
-    __shared__ int hs_[BEAM_MAX];
-    const int s = blockIdx.x, tid = threadIdx.x;
-    const int ncand = BEAM_CHUNKS * beam;
-    for (int c = tid; c < ncand; c += 64) { cval[c] = pval[(size_t)s * ncand + c]; cidx[c] = pidx[(size_t)s * ncand + c]; }
-    __syncthreads();
-    select_top(cval, cidx, ncand, beam, red, redi, sel_v, sel_i, tid, 64);
-    if (tid < beam) {      // gather / update state (base.py:86-119)
-        const int idx = sel_i[tid];
-        const int b = idx / V, v = idx % V;
-        if (first) { nl_[tid] = 1.f; ns_[tid] = sel_v[tid]; hs_[tid] = 0; }
-        else {
-            const bool st = stopped[s * beam + b];
-            nl_[tid] = seq_len[s * beam + b] + (st ? 0.f : 1.f);
-            ns_[tid] = sel_v[tid] * nl_[tid];      // scores = scores_sum_average * seq_lengths (base.py:114)
-            hs_[tid] = st;
-        }
-        hs_[tid] |= (v == stop_token) ? 1 : 0;
-        next_tok[s * beam + tid] = v;
-        src_row[s * beam + tid] = b;
-    }
-    __syncthreads();
-    if (tid < beam) {
-        scores[s * beam + tid] = ns_[tid];
-        seq_len[s * beam + tid] = nl_[tid];
-        stopped[s * beam + tid] = (unsigned char)hs_[tid];
-    }
-}
-
-// ---- beam step in ONE kernel, fed by the lm_head epilogue's partials (gemm.hip.h EpiLogits) ----------------------------------
-// One block per sample.  The row statistics (max, sum of exp) come from the per-(row, 64-column block) partials — no pass over the
-// logits; every 64-column block is bounded by the key of its maximum, the TB-th largest bound is a lower bound of the sample's TB-th
-// best candidate, and only the blocks whose bound reaches it (a handful) are read from the logits matrix at all.  Same arithmetic
-// (softmax().log() as the reference writes it), same tie rule (lowest flat index) and same state update as the three-kernel path,
-// which stays as the fallback for temperature != 1, run-time beam widths and candidate-list overflow (e.g. all logits equal).
-template <int TB, int PER>      // PER: (row, block) partials per thread = ceil(TB * ceil(V / 64) / 256) at most (checked by the host)
-__global__ __launch_bounds__(256) void k_beam_fused(const float* __restrict__ logits, size_t ldl, int V, int npart, const float* __restrict__ pmax,
-                                                    const float* __restrict__ psum, int first, int stop_token, float* __restrict__ scores,
-                                                    float* __restrict__ seq_len, unsigned char* __restrict__ stopped, int* __restrict__ next_tok,
-                                                    int* __restrict__ src_row) {
-    constexpr int FCAP = 1024, SCAP = 512;
-    __shared__ float red[8];
-    __shared__ int redi[8];
-    __shared__ float rowred[4][TB];
-    __shared__ float s_m[TB], s_lsum[TB], s_sum[TB], s_sc[TB], s_len[TB];
-    __shared__ int s_st[TB];
-    __shared__ float fcv[FCAP];
-    __shared__ int fci[FCAP];
-    __shared__ int surv[SCAP];
-    __shared__ int fcount, scount;
-    __shared__ float sel_v[TB];
-    __shared__ int sel_i[TB];
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int nrows = first ? 1 : TB;
-    const int nblk = (V + 63) >> 6;
-    // 1. every partial of the sample's rows is requested up front (entry i = tid + 256 e: row i / nblk, block i % nblk) — one round trip
-    //    instead of two dependent ones per row — and the row statistics m = max_j pmax, sum = sum_j psum exp(pmax - m) come from registers
-    const int total = nrows * nblk;
-    float pm[PER], ps[PER];
-#pragma unroll
-    for (int e = 0; e < PER; e++) {
-        const int i = tid + 256 * e;
-        const int b = min(i, total - 1) / nblk, j = min(i, total - 1) - b * nblk;
-        const size_t at = (size_t)(s * TB + b) * npart + j;
-        const float a = pmax[at], c = psum[at];
-        pm[e] = i < total ? a : -INFINITY;
-        ps[e] = i < total ? c : 0.f;
-    }
-    float lm[TB];
-#pragma unroll
-    for (int b = 0; b < TB; b++) lm[b] = -INFINITY;
-#pragma unroll
-    for (int e = 0; e < PER; e++) {
-        const int b = min(tid + 256 * e, total - 1) / nblk;
-#pragma unroll
-        for (int q = 0; q < TB; q++) lm[q] = (q == b) ? fmaxf(lm[q], pm[e]) : lm[q];
-    }
-#pragma unroll
-    for (int b = 0; b < TB; b++) {
-        const float m = wave_max(lm[b]);
-        if (lane == 0) rowred[wv][b] = m;
-    }
-    __syncthreads();
-    float ls[TB];
-#pragma unroll
-    for (int b = 0; b < TB; b++) {
-        lm[b] = fmaxf(fmaxf(rowred[0][b], rowred[1][b]), fmaxf(rowred[2][b], rowred[3][b]));
-        ls[b] = 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < PER; e++) {
-        const int b = min(tid + 256 * e, total - 1) / nblk;
-        float mb = -INFINITY;
-#pragma unroll
-        for (int q = 0; q < TB; q++) mb = (q == b) ? lm[q] : mb;
-        const float t = pm[e] != -INFINITY ? ps[e] * expf(pm[e] - mb) : 0.f;
-#pragma unroll
-        for (int q = 0; q < TB; q++) ls[q] += (q == b) ? t : 0.f;
-    }
-#pragma unroll
-    for (int b = 0; b < TB; b++) {
-        const float t = wave_sum(ls[b]);
-        if (lane == 0) rowred[wv][b] = t;
-    }
-    __syncthreads();
-    if (tid < nrows) {
-        const int b = tid;
-        const float t = (rowred[0][b] + rowred[1][b]) + (rowred[2][b] + rowred[3][b]);
-        const bool st = !first && stopped[s * TB + b];
-        float mb = -INFINITY;
-#pragma unroll
-        for (int q = 0; q < TB; q++) mb = (q == b) ? lm[q] : mb;
-        s_m[b] = mb; s_sum[b] = t; s_lsum[b] = logf(t); s_st[b] = st;
-        s_sc[b] = first ? 0.f : scores[s * TB + b];
-        s_len[b] = first ? 1.f : (seq_len[s * TB + b] + (st ? 0.f : 1.f));
-    }
-    if (tid == 0) { fcount = 0; scount = 0; }
-    __syncthreads();
-    // cheap image of a candidate's value (monotone in the logit), and the exact value (base.py:96-101)
-    auto key_of = [&](int b, int v, float x) -> float {
-        if (s_st[b]) return v == 0 ? (first ? 0.f : (s_sc[b] + 0.f) / s_len[b]) : -INFINITY;
-        const float d = (x - s_m[b]) - s_lsum[b];
-        return first ? d : (s_sc[b] + d) * (1.0f / s_len[b]);
-    };
-    auto val_of = [&](int b, int v, float x) -> float {
-        if (s_st[b]) return v == 0 ? (first ? 0.f : (s_sc[b] + 0.f) / s_len[b]) : -INFINITY;
-        const float lp = logf(expf(x - s_m[b]) / s_sum[b]);
-        return first ? lp : (s_sc[b] + lp) / s_len[b];
-    };
-    // 2. bound of every (row, block): key of the block maximum (a stopped row: only token 0, i.e. block 0)
-    float bk[PER];
-    float tmax = -INFINITY;
-#pragma unroll
-    for (int e = 0; e < PER; e++) {
-        const int i = tid + 256 * e;
-        const int b = min(i, total - 1) / nblk, j = min(i, total - 1) - b * nblk;
-        const float k = s_st[b] ? (j == 0 ? key_of(b, 0, 0.f) : -INFINITY) : key_of(b, 1, pm[e]);
-        bk[e] = i < total ? k : -INFINITY;
-        tmax = fmaxf(tmax, bk[e]);
-    }
-    float thr = -INFINITY;
-    for (int k = 0; k < TB; k++) {
-        float bv = wave_max(tmax);
-        if (lane == 0) red[(k & 1) * 4 + wv] = bv;
-        __syncthreads();
-        thr = fmaxf(fmaxf(red[(k & 1) * 4], red[(k & 1) * 4 + 1]), fmaxf(red[(k & 1) * 4 + 2], red[(k & 1) * 4 + 3]));
-        if (tmax == thr) tmax = -INFINITY;            // equal maxima leave together: the bound only gets lower (still valid)
-    }
-    // 3. surviving blocks -> LDS list
-#pragma unroll
-    for (int e = 0; e < PER; e++) {
-        if (bk[e] > -INFINITY && bk[e] + 1e-3f >= thr) {
-            const int pos = atomicAdd(&scount, 1);
-            if (pos < SCAP) surv[pos] = tid + 256 * e;
-        }
-    }
-    __syncthreads();
-    const int ns = scount;
-    bool ok = ns <= SCAP;
-    if (ok) {       // 4. one wave per surviving block: its 64 logits, exact values of the candidates within 1e-3 of the bound
-        for (int q = wv; q < ns; q += 4) {
-            const int i = surv[q], b = i / nblk, j = i - b * nblk, v = j * 64 + lane;
-            if (v < V) {
-                const float x = s_st[b] ? 0.f : logits[(size_t)(s * TB + b) * ldl + v];
-                const float key = key_of(b, v, x);
-                if (key > -INFINITY && key + 1e-3f >= thr) {
-                    const int pos = atomicAdd(&fcount, 1);
-                    if (pos < FCAP) { fcv[pos] = val_of(b, v, x); fci[pos] = b * V + v; }
-                }
-            }
-        }
-        __syncthreads();
-        ok = fcount <= FCAP;
-    }
-    if (!ok) {
-        // block-uniform overflow path (degenerate inputs, e.g. all logits equal): TB rounds of a full scan, each picking the best candidate
-        // that comes strictly after the previous pick in the (value descending, flat index ascending) order.  Slow and exact.
-        float pv = INFINITY;
-        int pi = -1;
-        for (int k = 0; k < TB; k++) {
-            float bv = -INFINITY;
-            int bi = 0x7fffffff;
-            for (int b = 0; b < nrows; b++)
-                for (int v = tid; v < V; v += 256) {
-                    const float x = s_st[b] ? 0.f : logits[(size_t)(s * TB + b) * ldl + v];
-                    const float val = val_of(b, v, x);
-                    const int idx = b * V + v;
-                    if ((pi < 0 || cand_better(pv, pi, val, idx)) && cand_better(val, idx, bv, bi)) { bv = val; bi = idx; }
-                }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(bv, o, 64);
-                const int oi = __shfl_xor(bi, o, 64);
-                if (cand_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-            }
-            if (lane == 0) { red[(k & 1) * 4 + wv] = bv; redi[(k & 1) * 4 + wv] = bi; }
-            __syncthreads();
-            bv = red[(k & 1) * 4]; bi = redi[(k & 1) * 4];
-#pragma unroll
-            for (int w = 1; w < 4; w++) {
-                const float ov = red[(k & 1) * 4 + w];
-                const int oi = redi[(k & 1) * 4 + w];
-                if (cand_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-            }
-            pv = bv; pi = bi;
-            if (tid == 0) { sel_v[k] = bi != 0x7fffffff ? bv : -INFINITY; sel_i[k] = bi; }
-        }
-        __syncthreads();
-    }
-    const int n = ok ? fcount : 0;
-    for (int k = 0; ok && k < TB; k++) {      // 5. TB rounds of block arg-max over the list (ties -> lowest flat index)
-        float bv = -INFINITY;
-        int bi = 0x7fffffff;
-        for (int c = tid; c < n; c += 256)
-            if (fci[c] != 0x7fffffff && cand_better(fcv[c], fci[c], bv, bi)) { bv = fcv[c]; bi = fci[c]; }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (cand_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-        }
-        if (lane == 0) { red[(k & 1) * 4 + wv] = bv; redi[(k & 1) * 4 + wv] = bi; }
-        __syncthreads();
-        bv = red[(k & 1) * 4]; bi = redi[(k & 1) * 4];
-#pragma unroll
-        for (int w = 1; w < 4; w++) {
-            const float ov = red[(k & 1) * 4 + w];
-            const int oi = redi[(k & 1) * 4 + w];
-            if (cand_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-        }
-        for (int c = tid; c < n; c += 256)
-            if (fci[c] == bi) fci[c] = 0x7fffffff;
-        if (tid == 0) { sel_v[k] = bi != 0x7fffffff ? bv : -INFINITY; sel_i[k] = bi; }
-        __syncthreads();
-    }
-    if (tid < TB) {      // 6. gather / update state (base.py:86-119), as k_beam_final
-        const int idx = sel_i[tid];
-        const int b = idx / V, v = idx % V;
-        float nl, nsc;
-        int hs;
-        if (first) { nl = 1.f; nsc = sel_v[tid]; hs = 0; }
-        else {
-            nl = s_len[b];                          // = seq_len[b] + (stopped ? 0 : 1), read before any state was written
-            nsc = sel_v[tid] * nl;                  // scores = scores_sum_average * seq_lengths (base.py:114)
-            hs = s_st[b];
-        }
-        hs |= (v == stop_token) ? 1 : 0;
-        next_tok[s * TB + tid] = v;
-        src_row[s * TB + tid] = b;
-        scores[s * TB + tid] = nsc;
-        seq_len[s * TB + tid] = nl;
-        stopped[s * TB + tid] = (unsigned char)hs;
-    }
-}
-
 struct DecWS {
     float *x, *x1;
     act_t *xn, *qkv, *att, *hact, *hf;
@@ -1316,71 +775,6 @@ int CC_API(cc_decode_reorder)(const cc_gpt2_cfg* c, int32_t R_src, int32_t R_dst
     hipLaunchKernelGGL(k_kv_reorder, dim3((int)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, S_(stream),
                        reinterpret_cast<const act_t*>(kv_src), reinterpret_cast<act_t*>(kv_dst), src, R_src,
                        R_dst, ctx, ctx_max, c->D, c->NL * 2);
-    return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
-}
-
-int64_t CC_API(cc_beam_ws_bytes)(int32_t S, int32_t beam, int32_t V) {
-    (void)V;
-    if (S <= 0 || beam <= 0 || beam > BEAM_MAX) return CC_ERR_SHAPE;
-    return (int64_t)S * beam * 2 * sizeof(float) + (int64_t)S * BEAM_CHUNKS * beam * (sizeof(float) + sizeof(int)) + 512;
-}
-
-int CC_API(cc_beam_step_p)(int32_t S, int32_t beam, int32_t V, const float* logits, int64_t ldl, const float* lpart, int32_t npart, float temperature,
-                   int32_t first, int32_t stop_token, float* scores, float* seq_lengths, uint8_t* has_stopped, int32_t* next_tokens,
-                   int32_t* src_rows, void* ws, void* stream);
-
-int CC_API(cc_beam_step)(int32_t S, int32_t beam, int32_t V, const float* logits, int64_t ldl, float temperature, int32_t first, int32_t stop_token,
-                 float* scores, float* seq_lengths, uint8_t* has_stopped, int32_t* next_tokens, int32_t* src_rows, void* ws, void* stream) {
-    return CC_API(cc_beam_step_p)(S, beam, V, logits, ldl, nullptr, 0, temperature, first, stop_token, scores, seq_lengths, has_stopped, next_tokens,
-                                  src_rows, ws, stream);
-}
-
-int CC_API(cc_beam_step_p)(int32_t S, int32_t beam, int32_t V, const float* logits, int64_t ldl, const float* lpart, int32_t npart, float temperature,
-                   int32_t first, int32_t stop_token, float* scores, float* seq_lengths, uint8_t* has_stopped, int32_t* next_tokens,
-                   int32_t* src_rows, void* ws, void* stream) {
-    if (S <= 0 || beam <= 0 || beam > BEAM_MAX || V <= 0 || !logits || ldl < V || !scores || !seq_lengths || !has_stopped || !next_tokens ||
-        !src_rows || !ws || (lpart && npart * 64 < V))
-        return CC_ERR_ARG;
-    hipStream_t st = S_(stream);
-    // partials from the lm_head epilogue (cc_decode_fwd_p), temperature 1: the whole update in one launch (k_beam_fused)
-    constexpr int FUSED_VMAX = 51200;      // the fused kernel's per-thread register image of the partials is sized for vocabularies up to this
-    if (lpart && (temperature <= 0.f || temperature == 1.0f) && (beam <= 5 || beam == 8) && V <= FUSED_VMAX) {
-        const float* pmax = lpart;
-        const float* psum = lpart + (size_t)S * beam * npart;
-#define BEAM_FUSED(TB) hipLaunchKernelGGL((k_beam_fused<TB, (TB * (FUSED_VMAX / 64) + 255) / 256>), dim3(S), dim3(256), 0, st, logits, (size_t)ldl, V, npart, pmax, psum, first, stop_token, scores, seq_lengths, has_stopped, next_tokens, src_rows)
-        switch (beam) {
-            case 1: BEAM_FUSED(1); break;
-            case 2: BEAM_FUSED(2); break;
-            case 3: BEAM_FUSED(3); break;
-            case 4: BEAM_FUSED(4); break;
-            case 5: BEAM_FUSED(5); break;
-            default: BEAM_FUSED(8); break;
-        }
-#undef BEAM_FUSED
-        return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
-    }
-    const float inv_temp = 1.0f / (temperature > 0.f ? temperature : 1.0f);   // base.py:83
-    float* rs = static_cast<float*>(ws);
-    float* pval = rs + (size_t)S * beam * 2;
-    int* pidx = reinterpret_cast<int*>(pval + (size_t)S * BEAM_CHUNKS * beam);
-    // step 0 reads only row 0 of every sample's block of `beam` rows, but computing all rows' statistics is harmless and uniform
-    if ((ldl & 3) || ((uintptr_t)logits & 15))
-        hipLaunchKernelGGL(k_beam_rowstats<false>, dim3(S * beam), dim3(512), 0, st, logits, (size_t)ldl, V, inv_temp, rs);
-    else
-        hipLaunchKernelGGL(k_beam_rowstats<true>, dim3(S * beam), dim3(512), 0, st, logits, (size_t)ldl, V, inv_temp, rs);
-#define BEAM_PARTIAL(TB) hipLaunchKernelGGL(k_beam_partial<TB>, dim3(S, BEAM_CHUNKS), dim3(256), 0, st, logits, (size_t)ldl, beam, V, inv_temp, first, rs, scores, seq_lengths, has_stopped, pval, pidx)
-    switch (beam) {
-        case 1: BEAM_PARTIAL(1); break;
-        case 2: BEAM_PARTIAL(2); break;
-        case 3: BEAM_PARTIAL(3); break;
-        case 4: BEAM_PARTIAL(4); break;
-        case 5: BEAM_PARTIAL(5); break;
-        case 8: BEAM_PARTIAL(8); break;
-        default: BEAM_PARTIAL(0); break;
-    }
-#undef BEAM_PARTIAL
-    hipLaunchKernelGGL(k_beam_final, dim3(S), dim3(64), 0, st, beam, V, first, stop_token, pval, pidx, scores, seq_lengths, has_stopped, next_tokens,
-                       src_rows);
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 

@@ -2100,7 +2100,7 @@ struct EpiLMHeadExp {
 };
 // Decode lm_head: fp32 logits (what the beam / sampling kernels read) + the same per-(row, 64-column block) partials (max, sum of
 // exp(x - max)) from the accumulators, so the beam update needs no pass over the 64 MB logits matrix for its row statistics and can
-// bound every 64-column block by its maximum (decode.hip k_beam_fused).  Columns >= V are stored as computed (the caller's matrix may
+// bound every 64-column block by its maximum (beam.hip k_beam_fused).  Columns >= V are stored as computed (the caller's matrix may
 // be wider) but excluded from the partials.
 struct EpiLogits {
     float* C;

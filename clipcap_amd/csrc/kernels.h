@@ -1,4 +1,4 @@
-// Host-side launchers of the non-GEMM kernels (definitions in kernels.hip / attention.hip / decode.hip).  Internal to the library.
+// Host-side launchers of the non-GEMM kernels (definitions in kernels.hip / attention.hip).  Internal to the library.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -92,10 +92,6 @@ int score_rows(const float* pmax, const float* psum, int npart, const int* keep,
                float* sample_stats, int B, int cap, hipStream_t st);
 int ce_dlogits(act_t* logits, int ld, int V, const int* target, const float* lse, const float* denom, const float* loss_scale, int M,
                hipStream_t st, op16_t* img = nullptr);   // img (bf16x3): write the gradient as the dgrad GEMM's operand image there instead of in place
-// sample.hip: one sampling step per row (temperature, repetition penalty, top-k, top-p, inverse-CDF draw at u[row])
-int sample_rows(const float* logits, int R, int V, int ld, float temperature, int top_k, float top_p, int mode, const long long* hist,
-                int hist_len, int hist_ld, float rep_pen, const float* u, int* next_token, float* probs_out, hipStream_t st, int stop_tok = -1,
-                float len_pen = 1.0f);   // stop_tok >= 0: sentence-length penalty (history tokens whose filtered value == stop id are scaled by len_pen)
 int ce_targets(const long long* tokens, int* target, int* row_map, int B, int cap, int L, int T, hipStream_t st);
 int score_keep(const long long* tokens, int* keep, int n, int ignore_zero, hipStream_t st);   // keep[i] = tokens[i] >= 0 (&& != 0 with ignore_zero)
 // Exponential form of the lm_head outputs (gemm.hip.h EpiLMHead, bf16 build):

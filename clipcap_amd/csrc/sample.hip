@@ -6,7 +6,7 @@
 // float atomics).  Ties at a threshold are kept in index order.  The draw is the inverse CDF in index order at a caller-supplied
 // uniform, so the same (logits, u) always gives the same token; the reference's torch.multinomial stream is not reproducible
 // from outside torch, and parity is on the pre-sampling distribution (probs_out), as SURVEY.md 8(a13) says.
-#include "kernels.h"
+#include "layout.h"
 
 namespace CC_NS {
 
@@ -395,9 +395,10 @@ size_t sample_lds_bytes(int V) {
     return (size_t)SM_NB * 8 + (SM_T / 64 + 2) * 8 + (size_t)SM_NB * 4 + 16 + 2 * (SM_T / 64) * 4 + (size_t)((V + 31) / 32) * 4;
 }
 
+// stop_tok >= 0: sentence-length penalty (history tokens whose filtered value == stop id are scaled by len_pen)
 int sample_rows(const float* logits, int R, int V, int ld, float temperature, int top_k, float top_p, int mode, const long long* hist,
-                int hist_len, int hist_ld, float rep_pen, const float* u, int* next_token, float* probs_out, hipStream_t st, int stop_tok,
-                float len_pen) {
+                int hist_len, int hist_ld, float rep_pen, const float* u, int* next_token, float* probs_out, hipStream_t st, int stop_tok = -1,
+                float len_pen = 1.0f) {
     if (R <= 0) return CC_OK;
     if (V <= 0 || ld < V || (mode != 0 && mode != 1)) return CC_ERR_ARG;
     const size_t sh = sample_lds_bytes(V);
@@ -411,3 +412,25 @@ int sample_rows(const float* logits, int R, int V, int ld, float temperature, in
 }
 
 }  // namespace CC_NS
+
+using namespace CC_NS;
+
+extern "C" {
+
+int CC_API(cc_sample_step)(const float* logits, int32_t R, int32_t V, int32_t ld, float temperature, int32_t top_k, float top_p, int32_t mode,
+                   const int64_t* history, int32_t hist_len, int32_t hist_ld, float repetition_penalty, const float* u, int32_t* next_token,
+                   float* probs_out, void* stream) {
+    if (!logits || !u || !next_token || R < 0) return CC_ERR_ARG;
+    return sample_rows(logits, R, V, ld, temperature, top_k, top_p, mode, reinterpret_cast<const long long*>(history), hist_len, hist_ld,
+                       repetition_penalty, u, next_token, probs_out, S_(stream));
+}
+
+int CC_API(cc_sample_step_lp)(const float* logits, int32_t R, int32_t V, int32_t ld, float temperature, int32_t top_k, float top_p, int32_t mode,
+                      const int64_t* history, int32_t hist_len, int32_t hist_ld, float repetition_penalty, int32_t stop_token,
+                      float length_penalty, const float* u, int32_t* next_token, float* probs_out, void* stream) {
+    if (!logits || !u || !next_token || R < 0) return CC_ERR_ARG;
+    return sample_rows(logits, R, V, ld, temperature, top_k, top_p, mode, reinterpret_cast<const long long*>(history), hist_len, hist_ld,
+                       repetition_penalty, u, next_token, probs_out, S_(stream), stop_token, length_penalty);
+}
+
+}  // extern "C"
