@@ -1,5 +1,5 @@
 // C ABI (include/clipcap_hip.h) — orchestration of the mapper and GPT-2 training/inference passes out of the HIP
-// kernels in gemm.hip.h / kernels.hip / attention.hip.  No state, no allocation, no synchronisation: everything is enqueued on the
+// kernels in gemm.hip.h / kernels.hip / layernorm.hip / reduce.hip / loss.hip / attention.hip.  No state, no allocation, no synchronisation: everything is enqueued on the
 // caller's stream and lives in caller-owned arenas / workspaces.
 #include "../../include/clipcap_hip.h"
 #include "gemm_api.h"
@@ -941,39 +941,9 @@ int CC_API(cc_adamw_step_clip)(float* p32, const float* g32, float* m, float* v,
 
 int64_t CC_API(cc_grad_norm_scratch_floats)(void) { return (int64_t)GRAD_NORM_BLOCKS; }
 
-int CC_API(cc_grad_sqnorm)(const float* g32, int64_t n, float* scratch, float* sumsq, void* stream) {
-    if (!g32 || !scratch || !sumsq || n < 0) return CC_ERR_ARG;
-    return grad_sqnorm(g32, (size_t)n, scratch, sumsq, S_(stream));
-}
-
-int CC_API(cc_grad_clip_coef)(const float* sumsq, float max_norm, float grad_scale, const float* loss_scale, float* clip, void* stream) {
-    if (!sumsq || !clip || !(max_norm >= 0.f)) return CC_ERR_ARG;
-    return grad_clip_coef(sumsq, max_norm, grad_scale, loss_scale, clip, S_(stream));
-}
-
 int CC_API(cc_cast_op16)(const float* src, uint16_t* dst, int64_t n, void* stream) {
     if (!src || !dst || n < 0 || kX3) return CC_ERR_ARG;
     return f32_to_bf16(src, dst, (size_t)n, S_(stream));
-}
-
-int CC_API(cc_grad_wire_pack)(const float* g32, uint16_t* wire, int64_t n, void* stream) {
-    if (!g32 || !wire || n < 0) return CC_ERR_ARG;
-    return wire_pack(g32, wire, (size_t)n, S_(stream));
-}
-
-int CC_API(cc_grad_wire_unpack)(const uint16_t* wire, float* g32, int64_t n, void* stream) {
-    if (!g32 || !wire || n < 0) return CC_ERR_ARG;
-    return wire_unpack(wire, g32, (size_t)n, S_(stream));
-}
-
-int CC_API(cc_grad_nonfinite)(const float* g32, int64_t n, float* found_inf, void* stream) {
-    if (!g32 || !found_inf || n < 0) return CC_ERR_ARG;
-    return grad_nonfinite(g32, (size_t)n, found_inf, S_(stream));
-}
-
-int CC_API(cc_loss_scale_update)(float* state, float* found_inf, float growth, float backoff, int32_t interval, void* stream) {
-    if (!state || !found_inf || growth < 1.f || backoff <= 0.f || backoff > 1.f || interval < 1) return CC_ERR_ARG;
-    return loss_scale_update(state, found_inf, growth, backoff, interval, S_(stream));
 }
 
 int CC_API(cc_gemm_op16_f32)(int32_t al, int32_t bl, const uint16_t* A, int32_t lda, const uint16_t* B, int32_t ldb, int32_t M, int32_t N, int32_t K,

@@ -359,7 +359,7 @@ static int attn_fwd_mfma3_launch(const float* qkv, int B, int S, int H, bool cau
 }
 // ------------------------------------------------------------------------------------------------------------
 // Backward of the same attention as three-term bf16 MFMA products (round 4; S <= 64, head dim 64 / 96): one workgroup per (sample, head),
-// every operand staged ONCE into LDS as a hi plane and a lo plane (the GEMMs' split, kernels.hip::k_x3_split_rows' arithmetic), so that
+// every operand staged ONCE into LDS as a hi plane and a lo plane (the GEMMs' split, common.hip.h::x3_pair8's arithmetic), so that
 // every MFMA fragment is a plain 16-B read (k along the row) or a ds_read_b64_tr_b16 pair (k down the rows).  Phases, a block barrier apart:
 //   0  qkv / dO rows (fp32) -> planes Q, K, V, dO [R][LD]
 //   1  tile jobs: S = Q K^T and dP = dO V^T (fp32 scratch in the P / dS plane area)

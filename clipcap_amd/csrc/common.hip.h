@@ -173,6 +173,36 @@ __device__ __forceinline__ void act_ld8(const act_t* p, float (&f)[8]) { act_unp
 __device__ __forceinline__ void act_st8(act_t* p, const float (&f)[8]) { act_straw8(p, act_pack8(f)); }
 __device__ __forceinline__ void act_st4(act_t* p, float a, float b, float c, float d) { act_straw4(p, act_pack4(a, b, c, d)); }
 
+// ---- bf16x3 operand pairs: x -> hi = bf16(x), lo = bf16(x - hi) (x - hi is exact in fp32), eight or four elements at a time, and their
+// store as one row of an operand image (row3 = the row's 3 K 16-bit elements, c = column): form 0 (A operand) [hi | hi | lo], form 1
+// (B operand) [hi | lo | hi]
+__device__ __forceinline__ void x3_pair8(const float (&f)[8], uint4& hi, uint4& lo) {
+    hi = pack8(f);
+    float h[8], d[8];
+    unpack8(hi, h);
+#pragma unroll
+    for (int e = 0; e < 8; e++) d[e] = f[e] - h[e];
+    lo = pack8(d);
+}
+__device__ __forceinline__ void x3_store(op16_t* row3, int K, int c, int form, const uint4& hi, const uint4& lo) {
+    *reinterpret_cast<uint4*>(row3 + c) = hi;
+    *reinterpret_cast<uint4*>(row3 + K + c) = form ? lo : hi;
+    *reinterpret_cast<uint4*>(row3 + 2 * K + c) = form ? hi : lo;
+}
+__device__ __forceinline__ void x3_pair4(float a, float b, float c, float d, uint2& hi, uint2& lo) {
+    const unsigned h01 = pack2op(a, b), h23 = pack2op(c, d);
+    float a0, a1, a2, a3;
+    unpack2(h01, a0, a1);
+    unpack2(h23, a2, a3);
+    hi = make_uint2(h01, h23);
+    lo = make_uint2(pack2op(a - a0, b - a1), pack2op(c - a2, d - a3));
+}
+__device__ __forceinline__ void x3_store4(op16_t* r3, int K, const uint2& hi, const uint2& lo) {      // form 0; r3 = row3 + c
+    *reinterpret_cast<uint2*>(r3) = hi;
+    *reinterpret_cast<uint2*>(r3 + K) = hi;
+    *reinterpret_cast<uint2*>(r3 + 2 * K) = lo;
+}
+
 // gelu_new (tanh approximation) and its derivative — transformers.activations.NewGELUActivation, in the sigmoid form
 //   0.5 (1 + tanh u) = 1 / (1 + exp(-2u)) = s,   u = k0 (x + k1 x^3)   =>   gelu = x s,   gelu' = s + x s (1 - s) 2 k0 (1 + 3 k1 x^2)
 // evaluated on the hardware exp2 / rcp units (v_exp_f32 / v_rcp_f32, ~1e-7 relative): 5 (8) VALU + 2 transcendental operations per

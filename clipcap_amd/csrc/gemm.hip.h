@@ -1617,7 +1617,7 @@ __device__ __forceinline__ void load_bias8(const float* bias, int col, int Ns, f
 }
 
 // Output store of the 16-bit-activation epilogues.  bf16x3 build, img > 0: C is not an fp32 activation but the [hi | hi | lo] operand IMAGE
-// of the consumer GEMM (rows of 3 * img 16-bit elements, kernels.hip::k_x3_split_rows' layout and arithmetic) — the producer writes it
+// of the consumer GEMM (rows of 3 * img 16-bit elements, common.hip.h::x3_pair8 / x3_store's layout and arithmetic) — the producer writes it
 // directly, 6 B per element, instead of 4 B here + a 4 B read and 6 B write in the split pass.  img == 0 (always, in the 16-bit builds): the
 // plain store.
 __device__ __forceinline__ void epi_store8(act_t* C, int ldc, int row, int col, const float (&v)[8], int img) {

@@ -1,4 +1,5 @@
-// Host-side launchers of the non-GEMM kernels (definitions in kernels.hip / attention.hip).  Internal to the library.
+// Host-side launchers of the non-GEMM kernels (definitions in kernels.hip / layernorm.hip / reduce.hip / loss.hip / attention.hip; the
+// gradient utilities of grads.hip are reached through their entry points only).  Internal to the library.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -7,10 +8,11 @@
 
 namespace CC_NS {
 
+// grid of a grid-stride launch over `total` items: per_block items per block, at most `cap` blocks
+inline dim3 flat_grid(size_t total, int per_block, int cap) { return dim3((unsigned)std::min<size_t>((total + per_block - 1) / per_block, cap)); }
+
 int f32_to_bf16(const float* src, op16_t* dst, size_t n, hipStream_t st);      // 16-bit operand cast (weights)
-int f32_to_act(const float* src, act_t* dst, size_t n, hipStream_t st);
-int wire_pack(const float* src, unsigned short* dst, size_t n, hipStream_t st);        // fp32 -> bf16 gradient wire slice (any n / alignment)
-int wire_unpack(const unsigned short* src, float* dst, size_t n, hipStream_t st);      // and back         // fp32 -> stored-activation type (a copy in the bf16x3 build)
+int f32_to_act(const float* src, act_t* dst, size_t n, hipStream_t st);         // fp32 -> stored-activation type (a copy in the bf16x3 build)
 int slice_f32_to_bf16(const float* src, size_t src_stride, act_t* dst, size_t dst_stride, int len, int B, hipStream_t st);
 int broadcast_rows(float* dst, size_t dst_stride, const float* src, int len, int B, hipStream_t st);
 int add_rows(float* dst, size_t dst_stride, const float* add, int len, int B, hipStream_t st);
@@ -19,6 +21,11 @@ int add_rows(float* dst, size_t dst_stride, const float* add, int len, int B, hi
 // Call, whose `red` is RED_SCRATCH_FLOATS floats of the entry point's workspace; when they need it and it is null: CC_ERR_STATE.
 constexpr size_t RED_SCRATCH_FLOATS = size_t(1) << 20;
 int batch_sum(const float* src, size_t src_stride, float* dst, int len, int B, Call& cx);
+// internal to the reductions (reduce.hip; ln_bwd in layernorm.hip folds its parameter-gradient partials the same way): partials
+// part[y][s][j] (y < groups, S slices x n columns) are added onto out[y * k + j / m][j % m] in the fixed order k_fold_partials states
+struct FoldOut { float* p[32]; int m; int k; };
+inline float* red_scratch(const Call& cx, size_t floats) { return floats <= RED_SCRATCH_FLOATS ? cx.red : nullptr; }
+int fold_partials(const float* part, int S, int n, int groups, const FoldOut& o, hipStream_t st);
 int copy_rows(const float* src, size_t src_stride, float* dst, size_t dst_stride, int len, int B, hipStream_t st);
 
 int transpose_bf16(const op16_t* src, op16_t* dst, int R, int C, hipStream_t st);
@@ -107,8 +114,8 @@ int lm_scale_rows(const act_t* hf, const float* fac, act_t* out, int D, int M, h
 int adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, float wd, int step, float gscale,
           const float* loss_scale, const float* found_inf, hipStream_t st, op16_t* w16 = nullptr,   // w16: also store the 16-bit copy of the updated parameters
           const float* clip = nullptr);            // clip (device, nullable): the gradient is also multiplied by clip[0] (grad_clip_coef)
-int grad_nonfinite(const float* g, size_t n, float* found_inf, hipStream_t st);
-// sumsq[0] += sum of g[i]^2, i < n (n % 4 == 0), bit for bit the same from run to run and from box to box: the grid depends on n alone.
+// grad_sqnorm (grads.hip, behind cc_grad_sqnorm): sumsq[0] += sum of g[i]^2, i < n (n % 4 == 0), bit for bit the same from run to run
+// and from box to box: the grid depends on n alone.
 // scratch: GRAD_NORM_BLOCKS floats of device scratch for this call.  The order, with n4 = n / 4 float4 groups,
 // nb = min(ceil(n4 / GRAD_NORM_THREADS), GRAD_NORM_BLOCKS) blocks and S = nb * GRAD_NORM_THREADS:
 //   * group i contributes q_i = (x*x + y*y) + (z*z + w*w) of its four elements (at most 3 roundings on an element's way in);
@@ -121,10 +128,6 @@ int grad_nonfinite(const float* g, size_t n, float* found_inf, hipStream_t st);
 constexpr int GRAD_NORM_BLOCKS = 1024;
 constexpr int GRAD_NORM_THREADS = 256;
 constexpr int GRAD_NORM_ACC = 4;
-int grad_sqnorm(const float* g, size_t n, float* scratch, float* sumsq, hipStream_t st);
-// clip[1] = sqrt(sumsq[0]) * grad_scale / (loss_scale ? loss_scale[0] : 1), clip[0] = min(1, max_norm / (clip[1] + 1e-6)); a norm that
-// is not finite gives clip[0] = NaN; max_norm = +inf gives exactly 1.0f
-int grad_clip_coef(const float* sumsq, float max_norm, float grad_scale, const float* loss_scale, float* clip, hipStream_t st);
 
 // bf16x3 build: GEMM operand pairs (common.hip.h).  dst[r][0:3K] = form 0 (A operand): [hi | hi | lo], form 1 (B operand): [hi | lo | hi]
 // of src[r][0:K] (fp32, row stride lds); hi = bf16(x), lo = bf16(x - hi).  K % 8 == 0.
@@ -138,6 +141,5 @@ struct X3SplitBatch {
     void add(const float* s, op16_t* d, int R, int C, int tr, int form) { it[n++] = Item{s, d, R, C, tr, form}; }
 };
 int x3_split_multi(const X3SplitBatch& b, hipStream_t st);
-int loss_scale_update(float* state, float* found_inf, float growth, float backoff, int interval, hipStream_t st);
 
 }  // namespace CC_NS

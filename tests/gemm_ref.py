@@ -1,7 +1,8 @@
 """float64 reference of what the GEMM wrappers of clipcap_amd/csrc/gemm_api.h compute, and the error bounds the GPU tests hold them to
 (tests/test_gpu_gemm_epilogues.py).  Plain torch, no GPU needed; tests/test_gemm_ref.py pins this module itself.
 
-Everything is written from the definitions in clipcap_amd/csrc/common.hip.h and kernels.hip, not from what the kernels return:
+Everything is written from the definitions in clipcap_amd/csrc/common.hip.h (x3_pair8 / x3_store, gelu_new, the dropout mask), not from what the
+kernels return:
   * split-bf16 operands: hi = bf16(x), lo = bf16(x - hi) (x - hi is exact in fp32); A image [hi | hi | lo], B image [hi | lo | hi];
   * gelu_new(x) = x s, s = 1 / (1 + exp(-2 k0 (x + k1 x^3))); gelu_new'(x) = s + x s (1 - s) 2 k0 (1 + 3 k1 x^2);
   * residual dropout: out = res + m * scale * (acc + bias), m the keep flag, scale = 1 / (1 - p) (as a float32, like make_drop).

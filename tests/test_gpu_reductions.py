@@ -1,6 +1,6 @@
-"""The deterministic cross-block reductions of the backward passes (kernels.hip: ln_bwd's dgamma / dbeta / dcol, colsum_bf16,
-colsum_bf16_multi, batch_sum, all folded by k_fold_partials), each called on its own through its C-ABI test hook and compared per
-column with a float64 reference of the same sum.
+"""The deterministic cross-block reductions of the backward passes (layernorm.hip: ln_bwd's dgamma / dbeta / dcol; reduce.hip:
+colsum_bf16, colsum_bf16_multi, batch_sum; all folded by reduce.hip's k_fold_partials), each called on its own through its C-ABI test
+hook and compared per column with a float64 reference of the same sum.
 
 What the reference sums is what the kernel sums: 16-bit inputs upcast exactly, dcol = the column sums of the ROUNDED 16-bit dx16 the
 kernel wrote.  Every output starts nonzero (the kernels accumulate, on the single-block path and on the fold path alike), every summed
@@ -9,7 +9,7 @@ each call (a slot the fold reads but no block wrote this call poisons the result
 
 Bound, per column: |kernel - ref| <= c * 2^-24 * (|out0| + sum |t|).  A term t reaches the output through at most c fp32 roundings,
 so this is the classical bound gamma_c of recursive / tree summation (Higham, Accuracy and Stability of Numerical Algorithms, 4.2),
-with c the longest serial chain of the launch as kernels.hip computes it (chain_* below mirrors that launch arithmetic):
+with c the longest serial chain of the launch as layernorm.hip / reduce.hip compute it (chain_* below mirrors that launch arithmetic):
   * the per-thread serial sum: a wave's rows (ln_bwd), a thread's rows of its slice (colsum: rows_per_slice / 32), a thread's four
     accumulators (batch_sum: ceil(per / 4) + 2);
   * the in-block sum: the NW wave rows of ln_bwd's LDS buffer, the 32 rows of colsum's;
@@ -89,7 +89,7 @@ def _fold_chain(S):
     return 0 if S <= 1 else 4 + _cdiv(S, 256) + 16
 
 
-# ---- launch arithmetic of kernels.hip (the grid each wrapper picks), for the chain lengths and to assert which path a shape takes ----
+# ---- launch arithmetic of layernorm.hip / reduce.hip (the grid each wrapper picks), for the chain lengths and to assert which path a shape takes ----
 def ln_launch(rows, D, dcol):
     nw = 8 if 16 * D * 4 <= 65536 else 4
     nvec = 3 if dcol else 2
@@ -277,6 +277,29 @@ def test_colsum_multi(n, M, N, ws):
     for i in range(n):
         x = Xs[i][:, :N].double()
         _check("colsum_multi", outs[i], out0s[i].double() + x.sum(0), out0s[i].double().abs() + x.abs().sum(0), chain_colsum(M, N, n))
+
+
+@pytest.mark.parametrize("op", ["bf16", "fp16"])
+@pytest.mark.parametrize("M,N", [(33, 8), (2049, 72), (70001, 8)])
+def test_colsum_multi_of_one_is_the_single_form(op, M, N, ws):
+    """cc_colsum_multi with n = 1 and cc_colsum_bf16 give the same bits (the single form is a batch of one: the same slices, partial rows
+    and fold): one slice with ragged rows; several slices with the fold and a ragged column block; more than 256 slices (two chunks of
+    the fold, ragged last slice).  Both outputs start from the same seeded non-zero values, so the += is part of what must agree."""
+    code, dt = OPS[op]
+    ld = N + 8
+    X, out0 = _colsum_case(dt, M, N, ld, 77 * M + N)
+    single, multi = out0.clone(), out0.clone()
+    assert (out0 != 0).all()
+    assert _lib().cc_colsum_bf16(code, _p(X), ld, M, N, _p(single), _p(_poison(ws)), _st()) == 0
+    xa, oa = (C.c_void_p * 1)(X.data_ptr()), (C.c_void_p * 1)(multi.data_ptr())
+    assert _lib().cc_colsum_multi(code, xa, oa, 1, ld, M, N, _p(_poison(ws)), _st()) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(single.view(torch.int32), multi.view(torch.int32))
+    assert (single != out0).all()
+
+
+def test_colsum_multi_of_one_shapes_reach_the_paths():
+    assert colsum_launch(33, 8) == (1, 64) and colsum_launch(2049, 72)[0] == 9 and colsum_launch(70001, 8)[0] > 256
 
 
 def test_colsum_multi_shapes_fold():
