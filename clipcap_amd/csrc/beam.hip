@@ -29,7 +29,7 @@ __global__ __launch_bounds__(512) void k_beam_rowstats(const float* __restrict__
     auto add4 = [&](float a, float b, float c, float d) {
         const float mx = fmaxf(fmaxf(a, b), fmaxf(c, d));
         if (mx > m) { sum *= expf(m - mx); m = mx; }              // expf(-inf) = 0 on the first group
-        sum += expf(a - m) + expf(b - m) + expf(c - m) + expf(d - m);
+        if (m > -INFINITY) sum += expf(a - m) + expf(b - m) + expf(c - m) + expf(d - m);   // banned tokens (-inf, constrain.hip) first: no -inf - -inf
     };
     for (int v = tid; v < V4; v += 512) {
         const float4 x = reinterpret_cast<const float4*>(lg)[v];
@@ -38,7 +38,7 @@ __global__ __launch_bounds__(512) void k_beam_rowstats(const float* __restrict__
     for (int v = V4 * 4 + tid; v < V; v += 512) {
         const float x = lg[v] * inv_temp;
         if (x > m) { sum *= expf(m - x); m = x; }
-        sum += expf(x - m);
+        if (m > -INFINITY) sum += expf(x - m);
     }
     auto merge = [&](float om, float os) {
         const float mx = fmaxf(m, om);

@@ -933,6 +933,35 @@ def beam_step(logits: torch.Tensor, samples: int, beam: int, temperature: float,
     return nt, sr
 
 
+def constrain_logits(logits: torch.Tensor, *, lpart: Optional[tuple] = None, history: Optional[torch.Tensor] = None, hist_len: int = 0,
+                     no_repeat_ngram: int = 0, ban_token: int = -1, suppress: Optional[torch.Tensor] = None,
+                     skip_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Token bans on one step's fp32 ``logits`` (R, V), IN PLACE, before beam_step / sample_step (cc_logits_constrain): a banned token's
+    logit becomes -inf, i.e. it is removed before the softmax.  Banned in row r: what repeating would complete an n-gram of size
+    ``no_repeat_ngram`` in ``history[r, :hist_len]`` (int32 or int64 (R, >= hist_len), oldest first; inference.utils.banned_tokens states
+    the rule), ``ban_token`` (-1: none) and every id of ``suppress`` (int32 device tensor).  Rows with a non-zero ``skip_rows`` entry (uint8
+    (R,), e.g. has_stopped) are left alone.  ``lpart``: DecodeSession.lpart of the forward that produced these logits — the partials of the
+    64-column blocks that received a ban are recomputed, so that beam_step(..., lpart) stays exact.  A view with a row stride is fine.
+    Returns ``logits``."""
+    dev = logits.device
+    R, V = logits.shape
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1
+    he = 4
+    if history is not None:
+        assert history.dtype in (torch.int32, torch.int64) and history.shape[0] == R and history.stride(1) == 1
+        he = history.element_size()
+    if suppress is not None:
+        assert suppress.dtype == torch.int32 and suppress.is_contiguous()
+    if skip_rows is not None:
+        assert skip_rows.dtype == torch.uint8 and skip_rows.numel() == R and skip_rows.is_contiguous()
+    check(_lib.lib().cc_logits_constrain(_p(logits), R, V, logits.stride(0), _p(lpart[0]) if lpart is not None else None,
+                                        lpart[1] if lpart is not None else 0, _p(history) if history is not None else None, he,
+                                        history.stride(0) if history is not None else 0, int(hist_len), int(no_repeat_ngram), int(ban_token),
+                                        _p(suppress) if suppress is not None else None, suppress.numel() if suppress is not None else 0,
+                                        _p(skip_rows) if skip_rows is not None else None, _stream(dev)), "cc_logits_constrain")
+    return logits
+
+
 def sample_step(logits: torch.Tensor, u: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 0.0, mode: int = 0,
                 history: torch.Tensor = None, hist_len: int = 0, repetition_penalty: float = 1.0, return_probs: bool = False,
                 length_penalty_stop: int = -1, length_penalty: float = 1.0):

@@ -55,3 +55,45 @@ def nucleus_distribution(logits: torch.Tensor, top_p: float = 0.8, top_k=None) -
     kept = (cum <= cut) * p
     kept = kept / kept.sum(dim=-1, keepdim=True)
     return torch.zeros_like(logits).scatter(-1, idx, kept.to(logits.dtype))
+
+
+# ---- constrained decoding (not in the reference: no_repeat_ngram_size / min_length / suppress_tokens of the decoders) ----------------
+# A ban sets the token's logit to -inf BEFORE the softmax, the convention of top_k_top_p_filtering above: the banned mass is
+# renormalised over the allowed tokens.  The device applies the bans in cc_logits_constrain; these two are its CPU side.
+
+MAX_SUPPRESS_TOKENS = 1023      # the suppress list cc_logits_constrain accepts
+
+
+def banned_tokens(history, no_repeat_ngram_size: int) -> set:
+    """Tokens the no-repeat rule forbids as the next token of ``history`` (generated ids, oldest first; a sequence or a 1-D tensor):
+    with g = no_repeat_ngram_size and n = len(history), h[i+g-1] for every i in [0, n-g] whose g-1 tokens h[i : i+g-1] equal the last
+    g-1 tokens h[n-g+1 : n] — appending such a token would repeat an n-gram of the history.  g = 1 bans every token of the history,
+    n < g bans nothing, 0 turns the rule off.  Plain Python: the statement of the rule that the device kernel is tested against."""
+    h = [int(t) for t in (history.tolist() if hasattr(history, "tolist") else history)]
+    g, n = int(no_repeat_ngram_size), len(h)
+    if g <= 0 or n < g:
+        return set()
+    tail = h[n - g + 1:]
+    return {h[i + g - 1] for i in range(n - g + 1) if h[i:i + g - 1] == tail}
+
+
+def validate_constraints(vocab_size: int, stop_token: int, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None) -> list:
+    """Checks the three decoding constraints against a vocabulary of ``vocab_size`` ids and returns the suppress list as plain ints
+    ([] for None).  ValueError for a negative size or length, an id outside [0, vocab_size), more than MAX_SUPPRESS_TOKENS ids, and a
+    suppress list that holds the stop token while min_length == 0: such a decode could never stop.  Pure: touches no device."""
+    g, m = int(no_repeat_ngram_size), int(min_length)
+    if g < 0:
+        raise ValueError(f"no_repeat_ngram_size must be >= 0, got {no_repeat_ngram_size}")
+    if m < 0:
+        raise ValueError(f"min_length must be >= 0, got {min_length}")
+    ids = [] if suppress_tokens is None else [int(t) for t in (suppress_tokens.tolist() if hasattr(suppress_tokens, "tolist") else suppress_tokens)]
+    if len(ids) > MAX_SUPPRESS_TOKENS:
+        raise ValueError(f"suppress_tokens holds {len(ids)} ids; at most {MAX_SUPPRESS_TOKENS} are supported")
+    bad = [t for t in ids if not 0 <= t < vocab_size]
+    if bad:
+        raise ValueError(f"suppress_tokens ids outside [0, {vocab_size}): {bad[:8]}")
+    if (m > 0 or stop_token in ids) and not 0 <= int(stop_token) < vocab_size:
+        raise ValueError(f"stop token {stop_token} is outside [0, {vocab_size})")
+    if m == 0 and int(stop_token) in ids:
+        raise ValueError(f"suppress_tokens contains the stop token {stop_token} and min_length is 0: this decode can never stop")
+    return ids

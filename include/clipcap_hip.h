@@ -66,7 +66,7 @@ extern "C" {
  * cc_gemm_dact, cc_gemm_f32, cc_gemm_wgrad_split, and the attention test hooks cc_attention_fwd_x, cc_attention_bwd_x; operand mode ADDED: CC_OP_BF16X3.  Round 6 (still 3): the default-off decode experiments
  * (cc_decode_image*, cc_decode_xt_image*, cc_decode_fwd_x, cc_decode_ws_check, cc_decode_last_path) moved to include/clipcap_hip_lab.h —
  * the lab library exports them, the product library does not.  ADDED since (still 3: no existing entry point changed): cc_lmhead_score,
- * cc_grad_norm_scratch_floats, cc_grad_sqnorm, cc_grad_clip_coef, cc_adamw_step_clip. */
+ * cc_grad_norm_scratch_floats, cc_grad_sqnorm, cc_grad_clip_coef, cc_adamw_step_clip, cc_logits_constrain. */
 #define CC_ABI_VERSION 3
 int cc_abi_version(void);
 
@@ -263,6 +263,26 @@ int cc_beam_step_p(int32_t S, int32_t beam, int32_t V, const float* logits, int6
                    float temperature, int32_t first, int32_t stop_token, float* scores, float* seq_lengths, uint8_t* has_stopped,
                    int32_t* next_tokens, int32_t* src_rows, void* ws, void* stream);
 int64_t cc_beam_ws_bytes(int32_t S, int32_t beam, int32_t V);
+/* Constrained decoding (since 3, added without a version bump): token bans on one step's logits [R][ldl], in place, BEFORE the beam update
+ * or the sampling step.  A ban sets the token's logit to -inf, i.e. before the softmax (the convention of the reference's
+ * top_k_top_p_filtering, utils.py:5-30): its mass is renormalised over the allowed tokens.  The banned set of row r:
+ *   - no_repeat_ngram = g >= 1 over the row's history h[0:n) (history + r * hist_stride elements of hist_elem_bytes = 4 (int32) or 8
+ *     (int64), n = hist_len, oldest first): for every i in [0, n-g] with h[i : i+g-1] == h[n-g+1 : n], h[i+g-1]; g == 1 bans the whole
+ *     history, n < g bans nothing, 0 = off (history may then be NULL);
+ *   - ban_token (-1 = none): the host's min_length rule passes the stop token while a caption is too short;
+ *   - suppress[0 : n_suppress) (device int32), at every call.
+ *   Ids outside [0, V) in the history or the list ban nothing (a history id takes part in the compare with its own value).  skip_rows (nullable, uint8 [R]): rows with a non-zero entry are left alone
+ *   (beam search passes has_stopped: the update ignores a stopped beam's logits).
+ * lpart / npart (lpart NULL: none): the softmax partials cc_decode_fwd_p wrote for these R rows (pmax [R][npart] then psum [R][npart], one
+ *   entry per 64-column block of the V real columns).  The partials of exactly the blocks that received a ban are recomputed from the
+ *   banned logits (a block without a finite entry: pmax = -inf, psum = 0), so cc_beam_step_p's one-launch update, which bounds every
+ *   block by its pmax and takes the row's softmax denominator from psum, sees consistent inputs.  Blocks without a ban, the padding
+ *   columns [V, ldl) and skipped rows are not written.
+ * One launch, one workgroup per row; no launch at all when nothing can be banned.  Limits: hist_len <= 1024, n_suppress <= 1023,
+ * V <= 2097152 (CC_ERR_SHAPE); npart * 64 >= V, hist_elem_bytes 4 or 8, hist_stride >= hist_len, -1 <= ban_token < V (CC_ERR_ARG). */
+int cc_logits_constrain(float* logits, int32_t R, int32_t V, int64_t ldl, float* lpart, int32_t npart, const void* history,
+                        int32_t hist_elem_bytes, int64_t hist_stride, int32_t hist_len, int32_t no_repeat_ngram, int32_t ban_token,
+                        const int32_t* suppress, int32_t n_suppress, const uint8_t* skip_rows, void* stream);
 /* gathers wte rows for next tokens: out fp32 [R, D] (base.py:117) */
 int cc_embed_tokens(const cc_gpt2_cfg* cfg, int32_t R, const float* w32, const int32_t* tokens, float* out, void* stream);
 /* its gradient: dwte fp32 [Vp, D] += scatter of dout fp32 [R, D] by tokens (rows sharing an id accumulate).  The non-deterministic form:
