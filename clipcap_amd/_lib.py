@@ -137,6 +137,7 @@ SIGNATURES = {
     "cc_gemm_tile_mode": (_I, [_I]),
     "cc_gemm_skinny_mode": (_I, [_I]),
     "cc_decode_mode": (_I, [_I]),
+    "cc_decode_attention": (_I, [_GC, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, C.POINTER(_I), _P]),
     "cc_gemm_op16_f32": (_I, [_I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P]),
     "cc_layernorm_fwd": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "cc_attention_fwd": (_I, [_I, _P, _I, _I, _I, _I, _I, _P, _P, _P]),

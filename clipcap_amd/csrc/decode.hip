@@ -530,6 +530,50 @@ void launch_group_union(int group, int ngroups, hipStream_t st, const int* row_m
     }
 }
 
+// The attention step of one decode layer: which form runs (decode_attn_plan) and its launches (decode_attn_run).  decode_fwd_impl and the
+// test hook cc_decode_attention both go through these two, so the hook launches what the product launches.
+struct AttnPlan {
+    int grp_cap;       // entries per group in the union list: whole passes of 128
+    size_t grp_shm;    // k_decode_attn_group's LDS bytes
+    bool grp_attn;     // beam-group form (k_group_union + k_decode_attn_group); false: k_decode_attn
+    float scale;
+};
+// CC_ERR_SHAPE: the per-row kernel's LDS (p | srow | red per wave) does not fit — refused for every form, before anything is launched
+int decode_attn_plan(int R, int Tn, int hd, int pos0, int ctx_max, int group, size_t grp_ents, AttnPlan& a) {
+    if ((size_t)4 * (2 * ctx_max + 8 * hd) * sizeof(float) > 64 * 1024) return CC_ERR_SHAPE;
+    a.scale = 1.0f / sqrtf((float)hd);
+    // beam-group attention (k_decode_attn_group): single-position steps of `group` consecutive rows that share ancestry (a perf hint only)
+    a.grp_cap = (group * (pos0 + 1) + 127) & ~127;          // entries per group, whole passes of 128
+    a.grp_shm = ((size_t)a.grp_cap * 8 + 96 + (size_t)8 * group * 64) * sizeof(float);
+    a.grp_attn = (cc_shared::g_decode_mode & 1) && Tn == 1 && group >= 2 && group <= 8 && hd == 64 && a.grp_shm <= 64 * 1024 &&
+                 (size_t)(R / group) * a.grp_cap <= grp_ents;
+    return CC_OK;
+}
+// append: the kernels store the new K / V slices and read them from qkv (else the caller's c_attn epilogue already has); build_union: this
+// call also builds the groups' union list (once per position: the first layer that runs the group form)
+int decode_attn_run(const AttnPlan& a, hipStream_t st, const DecWS& w, const act_t* qkv, act_t* kc, act_t* vc, const int* row_map, act_t* out, int R, int Tn,
+                    int H, int hd, int pos0, int ctx_max, int group, bool append, bool build_union) {
+    if (a.grp_attn) {
+        const int ng = R / group, app = append ? 1 : 0;
+        if (build_union) launch_group_union(group, ng, st, row_map, w, pos0, ctx_max, a.grp_cap, app, nullptr, 0);
+#define CC_GRP(G_)                                                                                                                            \
+    case G_:                                                                                                                                  \
+        hipLaunchKernelGGL((k_decode_attn_group<G_>), dim3(ng * H), dim3(256), a.grp_shm, st, qkv, kc, vc, w.grp_ent, w.grp_cnt, out, H, pos0,    \
+                           ctx_max, a.scale, a.grp_cap, app);                                                                                 \
+        break;
+        switch (group) { CC_GRP(2) CC_GRP(3) CC_GRP(4) CC_GRP(5) CC_GRP(6) CC_GRP(7) CC_GRP(8) default: return CC_ERR_ARG; }
+#undef CC_GRP
+    } else {
+        const int nw = R * H * Tn;
+        const size_t shm = (size_t)4 * (2 * ctx_max + 8 * hd) * sizeof(float);
+        if (!append)
+            hipLaunchKernelGGL(k_decode_attn<false>, dim3((nw + 3) / 4), dim3(256), shm, st, qkv, kc, vc, row_map, out, R, Tn, H, hd, pos0, ctx_max, a.scale);
+        else
+            hipLaunchKernelGGL(k_decode_attn<true>, dim3((nw + 3) / 4), dim3(256), shm, st, qkv, kc, vc, row_map, out, R, Tn, H, hd, pos0, ctx_max, a.scale);
+    }
+    return CC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -615,10 +659,11 @@ static int decode_fwd_impl(const cc_gpt2_cfg* c, int32_t R, int32_t Tn, int32_t 
     if (!gpt2_dims_ok(c) || R <= 0 || Tn <= 0 || pos0 < 0 || !w32 || !w16 || !x || !kv || !ws || !logits) return CC_ERR_ARG;
     const int Ns = std::min(c->Vp, rup(c->V, 8));
     if (pos0 + Tn > ctx_max || pos0 + Tn > c->NPOS || ldl < Ns || (ldl & 3) || ldl > 0x7fffffff) return CC_ERR_SHAPE;
-    if ((size_t)4 * (2 * ctx_max + 8 * (c->D / c->H)) * sizeof(float) > 64 * 1024) return CC_ERR_SHAPE;
     hipStream_t st = S_(stream);
     DecWS w;
     dec_carve(c, R, Tn, ws, w);
+    AttnPlan ap;
+    CC_TRY(decode_attn_plan(R, Tn, c->D / c->H, pos0, ctx_max, group, w.grp_ents, ap));
     Call cx{st, nullptr, w.x3, w.x3_bytes};
     const Gpt2Off o(c);
     const int D = c->D, M = R * Tn, H = c->H, hd = D / H;
@@ -632,12 +677,8 @@ static int decode_fwd_impl(const cc_gpt2_cfg* c, int32_t R, int32_t Tn, int32_t 
     }
     const size_t cache_layer = (size_t)2 * R * ctx_max * D;
     const uint16_t* w16t = W16(w16, o.total);   // transposed Conv1D weights (cc_gpt2_sync_weights): forward GEMMs are NT
-    const float scale = 1.0f / sqrtf((float)hd);
-    // beam-group attention (k_decode_attn_group): single-position steps of `group` consecutive rows that share ancestry (a perf hint only)
-    const int grp_cap = (group * (pos0 + 1) + 127) & ~127;          // entries per group, whole passes of 128
-    const size_t grp_shm = ((size_t)grp_cap * 8 + 96 + (size_t)8 * group * 64) * sizeof(float);
-    const bool grp_attn = (cc_shared::g_decode_mode & 1) && Tn == 1 && group >= 2 && group <= 8 && hd == 64 && grp_shm <= 64 * 1024 &&
-                          (size_t)(R / group) * grp_cap <= w.grp_ents;
+    const int grp_cap = ap.grp_cap;
+    const bool grp_attn = ap.grp_attn;
     bool xn_ready = one;
     bool hf_ready = false;
     int l_first = 0;
@@ -697,24 +738,7 @@ static int decode_fwd_impl(const cc_gpt2_cfg* c, int32_t R, int32_t Tn, int32_t 
         if (f_qkv) { fq.kcache = kc; fq.vcache = vc; fq.Tn = Tn; fq.pos0 = pos0; fq.ctx_max = ctx_max; }
         fq.bimg = bimg ? bimg + y.aw : nullptr;
         CC_TRY(gemm_nt_skinny(w.xn, D, W16(w16t, y.aw), D, M, 3 * D, D, w32 + y.ab, 0, nullptr, nullptr, w.qkv, 3 * D, w.scratch, w.scratch_bytes, cx, &fq));
-        if (grp_attn) {
-            const int ng = R / group, app = f_qkv ? 0 : 1;
-            if (l == 0) launch_group_union(group, ng, st, row_map, w, pos0, ctx_max, grp_cap, app, nullptr, 0);
-#define CC_GRP(G_)                                                                                                                            \
-    case G_:                                                                                                                                  \
-        hipLaunchKernelGGL((k_decode_attn_group<G_>), dim3(ng * H), dim3(256), grp_shm, st, w.qkv, kc, vc, w.grp_ent, w.grp_cnt, w.att, H, pos0,  \
-                           ctx_max, scale, grp_cap, app);                                                                                     \
-        break;
-            switch (group) { CC_GRP(2) CC_GRP(3) CC_GRP(4) CC_GRP(5) CC_GRP(6) CC_GRP(7) CC_GRP(8) default: return CC_ERR_ARG; }
-#undef CC_GRP
-        } else {
-            const int nw = R * H * Tn;
-            const size_t shm = (size_t)4 * (2 * ctx_max + 8 * hd) * sizeof(float);
-            if (f_qkv)
-                hipLaunchKernelGGL(k_decode_attn<false>, dim3((nw + 3) / 4), dim3(256), shm, st, w.qkv, kc, vc, row_map, w.att, R, Tn, H, hd, pos0, ctx_max, scale);
-            else
-                hipLaunchKernelGGL(k_decode_attn<true>, dim3((nw + 3) / 4), dim3(256), shm, st, w.qkv, kc, vc, row_map, w.att, R, Tn, H, hd, pos0, ctx_max, scale);
-        }
+        CC_TRY(decode_attn_run(ap, st, w, w.qkv, kc, vc, row_map, w.att, R, Tn, H, hd, pos0, ctx_max, group, !f_qkv, l == 0));
         // attn.c_proj + residual (+ fused ln_2)
         const bool f_d = gemm_nt_skinny_can_fuse(M, D, D, w.scratch_bytes) && gemm_nt_skinny_can_fuse(M, D, 4 * D, w.scratch_bytes);
         SkinnyFuse f2;
@@ -766,6 +790,25 @@ int CC_API(cc_decode_ws_check)(const cc_gpt2_cfg* c, int32_t R, int32_t Tn, cons
     return (e | e2) ? CC_ERR_STATE : CC_OK;
 }
 #endif
+
+// test hook: the attention step of one layer on caller buffers, through the product's own dispatch (decode_attn_plan / decode_attn_run)
+int CC_API(cc_decode_attention)(const cc_gpt2_cfg* c, int32_t R, int32_t Tn, int32_t pos0, int32_t ctx_max, const uint16_t* qkv, uint16_t* kv_layer,
+                        const int32_t* row_map, int32_t group, int32_t append, void* ws, uint16_t* out, int32_t* path, void* stream) {
+    if (group < 1 || (R > 0 && R % group)) return CC_ERR_ARG;
+    if (!gpt2_dims_ok(c) || R <= 0 || Tn <= 0 || pos0 < 0 || !qkv || !kv_layer || !ws || !out || (append != 0 && append != 1)) return CC_ERR_ARG;
+    if (pos0 + Tn > ctx_max || pos0 + Tn > c->NPOS) return CC_ERR_SHAPE;
+    DecWS w;
+    dec_carve(c, R, Tn, ws, w);
+    AttnPlan ap;
+    const int D = c->D, H = c->H, hd = D / H;
+    CC_TRY(decode_attn_plan(R, Tn, hd, pos0, ctx_max, group, w.grp_ents, ap));
+    act_t* kc = reinterpret_cast<act_t*>(kv_layer);
+    act_t* vc = kc + (size_t)R * ctx_max * D;
+    CC_TRY(decode_attn_run(ap, S_(stream), w, reinterpret_cast<const act_t*>(qkv), kc, vc, row_map, reinterpret_cast<act_t*>(out), R, Tn, H, hd, pos0, ctx_max,
+                           group, append != 0, true));
+    if (path) *path = ap.grp_attn ? 1 : 0;
+    return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
+}
 
 int CC_API(cc_decode_reorder)(const cc_gpt2_cfg* c, int32_t R_src, int32_t R_dst, int32_t ctx, int32_t ctx_max, const uint16_t* kv_src, uint16_t* kv_dst,
                       const int32_t* src, void* stream) {

@@ -66,7 +66,8 @@ extern "C" {
  * cc_gemm_dact, cc_gemm_f32, cc_gemm_wgrad_split, and the attention test hooks cc_attention_fwd_x, cc_attention_bwd_x; operand mode ADDED: CC_OP_BF16X3.  Round 6 (still 3): the default-off decode experiments
  * (cc_decode_image*, cc_decode_xt_image*, cc_decode_fwd_x, cc_decode_ws_check, cc_decode_last_path) moved to include/clipcap_hip_lab.h —
  * the lab library exports them, the product library does not.  ADDED since (still 3: no existing entry point changed): cc_lmhead_score,
- * cc_grad_norm_scratch_floats, cc_grad_sqnorm, cc_grad_clip_coef, cc_adamw_step_clip, cc_logits_constrain. */
+ * cc_grad_norm_scratch_floats, cc_grad_sqnorm, cc_grad_clip_coef, cc_adamw_step_clip, cc_logits_constrain, and the decode-attention
+ * test hook cc_decode_attention. */
 #define CC_ABI_VERSION 3
 int cc_abi_version(void);
 
@@ -482,6 +483,24 @@ int cc_gemm_skinny_mode(int32_t mode);
  * once; off = one attention launch per row set, the A/B arm of tests/test_gpu_decode_group.py).  The other bits select lab-build experiments
  * (include/clipcap_hip_lab.h) and do nothing in the product library.  mode < 0 only queries.  PROCESS-WIDE test knob; returns the previous mode. */
 int cc_decode_mode(int32_t mode);
+/* The KV-cached attention step of ONE layer as cc_decode_fwd_g launches it, on a caller's buffers (the same dispatch function: the
+ * per-row kernel k_decode_attn, or k_group_union + k_decode_attn_group when Tnew == 1, 2 <= group <= 8, head dim 64, the group's list
+ * fits 64 KiB of LDS and bit 0 of cc_decode_mode is set).  Test hook: the product path never calls it.  "Stored type" = the operand
+ * type's 16-bit element, fp32 in CC_OP_BF16X3; head dim = cfg->D / cfg->H.
+ *   qkv       stored type [R*Tnew][3 D]: q | k | v of the new positions (what c_attn wrote)
+ *   kv_layer  stored type: K [R][ctx_max][D] followed by V [R][ctx_max][D], one layer of the cache
+ *   row_map   int32 [R][ctx_max] (NULL = identity): cache row that holds position j < pos0 of row r, as cc_decode_fwd
+ *   group     as cc_decode_fwd_g (1 <= group, R % group == 0)
+ *   append    1: the kernels store the K / V slices of the new positions into cache row r, slots pos0 .. pos0 + Tnew - 1, and read them
+ *             from qkv;  0: the caller has stored them already (what the fused c_attn epilogue does) and they are read from the cache
+ *   ws        the workspace of cc_decode_ws_bytes(cfg, R, Tnew) (the group form keeps its union list there)
+ *   out       stored type [R*Tnew][D]: query (r, t) attends to positions 0 .. pos0 + t
+ *   path      HOST int32 (nullable): 0 = the per-row kernel was launched, 1 = union + group kernel
+ * CC_ERR_ARG: NULL pointers, R / Tnew <= 0, pos0 < 0, group < 1 or not a divisor of R, append not 0 / 1.  CC_ERR_SHAPE: pos0 + Tnew beyond
+ * ctx_max or cfg->NPOS, or a ctx_max whose per-row kernel needs more than 64 KiB of LDS (4 * (2 ctx_max + 8 head dim) * 4 bytes).  Nothing
+ * is launched or written on an error. */
+int cc_decode_attention(const cc_gpt2_cfg* cfg, int32_t R, int32_t Tnew, int32_t pos0, int32_t ctx_max, const uint16_t* qkv, uint16_t* kv_layer,
+                        const int32_t* row_map, int32_t group, int32_t append, void* ws, uint16_t* out, int32_t* path, void* stream);
 int cc_layernorm_fwd(int32_t op_dtype, const float* x, const float* gamma, const float* beta, uint16_t* y, float* mean, float* rstd, int32_t rows,
                      int32_t D, void* stream);
 int cc_attention_fwd(int32_t op_dtype, const uint16_t* qkv, int32_t B, int32_t S, int32_t H, int32_t hd, int32_t causal, uint16_t* out, float* lse,

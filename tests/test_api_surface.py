@@ -40,6 +40,7 @@ def test_library_exports_every_declared_symbol():
     hdr = open(os.path.join(ROOT, "include", "clipcap_hip.h")).read()
     declared = set(re.findall(r"\b(cc_[a-z0-9_]+)\s*\(", hdr))
     assert len(declared) >= 25
+    assert "cc_decode_attention" in declared          # the decode-attention test hook (tests/test_gpu_decode_attention.py)
     l = _lib.lib()
     for name in declared:
         assert hasattr(l, name), f"{name} declared in clipcap_hip.h but not exported"

@@ -11,8 +11,16 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-def _lockstep(lm, S, G, L0, steps, tol, seed=0, cross_group=False):
-    """Two sessions fed the same inputs and reorders — one stepping with group=1, one with group=G — plus the full re-forward."""
+def _union_size(row_map, pos, G):
+    """entries of the largest group's union list at this step: distinct cache rows per position over the group's tables, + the G new keys"""
+    m = row_map[:, :pos].long().view(-1, G, pos).sort(dim=1).values
+    return int((1 + (m[:, 1:] != m[:, :-1]).sum(1)).sum(1).max()) + G
+
+
+def _lockstep(lm, S, G, L0, steps, tol, seed=0, cross_group=False, diverging=False, min_union=0):
+    """Two sessions fed the same inputs and reorders — one stepping with group=1, one with group=G — plus the full re-forward.
+    diverging: every beam keeps its own history (the union grows by G entries a step) except for two random in-group reorders;
+    min_union: before the last step, the largest union any step has seen must exceed it."""
     from clipcap_amd.engine import DecodeSession
     ge = lm.engine
     D = ge.dims["D"]
@@ -26,8 +34,11 @@ def _lockstep(lm, S, G, L0, steps, tol, seed=0, cross_group=False):
     sess = [s.expand(base, R) for s in sess]
     assert int(sess[1].row_map[:, 0].unique().numel()) == S        # the fanned-out rows name ONE copy of their prefix
     hist = pref[base.long()]                                       # (R, t, D): every row's own input history, for the re-forward
-    worst = 0.0
+    worst, union = 0.0, 0
     for t in range(steps):
+        union = max(union, _union_size(sess[1].row_map, sess[1].pos, G))
+        if t == steps - 1:
+            assert union > min_union, (union, min_union)
         x = torch.randn(R, 1, D, generator=gen, device="cuda") * 0.5
         la = sess[0].forward(x, group=1).clone()
         lb = sess[1].forward(x, group=G).clone()
@@ -42,7 +53,9 @@ def _lockstep(lm, S, G, L0, steps, tol, seed=0, cross_group=False):
             full = ge.logits(hist[chk])[:, -1]
             assert ((lb[chk] - full).abs().max().item() / scale) <= 4 * tol, t
         # a beam step's reorder: inside the group (as beam search does), sometimes every row from one ancestor, sometimes identity
-        if t % 3 == 2:
+        if diverging:
+            loc = torch.randint(0, G, (R,), generator=gen, device="cuda") if t in (20, 60) else torch.arange(R, device="cuda") % G
+        elif t % 3 == 2:
             loc = torch.zeros(R, dtype=torch.int64, device="cuda")
         elif t % 3 == 1:
             loc = torch.arange(R, device="cuda") % G
@@ -91,3 +104,41 @@ def test_group_hint_is_ignored_where_it_does_not_apply():
         assert (l0 - ref[:, 4]).abs().max().item() <= 2e-3 and (l1 - ref[:, 5]).abs().max().item() <= 2e-3, grp
 
 
+@pytest.mark.parametrize("precision", [None, 16, 32])
+def test_group_attention_at_the_product_context_length(precision):
+    """What a real caption runs and no other test reaches: 2 prefixes x beam 5 on a 10-position prefix for 70 steps (80 keys at the end),
+    head dim 64, beams that keep their own histories — the union list passes 128 entries, so k_decode_attn_group takes a second and a third
+    pass and k_group_union a second 64-position block, while the per-row kernel's 64-key loops take their second trip."""
+    from tests import seeded
+    from clipcap_amd.model.gpt2 import GPT2LM
+    D, n_head, V, npos = 128, 2, 157, 128
+    gsd = seeded.state_dict(seeded.gpt2_shapes(D, 1, V, npos), 977)
+    gsd["transformer.wte.weight"] = gsd["transformer.wte.weight"] * 2.0
+    lm = GPT2LM(n_embd=D, n_layer=1, n_head=n_head, vocab_size=V, n_positions=npos, precision=precision)
+    lm.load_state_dict({k: torch.from_numpy(v) for k, v in gsd.items()}, strict=False)
+    lm = lm.to("cuda")
+    w = _lockstep(lm, 2, 5, 10, 70, 1e-4 if precision == 32 else 2e-3, seed=5, diverging=True, min_union=128)
+    print(f"precision {precision}: worst |group - per-row| / scale = {w:.2e}")
+
+
+@pytest.mark.parametrize("op", ["bf16", "fp16", "x3"])
+def test_cache_reorder_is_exact(op):
+    """cc_decode_reorder with R_src != R_dst, ctx < ctx_max, two layers, 16-bit and fp32 caches: dst[l][kv][r][:ctx] is src[l][kv][map[r]][:ctx]
+    bit for bit and every position >= ctx keeps what it held."""
+    import ctypes as C
+    from clipcap_amd import _lib
+    from clipcap_amd._lib import Gpt2Cfg
+    code, dt = {"bf16": (0, torch.bfloat16), "fp16": (1, torch.float16), "x3": (2, torch.float32)}[op]
+    D, H, NL, Rs, Rd, ctx, ctx_max = 64, 2, 2, 3, 5, 6, 9
+    cfg = Gpt2Cfg(D, H, NL, 128, 128, 16, code)
+    gen = torch.Generator(device="cuda").manual_seed(9)
+    src = torch.randn(NL, 2, Rs, ctx_max, D, generator=gen, device="cuda").to(dt)
+    dst = torch.full((NL, 2, Rd, ctx_max, D), float("nan"), dtype=dt, device="cuda")
+    rows = torch.tensor([2, 0, 2, 1, 0], dtype=torch.int32, device="cuda")
+    p = lambda t: C.c_void_p(t.data_ptr())
+    rc = _lib.lib().cc_decode_reorder(C.byref(cfg), Rs, Rd, ctx, ctx_max, p(src), p(dst), p(rows), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    assert rc == 0
+    bits = torch.int16 if dt != torch.float32 else torch.int32
+    assert torch.equal(dst[:, :, :, :ctx].contiguous().view(bits), src[:, :, rows.long(), :ctx].contiguous().view(bits))
+    assert bool(torch.isnan(dst[:, :, :, ctx:]).all())
