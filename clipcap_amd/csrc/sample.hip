@@ -14,7 +14,8 @@ constexpr int SM_T = 1024;          // threads per row
 constexpr int SM_NB = 2048;         // radix buckets (11 bits)
 
 __device__ __forceinline__ unsigned sm_key(float v) {
-    const unsigned u = __float_as_uint(v);
+    unsigned u = __float_as_uint(v);
+    if ((u << 1) == 0) u = 0;                               // -0.0 == +0.0: equal floats get equal keys
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);      // larger float <-> larger key
 }
 

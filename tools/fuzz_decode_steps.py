@@ -2,16 +2,16 @@
 """Randomised sweep of the device-side decode bookkeeping against the oracle: cc_beam_step (beam widths 1..10, vocabularies 50..60000,
 padded leading dimensions, stop tokens, frozen beams) and cc_sample_step / cc_sample_step_lp (nucleus / top-k / temperature, both filter
 conventions, repetition and sentence-length penalties) —
-the assertions of tests/test_gpu_beam.py and tests/test_gpu_sampling.py on random parameters.  Not part of the test suite:
+the assertions of tests/test_gpu_beam.py, tests/test_gpu_sample_ref.py (the float64 reference of tests/sample_ref.py: every row is
+compared, a cut inside a group of equal values is held to the index-order rule) and tests/test_gpu_sampling.py (the sentence-length
+penalty against the oracle) on random parameters.  Not part of the test suite:
     python tools/fuzz_decode_steps.py [seconds] [seed]"""
 import os
 import random
 import sys
 import time
-import traceback
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests import test_gpu_beam as TB
-from tests import test_gpu_sampling as TS
 
 
 def beam_case(beam, V, ld):
@@ -44,6 +44,28 @@ def beam_case(beam, V, ld):
             assert all(abs(x[2] - y[2]) <= 3e-5 for x, y in zip(a, b)), (step, s)      # the oracle's fp32 softmax().log() is good to ~1e-5
         return "tie"
     return "exact"
+
+
+def sample_ref_case(V, scale, top_p, top_k, temperature, mode, hist_len, seed):
+    """One launch of 7 random rows (Gaussian at `scale`, one of them on a 0.25 grid, one with a handful of -inf) through every form of the
+    call tests/test_gpu_sample_ref.py walks, held to tests/sample_ref.py's check: the kept set at an admissible cut (no row is left out;
+    a row with more than one admissible prefix length is counted, not skipped), every probability within its bound, the drawn token in
+    its CDF interval.  Returns (rows, rows with more than one admissible length, worst err / bound)."""
+    import numpy as np
+    from tests import sample_ref as SR
+    from tests import test_gpu_sample_ref as TR
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((7, V)) * scale
+    x[1] = np.round(x[1] * 4.0) / 4.0
+    x[2, rng.choice(V, size=min(5, V - 1), replace=False)] = -np.inf
+    hist = None
+    if hist_len:
+        hist = rng.integers(-1, V + 1, size=(7, hist_len + SR.HIST_PAD)).astype(np.int64)
+        hist[:, 1] = hist[:, 0]
+    P = SR.Params(temperature=temperature, top_k=top_k, top_p=top_p, mode=mode, rep_pen=1.2 if hist_len else 1.0, hist_len=hist_len)
+    c = SR.Case(f"fuzz-V{V}-s{scale:.3f}-p{top_p}-k{top_k}-T{temperature}-m{mode}-h{hist_len}-seed{seed}", "random", x, P, rng.random(7), hist)
+    worst, exact = TR.walk(c)
+    return c.R, c.R - exact, worst
 
 
 def length_penalty_case(V, stop, temp, rep, top_p, top_k, want_len, factor, hl, seed):
@@ -97,7 +119,7 @@ def length_penalty_case(V, stop, temp, rep, top_p, top_k, want_len, factor, hl, 
 def main():
     budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
     rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
-    t0, n, fails, skipped, saturated, ties, lp_fired, lp_cut = time.time(), 0, [], 0, 0, 0, 0, 0
+    t0, n, fails, ties, lp_fired, lp_cut, sr_rows, sr_several, sr_worst = time.time(), 0, [], 0, 0, 0, 0, 0, 0.0
     while time.time() - t0 < budget:
         kind = rng.choice(["beam", "nucleus", "filter", "length"])
         V = rng.choice([rng.randint(50, 400), rng.randint(400, 6000), rng.randint(6000, 60000)])
@@ -115,32 +137,22 @@ def main():
                 f, how = length_penalty_case(*args)
                 lp_fired += f > 0
                 lp_cut += how == "cut"
-            elif kind == "nucleus":
-                k = rng.choice([None, None, rng.randint(1, 500)])
-                args = (V, rng.uniform(1.0, 7.0), rng.choice([1.0, round(rng.uniform(0.02, 0.999), 3)]), k, round(rng.uniform(0.5, 1.5), 2))
-                TS.test_nucleus_distribution_matches_reference_semantics(*args)
             else:
-                top_k = rng.choice([0, rng.randint(1, min(V, 300))])
-                # no filter at all (top_p = 0 and top_k = 0) is left out: the sampler's weights are 2^-32 fixed point, so a token more than
-                # 22 nats below the row maximum gets probability 0 instead of < 2.3e-10, which the nonzero-count assertion would flag
-                top_p = rng.choice([1.0, round(rng.uniform(0.05, 0.99), 3)] + ([0.0] if 0 < top_k <= 20 else []))     # same reason: the k-th token must stay above 2^-32
-                args = (V, top_p, top_k, round(rng.uniform(0.5, 1.5), 2))
-                TS.test_filter_mode_matches_top_k_top_p_filtering(*args)
+                k = rng.choice([0, 0, 1, rng.randint(2, 500), V - 1, V, V + 5])
+                top_p = rng.choice([0.0, 1.0, round(rng.uniform(0.02, 0.999), 3), round(rng.uniform(0.02, 0.999), 3)])
+                args = (V, rng.uniform(1.0, 7.0), top_p, k, round(rng.uniform(0.5, 1.5), 2), 0 if kind == "nucleus" else 1, rng.choice([0, 0, 6, 1500]),
+                        rng.randint(0, 1 << 30))
+                rows, several, worst = sample_ref_case(*args)
+                sr_rows += rows
+                sr_several += several
+                sr_worst = max(sr_worst, worst)
         except Exception as e:
-            tb = traceback.format_exc()
-            if "assert checked >= R - 2" in tb:      # too many rows of this draw had their nucleus cut within rounding of top_p: nothing was compared
-                skipped += 1
-                continue
-            if "(probs[r] > 0).sum() == (ref[r] > 0).sum()" in tb:
-                # a row whose top probability rounds to 1.0 in fp32: the reference's fp32 cumsum saturates there, `cum <= cut` then keeps
-                # EVERY token (each with < 1e-8 of the mass); the kernel's integer masses keep the nucleus.  The probabilities agree to
-                # atol 2e-6 (asserted just before that line); only the count of non-zero entries differs.
-                saturated += 1
-                continue
             fails.append((kind, args))
             print("FAIL", kind, args, repr(e)[:300], flush=True)
         n += 1
-    print(f"{n} cases in {time.time() - t0:.0f} s, {len(fails)} failures, {skipped} draws skipped (nucleus cut within rounding of top_p), {saturated} with an fp32-saturated reference cumsum, {ties} beam steps with a tie below the reference's own rounding sorted the other way; sentence-length penalty: fired in {lp_fired} rows, {lp_cut} rows compared by mass (top_p cut inside a tie)")
+    print(f"{n} cases in {time.time() - t0:.0f} s, {len(fails)} failures, {ties} beam steps with a tie below the reference's own rounding sorted the other way; "
+          f"sampling: {sr_rows} rows against float64, {sr_several} with more than one admissible prefix length, worst probs_out err / bound {sr_worst:.3f}; "
+          f"sentence-length penalty: fired in {lp_fired} rows, {lp_cut} rows compared by mass (top_p cut inside a tie)")
     sys.exit(1 if fails else 0)
 
 
