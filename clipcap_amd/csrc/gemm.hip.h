@@ -22,11 +22,13 @@
 #include <type_traits>
 #include "common.hip.h"
 #include "gemm_api.h"
+#include "gemm_plan.h"
 
 namespace CC_NS {
 
-constexpr int G_BM = 128, G_BN = 128, G_BK = 64, G_THREADS = 256;
-constexpr int G_TILE_BYTES = G_BM * G_BK * 2;  // 16 KiB per operand per buffer
+// tile sizes: defined beside the dispatch rules that depend on them (gemm_plan.h)
+using cc_plan::G_BM; using cc_plan::G_BN; using cc_plan::G_BK; using cc_plan::G_THREADS; using cc_plan::G_TILE_BYTES;
+using cc_plan::H_BM; using cc_plan::H_BN; using cc_plan::H_BK; using cc_plan::H_NS; using cc_plan::H_STAGE;
 constexpr int G_EPI_LD = 68;                    // floats per row of the epilogue strip (64 + pad, keeps 16-B alignment)
 
 struct GemmShape {
@@ -1173,7 +1175,6 @@ static __global__ __launch_bounds__(256) void k_skinny_image(const op16_t* __res
 #ifndef CC_STAG_READ_FIRST
 #define CC_STAG_READ_FIRST 1   // fragment reads of tile t are issued before the DMA of tile t+3: the DMA issue stalls (queue back-pressure) then cover the read latency; +1-2 % on the K <= 4096 shapes, A/B in HISTORY.md 4.5
 #endif
-constexpr int H_BM = 256, H_BN = 256, H_BK = 32, H_NS = 4, H_STAGE = (H_BM + H_BN) * H_BK * 2;   // 32 KiB per stage, 128 KiB total (5 stages = all 160 KiB measured 2-3 % slower)
 // The B tile may be narrower: NJ MFMA column tiles per wave -> block tile 256 x (64 NJ); NJ = 3 gives 256 x 192 for N = 768-like widths.
 // 64-B rows, 4 chunks of 16 B.  ds_read_b128 is serviced in the lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, ... (guide, LDS
 // table): with lane = (row & 15) + 16 * chunk a group holds rows 0-3 and 12-15 at chunk c and rows 4-11 at chunk c^1, so the XOR
@@ -2170,7 +2171,7 @@ template <> struct epi_row_strip<EpiLMHeadScore> { static constexpr bool value =
 template <> struct epi_row_strip<EpiLMHeadExp> { static constexpr bool value = true; };
 
 // ------------------------------------------------------------------------------------------------
-// Host launcher
+// Host launchers: each gets its plan from gemm_plan.h (tile form, K slices, grid, LDS bytes) and launches what the plan says
 // ------------------------------------------------------------------------------------------------
 // Launch of a kernel with dynamic LDS beyond the default limit: the first launch of each kernel instantiation raises its limit to `shmem`
 // (every instantiation is only ever launched with one size).
@@ -2180,158 +2181,64 @@ inline void launch_dyn(dim3 grid, dim3 block, size_t shmem, hipStream_t st, cons
     if (!attr) { (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); attr = true; }
     hipLaunchKernelGGL(Kernel, grid, block, shmem, st, args...);
 }
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline cc_plan::GemmModes gemm_modes() {
+    static const int ncu = []() { int n = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
+    return {g_gemm_tile_mode, g_gemm_s64, g_gemm_small_x2, kX3, ncu};
+}
+template <class Epi>
+constexpr cc_plan::EpiTraits epi_traits() {
+    return {epi_row_strip<Epi>::value, epi_strip_aux<Epi>::value, epi_is_dact<Epi>::value, std::is_same<Epi, EpiF32>::value, epi_acc_init<Epi>::value, kX3};
+}
 template <class Epi>
 inline int launch_gemm_s64(const op16_t* A, int lda, const op16_t* B, int ldb, int M, int N, int K, int ksplit, int nj, const Epi& epi, int* ks_eff,
                            hipStream_t st, const op16_t* Bimg = nullptr);
-// bf16x3 build: the fused two-stage forms of the NT kernels (gemm_stag256_body<X3F>, gemm_nt_glds_x3f_kernel, gemm_nt_glds4x2_x3f_kernel); CC_X3_FUSED=0: A/B switch
-inline bool x3_fused_on() {
-    static const bool on = kX3 && !(cc_lab_env("CC_X3_FUSED") && atoi(cc_lab_env("CC_X3_FUSED")) == 0);
-    return on;
-}
+// NT launcher (and, for operands that are not both K-contiguous, the register-staged kernel).  tile: -2 = process-wide mode / chooser, else as
+// cc_gemm_tile_mode; group_m: row tiles per ordering group (0 = default); *ks_eff returns the effective slice count.
 template <class Epi>
 inline int launch_gemm(int al, int bl, const op16_t* A, int lda, const op16_t* B, int ldb, int M, int N, int K,
-                       int ksplit, const Epi& epi, hipStream_t st, int tile = -2, int group_m = 0) {   // tile: -2 = process-wide mode / chooser, else as cc_gemm_tile_mode; group_m: row tiles per ordering group (0 = default)
-    if (M <= 0 || N <= 0 || K <= 0) return CC_OK;
-    if ((lda & 7) || (ldb & 7) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15)) return CC_ERR_SHAPE;
-    if (al == 0 && (K & 7)) return CC_ERR_SHAPE;
-    if (bl == 0 && (K & 7)) return CC_ERR_SHAPE;
-    if (al == 1 && (M & 7)) return CC_ERR_SHAPE;
-    if (bl == 1 && (N & 7)) return CC_ERR_SHAPE;
-    if constexpr (!epi_row_strip<Epi>::value && !epi_strip_aux<Epi>::value) {
-        if (g_gemm_s64 > 0 && al == 0 && bl == 0 && (K % G_BK) == 0 && M <= 1024)     // tools/small_gemm_bench.py (CC_GEMM_S64 = 1 / 2)
-            return launch_gemm_s64(A, lda, B, ldb, M, N, K, ksplit, g_gemm_s64, epi, nullptr, st);
-    }
+                       int ksplit, const Epi& epi, hipStream_t st, int tile = -2, int group_m = 0, int* ks_eff = nullptr) {
+    using namespace cc_plan;
+    constexpr EpiTraits t = epi_traits<Epi>();
+    const NtPlan p = plan_nt(al, bl, M, N, K, lda, ldb, ksplit, tile, group_m, aligned16(A), aligned16(B), t, gemm_modes(), gemm_knobs());
+    if (p.status != CC_OK || p.form == NT_NOTHING) return p.status;
+    if (ks_eff) *ks_eff = p.ks_eff;
     GemmShape g;
     g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb;
-    static const int env_group = []() { const char* e = cc_lab_env("CC_GROUP_M"); return e ? atoi(e) : 0; }();
-    g.group_m = env_group > 0 ? env_group : (group_m > 0 ? group_m : 8);
-    static const int env_stagger = []() { const char* e = cc_lab_env("CC_GEMM_STAGGER"); return e ? atoi(e) : 0; }();   // tuning knob
-    g.stagger = env_stagger;
-    if (ksplit < 1) ksplit = 1;
-    int kt = (K + G_BK - 1) / G_BK;
-    int per = (kt + ksplit - 1) / ksplit;
-    ksplit = (kt + per - 1) / per;
-    g.k_chunk = per * G_BK;
-    dim3 grid(((M + G_BM - 1) / G_BM) * ((N + G_BN - 1) / G_BN), 1, ksplit);
-    // Tile choice for NT launches.  The 256-row kernel moves 1/2 (256 wide) or 2/3 (192 wide) of the 128 x 128 kernel's L2->LDS
-    // bytes per flop and runs ~1.2x / ~1.15x its rate on full waves, but holds one block per CU, so wave quantisation decides:
-    // cost = rounds x tile area / rate, the 128 x 128 kernel counted with 2 co-resident blocks per CU (measured table: DESIGN.md 4.1).
-    // The 320 x 256 form (10 row tiles per wave, 36-KiB stages) does 1.25x the MFMAs per K-step at 1.13-1.27x the step time: it wins
-    // where it saves a round (12800 x 3072: 480 tiles = 2 rounds instead of 3; the lm_head: 25 instead of 31).
-    // g_gemm_tile_mode (cc_gemm_tile_mode / CC_GEMM_S256) = 0 (never) / 3 / 4 / 5 / 6 (force 256x192 / 256x256 / 320x256 / 160x256) overrides it for
-    // tests and tools/gemm_tiles.py.
-    const int s256 = tile != -2 ? tile : g_gemm_tile_mode;
-    int nj = 0, ni = 8;
-    constexpr bool can160 = !kX3 && !epi_row_strip<Epi>::value && !epi_is_dact<Epi>::value;      // the 160 x 256 form (below)
-    // K slices (blockIdx.z) on the 256-row kernels only for the slab-writing fp32 epilogue and only when the caller names the tile
-    constexpr bool zsplit_ok = std::is_same<Epi, EpiF32>::value;
-    if (al == 0 && bl == 0 && (K % H_BK) == 0 && (ksplit == 1 || (zsplit_ok && tile > 0)) && s256 != 0) {
-        const long tm = (M + H_BM - 1) / H_BM, t128 = (long)grid.x;
-        const long t256 = tm * ((N + 255) / 256), t192 = tm * ((N + 191) / 192), t320 = (long)((M + 319) / 320) * ((N + 255) / 256);
-        const double c128 = t128 <= 256 ? 16384.0 / 0.75 : (double)((t128 + 511) / 512) * 32768.0;
-        // (bf16x3 build, round 5: crediting the 256 x 192 form with its fused two-stage loop — c192 / 1.45, which moves c_attn / c_fc forward from
-        // the three-pass 256-wide forms to 3-4 rounds of fused 192-wide tiles — measured 28.55 -> 30.1 ms per step, two alternations: reverted)
-        const double c256 = (double)((t256 + 255) / 256) * 65536.0 / 1.2, c192 = (double)((t192 + 255) / 256) * 49152.0 / 1.15;
-        const double c320 = (double)((t320 + 255) / 256) * 81920.0 / 1.3;
-        constexpr bool can192 = !epi_row_strip<Epi>::value;   // the lm_head partials assume 64-column wave strips
-        // the activation-gradient epilogue (aux tile read + gelu' + store) is not hidden at one block per CU: 12800 x 3072 x 768 measured
-        // 106.6 us on 320 x 256 vs 97.3 on 128 x 128 (two co-resident blocks), while the plain / gelu-forward epilogues gain (90 -> 78 us)
-        // (also with the forward-stored derivative, act 3 — a single multiply —, the 128 x 128 kernel stays ahead: 12.31 vs 12.44 ms per step)
-        constexpr bool can320 = !epi_is_dact<Epi>::value;
-        // (round 5) 160 x 256 (5 row tiles per wave, 26-KiB stages): for the N = 768 launches at M = 12800 it is 240 tiles on the 256 CUs where
-        // 256 x 192 is 200 — hipBLASLt's pick for these shapes too (MT160x256, profiles/r05_j_*).  A single-round launch takes one tile's
-        // latency, so the smaller tile is the shorter launch whenever both fit one round; never for the bf16x3 build (its fused form is 192-wide).
-        const long t160 = (long)((M + 159) / 160) * ((N + 255) / 256);
-        const double c160 = (double)((t160 + 255) / 256) * 40960.0 / 1.1;
-        static const bool s160_on = []() { const char* e = cc_lab_env("CC_GEMM_S160"); return !e || atoi(e) != 0; }();
-        if (can160 && (s256 == 6 || s256 == 7 || (s256 < 0 && s160_on && ksplit == 1 && c160 < 0.98 * c128 && c160 < 0.98 * c256 && c160 < 0.98 * c320 && (!can192 || c160 < 0.98 * c192)))) { nj = 4; ni = 5; }
-        else if (s256 == 5 || (can320 && s256 < 0 && c320 < 0.98 * c128 && c320 < c256 && (!can192 || c320 < c192))) { nj = 4; ni = 10; }
-        else if (s256 == 4 || (s256 < 0 && c256 < 0.98 * c128 && (!can192 || c256 <= c192))) nj = 4;
-        else if (can192 && (s256 == 3 || (s256 < 0 && c192 < 0.98 * c128))) nj = 3;
-    }
-    if (nj) {
-        const int bm = 32 * ni;
-        const size_t sh = (size_t)H_NS * (bm + H_BN) * H_BK * 2;
-        const dim3 gr((unsigned)(((M + bm - 1) / bm) * ((N + 64 * nj - 1) / (64 * nj))), 1, (unsigned)ksplit);
-        if (nj == 4 && ni == 8) launch_dyn<gemm_nt_stag256_kernel<Epi, 4, false, 8>>(gr, dim3(512), sh, st, A, B, g, epi);
-        else if (nj == 4 && ni == 5) {
-            if constexpr (can160) {
-                // (round 6) the 160 x 256 launches go to the persistent 4-wave kernel with 64-deep full-line stages (gemm_q4.hip.h) wherever K fits its
-                // ring: three stages for K % 192 == 0, two for K % 128 == 0; byte offsets inside an operand are 32-bit there.  Measured against the
-                // staggered 160 x 256 kernel (profiles/r06_l): 12800 x 768 x 3072 58.9 -> 52.8 us, x 2304 44.2 -> 41.7, x 768 20.2 -> 21.2 (plain functor:
-                // 57.1 -> 49.7, 43.7 -> 38.5, 20.6 -> 19.8).  cc_gemm_tile_mode 6 keeps the staggered kernel, 7 forces this one.
-                static const bool q4_on = []() { const char* e = cc_lab_env("CC_GEMM_Q4"); return !e || atoi(e) != 0; }();
-                const bool fits32 = (size_t)M * (size_t)lda * 2 < 0xffff0000ull && (size_t)N * (size_t)ldb * 2 < 0xffff0000ull;
-                const int ns = (K % 192 == 0 && K >= 384) ? 3 : ((K % 128 == 0 && K >= 256) ? 2 : 0);
-                static const bool q4_last = []() { const char* e = cc_lab_env("CC_Q4_LAST"); return !e || atoi(e) != 0; }();
-                g.flags = q4_last ? 0 : 1;
-                if (ns && fits32 && ksplit == 1 && s256 != 6 && (q4_on || s256 == 7)) {
-                    static const int ncu = []() { int n = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
-                    const int tiles = ((M + 159) / 160) * ((N + 255) / 256);
-                    const dim3 gq((unsigned)(tiles < ncu ? tiles : ncu));
-                    if (ns == 3) {
-                        launch_dyn<gemm_nt_q4_kernel<Epi, 5, 3>>(gq, dim3(256), (size_t)3 * (160 + 256) * 128, st, A, B, g, epi);
-                    } else {
-                        launch_dyn<gemm_nt_q4_kernel<Epi, 5, 2>>(gq, dim3(256), (size_t)2 * (160 + 256) * 128, st, A, B, g, epi);
-                    }
-                } else launch_dyn<gemm_nt_stag256_kernel<Epi, 4, false, 5>>(gr, dim3(512), sh, st, A, B, g, epi);
-            }
-        }
-        else if (nj == 4) launch_dyn<gemm_nt_stag256_kernel<Epi, 4, false, 10>>(gr, dim3(512), sh, st, A, B, g, epi);
-        else if constexpr (!epi_row_strip<Epi>::value) {
-            bool fused = false;
-            if constexpr (kX3) {       // bf16x3 build: every NT launch carries operand images over K' = 3 K — the fused two-stage form (gemm_stag256_body, X3F)
-                const bool x3f_on = x3_fused_on();
-                if (x3f_on && (K % (3 * H_BK)) == 0 && ksplit <= K / (3 * H_BK)) {     // (K slices: ranges of the logical K's chunks, every slice non-empty)
-                    launch_dyn<gemm_nt_stag256_kernel<Epi, 3, false, 8, true>>(gr, dim3(512), sh, st, A, B, g, epi);
-                    fused = true;
-                }
-            }
-            if (!fused) launch_dyn<gemm_nt_stag256_kernel<Epi, 3, false, 8>>(gr, dim3(512), sh, st, A, B, g, epi);
-        }
-    } else
+    g.k_chunk = p.k_chunk; g.group_m = p.group_m; g.stagger = p.stagger; g.flags = p.flags;
+    const dim3 grid(p.grid_x, 1, p.grid_z), block(p.block);
+    // the forms a functor has: the planner picks no other, and a plan that names one anyway is refused, not dropped
+    constexpr bool can160 = !t.x3 && !t.row_strip && !t.dact, can192 = !t.row_strip;
+    switch (p.form) {
+    case NT_SKINNY:
+        if constexpr (!t.row_strip && !t.strip_aux) return launch_gemm_s64(A, lda, B, ldb, M, N, K, ksplit, p.skinny_form, epi, ks_eff, st);
+        else return CC_ERR_ARG;
+    case NT_STAG_256: launch_dyn<gemm_nt_stag256_kernel<Epi, 4, false, 8>>(grid, block, p.lds, st, A, B, g, epi); break;
+    case NT_STAG_320: launch_dyn<gemm_nt_stag256_kernel<Epi, 4, false, 10>>(grid, block, p.lds, st, A, B, g, epi); break;
+    case NT_STAG_160: if constexpr (can160) launch_dyn<gemm_nt_stag256_kernel<Epi, 4, false, 5>>(grid, block, p.lds, st, A, B, g, epi); else return CC_ERR_ARG; break;
+    case NT_Q4_3: if constexpr (can160) launch_dyn<gemm_nt_q4_kernel<Epi, 5, 3>>(grid, block, p.lds, st, A, B, g, epi); else return CC_ERR_ARG; break;
+    case NT_Q4_2: if constexpr (can160) launch_dyn<gemm_nt_q4_kernel<Epi, 5, 2>>(grid, block, p.lds, st, A, B, g, epi); else return CC_ERR_ARG; break;
+    case NT_STAG_192: if constexpr (can192) launch_dyn<gemm_nt_stag256_kernel<Epi, 3, false, 8>>(grid, block, p.lds, st, A, B, g, epi); else return CC_ERR_ARG; break;
+    case NT_STAG_192_X3F: if constexpr (can192 && kX3) launch_dyn<gemm_nt_stag256_kernel<Epi, 3, false, 8, true>>(grid, block, p.lds, st, A, B, g, epi); else return CC_ERR_ARG; break;
 #ifdef CC_GEMM_ABLATION
-    static const int abl = []() { const char* e = cc_lab_env("CC_GEMM_ABL"); return e ? atoi(e) : 0; }();
-    if (al == 0 && bl == 0 && (K % G_BK) == 0 && abl == 1) { hipLaunchKernelGGL((gemm_nt_glds_kernel<Epi, 1>), grid, dim3(G_THREADS), 0, st, A, B, g, epi); }
-    else if (al == 0 && bl == 0 && (K % G_BK) == 0 && abl == 2) { hipLaunchKernelGGL((gemm_nt_glds_kernel<Epi, 2>), grid, dim3(G_THREADS), 0, st, A, B, g, epi); }
-    else if (al == 0 && bl == 0 && (K % G_BK) == 0 && abl == 4) { hipLaunchKernelGGL((gemm_nt_glds_kernel<Epi, 4>), grid, dim3(G_THREADS), 0, st, A, B, g, epi); }
-    else if (al == 0 && bl == 0 && (K % G_BK) == 0 && abl == 5) { hipLaunchKernelGGL((gemm_nt_glds_kernel<Epi, 5>), grid, dim3(G_THREADS), 0, st, A, B, g, epi); }
-    else if (al == 0 && bl == 0 && (K % G_BK) == 0 && abl == 6) { hipLaunchKernelGGL((gemm_nt_glds_kernel<Epi, 6>), grid, dim3(G_THREADS), 0, st, A, B, g, epi); }
-    else
+    case NT_ABLATION:
+        if (p.abl == 1) hipLaunchKernelGGL((gemm_nt_glds_kernel<Epi, 1>), grid, block, 0, st, A, B, g, epi);
+        else if (p.abl == 2) hipLaunchKernelGGL((gemm_nt_glds_kernel<Epi, 2>), grid, block, 0, st, A, B, g, epi);
+        else if (p.abl == 4) hipLaunchKernelGGL((gemm_nt_glds_kernel<Epi, 4>), grid, block, 0, st, A, B, g, epi);
+        else if (p.abl == 5) hipLaunchKernelGGL((gemm_nt_glds_kernel<Epi, 5>), grid, block, 0, st, A, B, g, epi);
+        else hipLaunchKernelGGL((gemm_nt_glds_kernel<Epi, 6>), grid, block, 0, st, A, B, g, epi);
+        break;
 #endif
-    if (al == 0 && bl == 0 && (K % G_BK) == 0 && (long)grid.x * grid.z <= 256 && g_gemm_tile_mode != 0 && K / (int)grid.z >= 4 * G_BK) {
-        // at most one block per CU: nothing co-resident to hide the 2-stage kernel's per-K-step round trip -> 4-stage variant
-        constexpr size_t sh4 = (size_t)8 * G_TILE_BYTES;
-        bool fused = false;
-        if constexpr (kX3) {
-            const bool x3f_on = x3_fused_on();
-            if (g_gemm_small_x2 && x3f_on && ksplit == 1 && (K % (3 * G_BK)) == 0) {
-                launch_dyn<gemm_nt_glds4x2_x3f_kernel<Epi>>(grid, dim3(2 * G_THREADS), sh4, st, A, B, g, epi);
-                fused = true;
-            }
-        }
-        if (fused) {}
-        else if (g_gemm_small_x2) launch_dyn<gemm_nt_glds4x2_kernel<Epi>>(grid, dim3(2 * G_THREADS), sh4, st, A, B, g, epi);
-        else launch_dyn<gemm_nt_glds4_kernel<Epi>>(grid, dim3(G_THREADS), sh4, st, A, B, g, epi);
-    } else if (al == 0 && bl == 0 && (K % G_BK) == 0) {
-        bool fused = false;
-        if constexpr (kX3) {       // bf16x3 build: operand images over K' = 3 K -> the fused two-stage form
-            const bool x3f_on = x3_fused_on();
-            if (x3f_on && ksplit == 1 && (K % (3 * G_BK)) == 0) {
-                hipLaunchKernelGGL((gemm_nt_glds_x3f_kernel<Epi>), grid, dim3(G_THREADS), 0, st, A, B, g, epi);
-                fused = true;
-            }
-        }
-        if (!fused) hipLaunchKernelGGL((gemm_nt_glds_kernel<Epi>), grid, dim3(G_THREADS), 0, st, A, B, g, epi);
+    case NT_GLDS4X2_X3F: if constexpr (kX3) launch_dyn<gemm_nt_glds4x2_x3f_kernel<Epi>>(grid, block, p.lds, st, A, B, g, epi); else return CC_ERR_ARG; break;
+    case NT_GLDS4X2: launch_dyn<gemm_nt_glds4x2_kernel<Epi>>(grid, block, p.lds, st, A, B, g, epi); break;
+    case NT_GLDS4: launch_dyn<gemm_nt_glds4_kernel<Epi>>(grid, block, p.lds, st, A, B, g, epi); break;
+    case NT_GLDS_X3F: if constexpr (kX3) hipLaunchKernelGGL((gemm_nt_glds_x3f_kernel<Epi>), grid, block, 0, st, A, B, g, epi); else return CC_ERR_ARG; break;
+    case NT_GLDS: hipLaunchKernelGGL((gemm_nt_glds_kernel<Epi>), grid, block, 0, st, A, B, g, epi); break;
+    case NT_REG_00: hipLaunchKernelGGL((gemm_bf16_kernel<0, 0, Epi>), grid, block, 0, st, A, B, g, epi); break;
+    case NT_REG_01: hipLaunchKernelGGL((gemm_bf16_kernel<0, 1, Epi>), grid, block, 0, st, A, B, g, epi); break;
+    case NT_REG_11: hipLaunchKernelGGL((gemm_bf16_kernel<1, 1, Epi>), grid, block, 0, st, A, B, g, epi); break;
+    default: return CC_ERR_ARG;
     }
-    else if (al == 0 && bl == 0)
-        hipLaunchKernelGGL((gemm_bf16_kernel<0, 0, Epi>), grid, dim3(G_THREADS), 0, st, A, B, g, epi);
-    else if (al == 0 && bl == 1)
-        hipLaunchKernelGGL((gemm_bf16_kernel<0, 1, Epi>), grid, dim3(G_THREADS), 0, st, A, B, g, epi);
-    else if (al == 1 && bl == 1)
-        hipLaunchKernelGGL((gemm_bf16_kernel<1, 1, Epi>), grid, dim3(G_THREADS), 0, st, A, B, g, epi);
-    else
-        return CC_ERR_ARG;
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 
@@ -2340,60 +2247,40 @@ inline int launch_gemm(int al, int bl, const op16_t* A, int lda, const op16_t* B
 template <class Epi>
 inline int launch_gemm_s64(const op16_t* A, int lda, const op16_t* B, int ldb, int M, int N, int K, int ksplit, int nj, const Epi& epi, int* ks_eff,
                            hipStream_t st, const op16_t* Bimg) {
-    if ((K % G_BK) || (lda & 7) || (ldb & 7) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15)) return CC_ERR_SHAPE;
+    const cc_plan::S64Plan p = cc_plan::plan_s64(M, N, K, lda, ldb, ksplit, nj, aligned16(A), aligned16(B), Bimg && aligned16(Bimg));
+    if (p.status != CC_OK) return p.status;
+    if (ks_eff) *ks_eff = p.ks_eff;
     GemmShape g;
     g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb;
-    g.group_m = 8;
-    g.stagger = 0;
-    if (ksplit < 1) ksplit = 1;
-    const int kt = K / G_BK;
-    const int per = (kt + ksplit - 1) / ksplit;
-    ksplit = (kt + per - 1) / per;
-    g.k_chunk = per * G_BK;
-    if (ks_eff) *ks_eff = ksplit;
-    const int tm = (M + 63) / 64;
+    g.k_chunk = p.k_chunk; g.group_m = 8; g.stagger = 0;
+    const dim3 grid(p.grid_x, 1, p.grid_z), block(p.block);
+    switch (p.form) {
 #ifdef CC_EXPERIMENTS
-    if (nj == 3 && Bimg && (N % 64) == 0 && ((uintptr_t)Bimg & 15) == 0) {      // ... with the weight operand global -> VGPR from its fragment-ordered image
-        constexpr size_t sh = (size_t)4 * 128 * 128;      // (the epilogue's partial tiles need the 64 KiB)
-        launch_dyn<gemm_nt_s64kwb_kernel<Epi, 4>>(dim3((unsigned)(tm * (N / 64)), 1, (unsigned)ksplit), dim3(320), sh, st, A, Bimg, g, epi);
-    } else
-#else
-    (void)Bimg;
+    case cc_plan::S64_IMAGE: launch_dyn<gemm_nt_s64kwb_kernel<Epi, 4>>(grid, block, p.lds, st, A, Bimg, g, epi); break;
 #endif
-    if (nj == 4) {                   // 80 x 64 tiles, K split over the waves (gemm_nt_s80kw_kernel)
-        constexpr size_t sh = (size_t)4 * 6 * 16 * 64 * sizeof(float);      // the epilogue's partial tiles: 96 KiB (the four 20-KiB stages fit inside)
-        launch_dyn<gemm_nt_s80kw_kernel<Epi>>(dim3((unsigned)(((M + 79) / 80) * ((N + 63) / 64)), 1, (unsigned)ksplit), dim3(G_THREADS), sh, st, A, B, g, epi);
-    } else if (nj == 3) {                   // K split over the waves (gemm_nt_s64kw_kernel)
-        constexpr size_t sh = (size_t)4 * 128 * 128;
-        launch_dyn<gemm_nt_s64kw_kernel<Epi>>(dim3((unsigned)(tm * ((N + 63) / 64)), 1, (unsigned)ksplit), dim3(G_THREADS), sh, st, A, B, g, epi);
-    } else if (nj == 2) {
-        launch_dyn<gemm_nt_s64_kernel<Epi, 2, 3, 1>>(dim3((unsigned)(tm * ((N + 127) / 128)), 1, (unsigned)ksplit), dim3(G_THREADS), (size_t)3 * (64 + 128) * 128, st, A, B, g, epi);
-    } else {
-        launch_dyn<gemm_nt_s64_kernel<Epi, 1, 4, 1>>(dim3((unsigned)(tm * ((N + 63) / 64)), 1, (unsigned)ksplit), dim3(G_THREADS), (size_t)4 * (64 + 64) * 128, st, A, B, g, epi);
+    case 4: launch_dyn<gemm_nt_s80kw_kernel<Epi>>(grid, block, p.lds, st, A, B, g, epi); break;
+    case 3: launch_dyn<gemm_nt_s64kw_kernel<Epi>>(grid, block, p.lds, st, A, B, g, epi); break;
+    case 2: launch_dyn<gemm_nt_s64_kernel<Epi, 2, 3, 1>>(grid, block, p.lds, st, A, B, g, epi); break;
+    default: launch_dyn<gemm_nt_s64_kernel<Epi, 1, 4, 1>>(grid, block, p.lds, st, A, B, g, epi); break;
     }
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 
-// Weight-gradient form C[M][N] = sum_k A[k][M] B[k][N] (both operands K-strided) on the 256 x 256 kernel with direct-to-LDS staging
-// and transpose reads; K is split over blockIdx.z (epi must be an EpiF32 in slab mode when ksplit > 1).  K % 32 == 0, M % 8 == 0,
-// N % 8 == 0.  Returns the effective slice count through *ks_eff.
-template <class Epi>
-inline int launch_gemm_tt256(const op16_t* A, int lda, const op16_t* B, int ldb, int M, int N, int K, int ksplit, const Epi& epi, int* ks_eff,
-                             hipStream_t st) {
-    if ((K % H_BK) || (M & 7) || (N & 7) || (lda & 7) || (ldb & 7) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15)) return CC_ERR_SHAPE;
+// Weight-gradient form C[M][N] = sum_k A[k][M] B[k][N] (both operands K-strided), K split over blockIdx.z (epi must be an EpiF32 in slab mode
+// when ksplit > 1); M % 8 == 0, N % 8 == 0.  TILE 256: the 256 x 256 kernel with direct-to-LDS staging and transpose reads (K % 32 == 0);
+// TILE 128: the TT 128 x 128 kernel (gemm_tt_glds4_kernel, K % 64 == 0).  Returns the effective slice count through *ks_eff.
+template <int TILE, class Epi>
+inline int launch_gemm_tt(const op16_t* A, int lda, const op16_t* B, int ldb, int M, int N, int K, int ksplit, const Epi& epi, int* ks_eff,
+                          hipStream_t st) {
+    const cc_plan::TTPlan p = cc_plan::plan_tt(TILE, M, N, K, lda, ldb, ksplit, aligned16(A), aligned16(B));
+    if (p.status != CC_OK) return p.status;
+    if (ks_eff) *ks_eff = p.ks_eff;
     GemmShape g;
     g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb;
-    g.group_m = 8;
-    g.stagger = 0;
-    if (ksplit < 1) ksplit = 1;
-    const int kt = (K + G_BK - 1) / G_BK;
-    const int per = (kt + ksplit - 1) / ksplit;
-    ksplit = (kt + per - 1) / per;
-    g.k_chunk = per * G_BK;
-    if (ks_eff) *ks_eff = ksplit;
-    constexpr size_t sh = (size_t)H_NS * H_STAGE;
-    const dim3 gr((unsigned)(((M + H_BM - 1) / H_BM) * ((N + H_BN - 1) / H_BN)), 1, (unsigned)ksplit);
-    launch_dyn<gemm_nt_stag256_kernel<Epi, 4, true>>(gr, dim3(512), sh, st, A, B, g, epi);
+    g.k_chunk = p.k_chunk; g.group_m = 8; g.stagger = 0;
+    const dim3 grid(p.grid_x, 1, p.grid_z), block(p.block);
+    if constexpr (TILE == 256) launch_dyn<gemm_nt_stag256_kernel<Epi, 4, true>>(grid, block, p.lds, st, A, B, g, epi);
+    else launch_dyn<gemm_tt_glds4_kernel<Epi>>(grid, block, p.lds, st, A, B, g, epi);
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 
@@ -2401,7 +2288,7 @@ inline int launch_gemm_tt256(const op16_t* A, int lda, const op16_t* B, int ldb,
 // problems and all their K slices form one 1-D grid (problem i owns logical blocks [first[i], first[i+1]), slice-major inside), so the
 // launch fills the CUs with ONE tail instead of four, and the per-launch floor is paid once.  Each problem writes fp32 slabs (C of
 // its functor + slice * zstride) that the batched slab reduce folds into dW.
-constexpr int TT_GROUP_MAX = 32;
+using cc_plan::TT_GROUP_MAX;
 struct TTGroup {
     const op16_t* A[TT_GROUP_MAX];
     const op16_t* B[TT_GROUP_MAX];
@@ -2502,37 +2389,11 @@ static __global__ __launch_bounds__(256) void gemm_tt_tail_reduce_kernel(TTGroup
         *reinterpret_cast<float4*>(d) = make_float4(o.x + a.x, o.y + a.y, o.z + a.z, o.w + a.w);
     }
 }
-inline int launch_gemm_tt256_group(const TTGroup& grp, hipStream_t st) {
-    constexpr size_t sh = (size_t)H_NS * H_STAGE;
-    const unsigned blocks = grp.whole >= 0 ? (unsigned)(grp.whole + (grp.first[grp.n] - grp.whole) * grp.split) : (unsigned)grp.first[grp.n];
-    launch_dyn<gemm_tt_stag256_group_kernel>(dim3(blocks), dim3(512), sh, st, grp);
-    if (grp.whole >= 0) hipLaunchKernelGGL(gemm_tt_tail_reduce_kernel, dim3((unsigned)(grp.first[grp.n] - grp.whole) * 16), dim3(256), 0, st, grp);
-    return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
-}
-inline int launch_gemm_tt128_group(const TTGroup& grp, hipStream_t st) {
-    const size_t sh = 4 * 2 * G_TILE_BYTES;
-    launch_dyn<gemm_tt_glds4_group_kernel>(dim3((unsigned)grp.first[grp.n]), dim3(G_THREADS), sh, st, grp);
-    return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
-}
-
-// TT 128 x 128 launcher (see gemm_tt_glds4_kernel): K % 64 == 0, M % 8 == 0, N % 8 == 0; slices over blockIdx.z.
-template <class Epi>
-inline int launch_gemm_tt128(const op16_t* A, int lda, const op16_t* B, int ldb, int M, int N, int K, int ksplit, const Epi& epi, int* ks_eff,
-                             hipStream_t st) {
-    if ((K % G_BK) || (M & 7) || (N & 7) || (lda & 7) || (ldb & 7) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15)) return CC_ERR_SHAPE;
-    GemmShape g;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb;
-    g.group_m = 8;
-    g.stagger = 0;
-    if (ksplit < 1) ksplit = 1;
-    const int kt = K / G_BK;
-    const int per = (kt + ksplit - 1) / ksplit;
-    ksplit = (kt + per - 1) / per;
-    g.k_chunk = per * G_BK;
-    if (ks_eff) *ks_eff = ksplit;
-    constexpr size_t sh = (size_t)8 * G_TILE_BYTES;
-    const dim3 gr((unsigned)(((M + G_BM - 1) / G_BM) * ((N + G_BN - 1) / G_BN)), 1, (unsigned)ksplit);
-    launch_dyn<gemm_tt_glds4_kernel<Epi>>(gr, dim3(G_THREADS), sh, st, A, B, g, epi);
+// the grouped launch a plan describes (cc_plan::WgradGroupPlan: kernel by tile, grid, LDS bytes, and the tail reduce of the direct form)
+inline int launch_gemm_tt_group(const TTGroup& grp, const cc_plan::WgradGroupPlan& p, hipStream_t st) {
+    if (p.tile == 256) launch_dyn<gemm_tt_stag256_group_kernel>(dim3(p.blocks), dim3(p.block), p.lds, st, grp);
+    else launch_dyn<gemm_tt_glds4_group_kernel>(dim3(p.blocks), dim3(p.block), p.lds, st, grp);
+    if (p.reduce_blocks) hipLaunchKernelGGL(gemm_tt_tail_reduce_kernel, dim3(p.reduce_blocks), dim3(256), 0, st, grp);
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 

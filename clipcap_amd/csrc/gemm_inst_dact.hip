@@ -12,8 +12,7 @@ int gemm_dact(int al, int bl, ActIn A, int lda, const op16_t* B, int ldb, int M,
     if (rca != CC_OK) return rca;
     EpiDAct e{C, aux, ldc, M, N, act};
     e.img = Co.img;
-    static const bool spec_on = []() { const char* v = cc_lab_env("CC_EPI_SPEC"); return !v || atoi(v) != 0; }();
-    if (spec_on && act == 3 && e.img == 0) {       // the forward stored gelu': one multiply, no switch per unit
+    if (cc_plan::pick_dact(act, e.img, cc_plan::gemm_knobs()) == cc_plan::EPI_SPEC) {
         EpiDActT<3> m{C, aux, ldc, M, N, 3};
         return launch_gemm(al, bl, A16, lda, B, ldb, M, N, K, 1, m, st);
     }

@@ -51,100 +51,40 @@ __global__ __launch_bounds__(256) void k_slab_reduce_multi(SlabItems items) {
         *reinterpret_cast<float4*>(d) = make_float4(a.x + c.x, a.y + c.y, a.z + c.z, a.w + c.w);
     }
 }
-// the deferred problems of a batch as one grouped launch: a common slice count ks is chosen to minimise
-// rounds x (K-steps per block + fixed per-block cost), rounds = ceil(blocks / CUs), then the slabs are parked for the batched reduce
+// the deferred problems of a batch as one grouped launch (cc_plan::plan_wgrad_group_direct / plan_wgrad_group); the slab form's slabs are
+// parked for the batched reduce
 static int wgrad_launch_group(WgradBatch& b, hipStream_t st) {
     if (b.nd == 0) return CC_OK;
+    const int K = b.d[0].K;
+    double flops = 0.0;
+    cc_plan::WgradProblem pr[TT_GROUP_MAX];
+    for (int i = 0; i < b.nd; i++) { pr[i] = {b.d[i].Mw, b.d[i].Nw}; flops += 2.0 * b.d[i].Mw * b.d[i].Nw * (double)K; }
+    cc_shared::ProfScope _all(cc_shared::SITE_ALL_GEMMS, st, flops);
+    const cc_plan::WgradGroupPlan p = b.direct ? cc_plan::plan_wgrad_group_direct(pr, b.nd, K, b.scratch && b.n == 0, WGRAD_SCRATCH_BYTES, cc_plan::gemm_knobs())
+                                               : cc_plan::plan_wgrad_group(pr, b.nd, K, WGRAD_SCRATCH_BYTES - b.used, cc_plan::gemm_knobs());
+    if (p.status != CC_OK) return p.status;
     TTGroup grp;
     grp.n = b.nd;
-    grp.mode = 0;
-    const int K = b.d[0].K;
-    if (b.direct) {
-        // one K slice per tile, dW += tile in the epilogue: the 256 x 256 kernel when K allows it (a block walks the whole K: 160 steps at K = 5120)
-        double fl = 0.0;
-        for (int i = 0; i < b.nd; i++) fl += 2.0 * b.d[i].Mw * b.d[i].Nw * (double)K;
-        cc_shared::ProfScope _alld(cc_shared::SITE_ALL_GEMMS, st, fl);
-        const bool t256 = (K % H_BK) == 0;
-        const int tile = t256 ? 256 : 128;
-        const int kt64 = (K + G_BK - 1) / G_BK;
-        int first = 0;
-        for (int i = 0; i < b.nd; i++) {
-            const auto& d = b.d[i];
-            grp.A[i] = d.X; grp.B[i] = d.Y;
-            grp.g[i] = GemmShape{d.Mw, d.Nw, d.K, d.ldx, d.ldy, kt64 * G_BK, 8, 0};
-            grp.slab[i] = d.dW; grp.zstride[i] = 0; grp.ldc[i] = d.ldw;
-            grp.first[i] = first;
-            first += ((d.Mw + tile - 1) / tile) * ((d.Nw + tile - 1) / tile);
-        }
-        for (int i = b.nd; i <= TT_GROUP_MAX; i++) grp.first[i] = first;
-        grp.mode = 1;
-        if (t256) {
-            // the tail beyond the last full round of 256 workgroups: K slices + atomics, so that it is a short round of every CU
-            // (CC_WGRAD_TAIL=0 in the lab build: whole tiles only)
-            static const bool tail_on = []() { const char* e = cc_lab_env("CC_WGRAD_TAIL"); return !e || atoi(e) != 0; }();
-            const int full = (first / 256) * 256, rem = first - full;
-            int sp = rem > 0 ? 256 / rem : 1;
-            sp = std::min(sp, std::min(8, std::max(1, (K / H_BK) / 16)));      // at least 16 K-steps per slice
-            // (the slices' slabs: rem x sp x 256 KiB <= 64 MiB of the scratch, which a direct batch does not use otherwise)
-            if (tail_on && full > 0 && sp >= 2 && b.scratch && b.n == 0 && (size_t)rem * sp * H_BM * H_BN * sizeof(float) <= WGRAD_SCRATCH_BYTES) {
-                grp.whole = full; grp.split = sp; grp.tail = b.scratch;
-            }
-        }
-        b.nd = 0;
-        return t256 ? launch_gemm_tt256_group(grp, st) : launch_gemm_tt128_group(grp, st);
-    }
-    double flops = 0.0;
-    for (int i = 0; i < b.nd; i++) flops += 2.0 * b.d[i].Mw * b.d[i].Nw * (double)K;
-    cc_shared::ProfScope _all(cc_shared::SITE_ALL_GEMMS, st, flops);
-    size_t slab_sum = 0;
-    for (int i = 0; i < b.nd; i++) slab_sum += (((size_t)b.d[i].Mw * b.d[i].Nw * sizeof(float)) + 255) & ~size_t(255);
-    const size_t room = WGRAD_SCRATCH_BYTES - b.used;
-    // tile kernel: 256 x 256 (8 waves, fewer / fatter blocks) or 128 x 128; slice count: minimise rounds x (K-steps + fixed per-block
-    // cost), rounds = ceil(blocks / CUs).  CC_WGRAD_TILE / CC_WGRAD_KS override (tuning knobs).
-    static const int force_tile = []() { const char* e = cc_lab_env("CC_WGRAD_TILE"); return e ? atoi(e) : 0; }();
-    static const int force_ks = []() { const char* e = cc_lab_env("CC_WGRAD_KS"); return e ? atoi(e) : 0; }();
-    int best_tile = 128, best_ks = 1;
-    double best_cost = 1e30;
-    for (int tile : {256, 128}) {
-        if (force_tile && tile != force_tile) continue;
-        if (tile == 256 && (K % H_BK)) continue;
-        const int bk = tile == 256 ? H_BK : G_BK, ksteps = K / bk;
-        int total = 0;
-        for (int i = 0; i < b.nd; i++) total += ((b.d[i].Mw + tile - 1) / tile) * ((b.d[i].Nw + tile - 1) / tile);
-        // per K-step cost in units of a 128-tile step (measured: 256-tile step of 32 ~ 0.8 us for 4x the tile area, 128-tile step of 64 ~ 0.65 us)
-        const double step_cost = tile == 256 ? 1.25 : 1.0, fixed = tile == 256 ? 16.0 : 14.0;
-        for (int ks = 1; ks <= 8 && (size_t)ks * slab_sum <= room && ksteps / ks >= 8; ks++) {
-            if (force_ks && ks != force_ks) continue;
-            const int per = (ksteps + ks - 1) / ks;
-            const int rounds = (total * ks + 255) / 256;
-            const double cost = rounds * (per * step_cost + fixed);
-            if (cost < best_cost) { best_cost = cost; best_tile = tile; best_ks = ks; }
-        }
-    }
-    if (best_cost >= 1e30) return CC_ERR_STATE;      // no (tile, slices) fits the scratch: gemm_wgrad's admission check keeps this from happening
-    const int bk = best_tile == 256 ? H_BK : G_BK, ksteps = K / bk;
-    // slices are multiples of 64 deep for both kernels (k_chunk convention of GemmShape)
-    const int kt64 = (K + G_BK - 1) / G_BK;
-    const int per64 = (kt64 + best_ks - 1) / best_ks, ks = (kt64 + per64 - 1) / per64;
-    (void)ksteps;
-    int first = 0;
+    grp.mode = b.direct ? 1 : 0;
+    if (p.whole >= 0) { grp.whole = p.whole; grp.split = p.split; grp.tail = b.scratch; }
     for (int i = 0; i < b.nd; i++) {
         const auto& d = b.d[i];
-        const size_t slab = (size_t)d.Mw * d.Nw;
-        float* sc = b.scratch + b.used / sizeof(float);
-        const int tiles = ((d.Mw + best_tile - 1) / best_tile) * ((d.Nw + best_tile - 1) / best_tile);
         grp.A[i] = d.X; grp.B[i] = d.Y;
-        grp.g[i] = GemmShape{d.Mw, d.Nw, d.K, d.ldx, d.ldy, per64 * G_BK, 8, 0};
-        grp.slab[i] = sc; grp.zstride[i] = slab; grp.ldc[i] = d.Nw;
-        grp.first[i] = first;
-        first += tiles * ks;
-        b.it[b.n++] = WgradBatch::Item{sc, slab, ks, d.Nw, d.dW, d.ldw, slab / 4};
-        b.used += (size_t)ks * slab * sizeof(float);
-        b.used = (b.used + 255) & ~size_t(255);
+        grp.g[i] = GemmShape{d.Mw, d.Nw, d.K, d.ldx, d.ldy, p.k_chunk, 8, 0};
+        if (b.direct) {      // dW += tile in the epilogue
+            grp.slab[i] = d.dW; grp.zstride[i] = 0; grp.ldc[i] = d.ldw;
+        } else {
+            const size_t slab = (size_t)d.Mw * d.Nw;
+            float* sc = b.scratch + b.used / sizeof(float);
+            grp.slab[i] = sc; grp.zstride[i] = slab; grp.ldc[i] = d.Nw;
+            b.it[b.n++] = WgradBatch::Item{sc, slab, p.ks, d.Nw, d.dW, d.ldw, slab / 4};
+            b.used += (size_t)p.ks * slab * sizeof(float);
+            b.used = (b.used + 255) & ~size_t(255);
+        }
     }
-    for (int i = b.nd; i <= TT_GROUP_MAX; i++) grp.first[i] = first;
+    for (int i = 0; i <= TT_GROUP_MAX; i++) grp.first[i] = p.first[i];
     b.nd = 0;
-    return best_tile == 256 ? launch_gemm_tt256_group(grp, st) : launch_gemm_tt128_group(grp, st);
+    return launch_gemm_tt_group(grp, p, st);
 }
 
 int wgrad_flush(WgradBatch& b, hipStream_t st) {
@@ -229,53 +169,20 @@ int gemm_wgrad(ActIn Xa, int ldx, const act_t* Ya, int ldy, int Mw, int Nw, int 
     cc_shared::ProfScope _all(cc_shared::SITE_ALL_GEMMS, st, flops);
     const size_t used = (batch && scratch) ? batch->used : 0;
     float* sc = scratch ? scratch + used / sizeof(float) : nullptr;
-    const size_t fit = scratch ? (WGRAD_SCRATCH_BYTES - used) / (slab * sizeof(float)) : 1;
-    // 256 x 256 kernel with DMA staging + transpose reads (one block per CU; slices sized to fill the CUs once).  It wins from
-    // about 30 GFLOP per launch (GPT-2 weight gradients: +10...17 %); below that the 128 x 128 TT kernel's finer tiles and fewer,
-    // smaller slabs win (mapper weight gradients, K = 5120) — tools/wgrad_bench.py.
-    if (g_gemm_tile_mode != 0 && tt_ok && (K % H_BK) == 0 && (g_gemm_tile_mode == 4 || 2.0 * Mw * Nw * (double)K >= 3e10)) {
-        const int tiles = ((Mw + H_BM - 1) / H_BM) * ((Nw + H_BN - 1) / H_BN);
-        int ks = std::max(1, 256 / tiles);
-        ks = std::min(ks, std::max(1, K / 512));          // at least 16 K-tiles per slice
-        if ((size_t)ks > fit) ks = (int)std::max<size_t>(fit, 1);
-        if (ks == 1) {                                    // wide outputs (lm_head): accumulate straight into dW
-            EpiF32 e{dW, nullptr, ldw, Mw, Nw, 1, 1.0f};
-            return launch_gemm_tt256(X, ldx, Y, ldy, Mw, Nw, K, 1, e, nullptr, st);
-        }
-        EpiF32 e{sc, nullptr, Nw, Mw, Nw, 3, 1.0f};
-        e.zstride = slab;
-        int ks_eff = 1;
-        const int rc = launch_gemm_tt256(X, ldx, Y, ldy, Mw, Nw, K, ks, e, &ks_eff, st);
-        if (rc != CC_OK) return rc;
-        return wgrad_reduce(sc, slab, ks_eff, Nw, dW, ldw, batch, st);
+    const cc_plan::WgradPlan p = cc_plan::plan_wgrad(Mw, Nw, K, tt_ok, scratch != nullptr, WGRAD_SCRATCH_BYTES - used, gemm_modes());
+    if (p.form == cc_plan::WG_TT256_DIRECT) {
+        EpiF32 e{dW, nullptr, ldw, Mw, Nw, 1, 1.0f};
+        return launch_gemm_tt<256>(X, ldx, Y, ldy, Mw, Nw, K, 1, e, nullptr, st);
     }
-    const int tiles = ((Mw + G_BM - 1) / G_BM) * ((Nw + G_BN - 1) / G_BN);
-    // small weight gradients (mapper, K = 5120): 128 x 128 TT kernel, 4-stage DMA pipeline + transpose reads, one block per CU
-    if (g_gemm_tile_mode != 0 && tt_ok && (K % G_BK) == 0 && K >= 1024 && tiles <= 256 && scratch && fit >= 1) {
-
-        int ks = std::max(1, 256 / tiles);
-        ks = std::min(ks, std::max(1, K / (4 * G_BK)));
-        if ((size_t)ks > fit) ks = (int)fit;
-        EpiF32 e{sc, nullptr, Nw, Mw, Nw, 3, 1.0f};
-        e.zstride = slab;
-        int ks_eff = 1;
-        const int rc = launch_gemm_tt128(X, ldx, Y, ldy, Mw, Nw, K, ks, e, &ks_eff, st);
-        if (rc != CC_OK) return rc;
-        return wgrad_reduce(sc, slab, ks_eff, Nw, dW, ldw, batch, st);
-    }
-    int ks = 512 / (tiles > 0 ? tiles : 1);
-    const int kmax = (K + 255) / 256;  // at least 4 K-steps per slice
-    if (ks > kmax) ks = kmax;
-    if (scratch) { if ((size_t)ks > fit) ks = (int)fit; } else ks = 1;
-    if (ks <= 1) return gemm_f32out_op(1, 1, X, ldx, Y, ldy, Mw, Nw, K, dW, ldw, nullptr, 1, 1.0f, 1, st);
+    if (p.form == cc_plan::WG_REG_DIRECT) return gemm_f32out_op(1, 1, X, ldx, Y, ldy, Mw, Nw, K, dW, ldw, nullptr, 1, 1.0f, 1, st);
     // slices z write slab z (EpiF32 store mode; C pointer advanced per z inside the kernel via blockIdx.z * slab)
     EpiF32 e{sc, nullptr, Nw, Mw, Nw, 3, 1.0f};
     e.zstride = slab;
-    int rc = launch_gemm(1, 1, X, ldx, Y, ldy, Mw, Nw, K, ks, e, st);
+    int ks_eff = 1;
+    const int rc = p.form == cc_plan::WG_TT256_SLABS   ? launch_gemm_tt<256>(X, ldx, Y, ldy, Mw, Nw, K, p.ks, e, &ks_eff, st)
+                   : p.form == cc_plan::WG_TT128_SLABS ? launch_gemm_tt<128>(X, ldx, Y, ldy, Mw, Nw, K, p.ks, e, &ks_eff, st)
+                                                       : launch_gemm(1, 1, X, ldx, Y, ldy, Mw, Nw, K, p.ks, e, st, -2, 0, &ks_eff);
     if (rc != CC_OK) return rc;
-    // the launcher may have reduced the slice count (ceil division): recompute it the same way
-    const int kt = (K + G_BK - 1) / G_BK, per = (kt + ks - 1) / ks;
-    const int ks_eff = (kt + per - 1) / per;
     return wgrad_reduce(sc, slab, ks_eff, Nw, dW, ldw, batch, st);
 }
 
@@ -410,10 +317,7 @@ __global__ __launch_bounds__(256) void k_splitk_finish_row(const float* __restri
     }
 }
 
-int skinny_single_min_tiles() {
-    static const int v = []() { const char* e = cc_lab_env("CC_SKINNY_SINGLE"); return e ? atoi(e) : 60; }();   // measured on config 5: 171 (never) / 165 (90) / 159 (60) / 160 (20) ms per decode batch
-    return v;
-}
+int skinny_single_min_tiles() { return cc_plan::gemm_knobs().skinny_single; }
 bool gemm_nt_skinny_can_fuse(int M, int N, int K, size_t scratch_bytes) {
     return M > 0 && N > 0 && (N & 7) == 0 && N <= 3072 && (K % G_BK) == 0 && scratch_bytes >= (size_t)M * N * sizeof(float);
 }
@@ -446,45 +350,20 @@ __global__ __launch_bounds__(256) void k_deepk_finish_lm(const float* __restrict
 int gemm_nt_deepk(ActIn Aa, int lda, const op16_t* B, int ldb, int M, int N, int K, act_t* out16, int ldo, float* scratch,
                   size_t scratch_bytes, Call& cx, const LmFix* fix) {
     const hipStream_t st = cx.st;
-    static const int knob = []() { const char* e = cc_lab_env("CC_DEEPK"); return e ? atoi(e) : -1; }();   // 0 = off, n > 0 = force n slices
-    if (knob == 0 || g_gemm_tile_mode == 0 || !scratch || (N & 7) || (ldo & 7) || (K % 64) || (lda & 7) || (ldb & 7)) return CC_ERR_SHAPE;
-    const long tiles = (long)((M + H_BM - 1) / H_BM) * ((N + H_BN - 1) / H_BN);
-    const size_t slab = (size_t)M * N;
-    int ks = knob > 0 ? knob : (int)(256 / (tiles > 0 ? tiles : 1));
-    const size_t fit = scratch_bytes / (slab * sizeof(float));
-    if ((size_t)ks > fit) ks = (int)fit;
-    if (ks > K / 2048) ks = K / 2048;                      // slices of at least 64 K-steps: below that the slab pass costs what the idle CUs gain
-    if (ks < 2 || tiles > 128) return CC_ERR_SHAPE;
+    const cc_plan::DeepKPlan p = cc_plan::plan_deepk(M, N, K, lda, ldb, ldo, scratch != nullptr, scratch_bytes, gemm_modes(), cc_plan::gemm_knobs());
+    if (p.status != CC_OK) return p.status;
     cc_shared::ProfScope _all(cc_shared::SITE_ALL_GEMMS, st, 2.0 * M * N * (double)K);
     const op16_t* A;
     const int rca = nt_operand(cx, Aa, 0, 0, M, lda, ldb, K, A);
     if (rca != CC_OK) return rca;
+    // (the split-bf16 slice search's refusal: kept apart from p.status so that, as before, an operand error is reported ahead of it)
+    if (p.status_late != CC_OK) return p.status_late;
+    const size_t slab = (size_t)M * N;
     EpiF32 e{scratch, nullptr, N, M, N, 3, 1.0f};
     e.zstride = slab;
-    // tile order: an XCD's share of the grid (tiles / 8 consecutive logical tiles per K slice) should hold whole row panels, so that the
-    // column tiles of a panel run side by side on one L2 and the deep A panel is fetched once, not once per column tile
-    int tile = 4, tiles_n = (N + H_BN - 1) / H_BN;
-    long tl = tiles;
-    if (kX3 && x3_fused_on() && (K % (3 * H_BK)) == 0) {
-        // bf16x3: the fused two-stage form lives on the 256 x 192 kernel (gemm_stag256_body<X3F>): its tile count, and the slice count
-        // that minimises rounds x chunks per slice (whole rounds of 256 workgroups)
-        tile = 3;
-        tiles_n = (N + 191) / 192;
-        tl = (long)((M + H_BM - 1) / H_BM) * tiles_n;
-        const int nc = K / (3 * H_BK);
-        long best = -1;
-        int best_ks = ks;
-        for (int k2 = 1; k2 <= 8 && (size_t)k2 <= fit && k2 <= nc / 32; k2++) {
-            const long cost = ((tl * k2 + 255) / 256) * ((nc + k2 - 1) / k2);
-            if (best < 0 || cost < best) { best = cost; best_ks = k2; }
-        }
-        ks = best_ks;
-        if (ks < 2) return CC_ERR_SHAPE;
-    }
-    const int gm = std::max(1, (int)((tl + 7) / 8) / tiles_n);
-    const int rc = launch_gemm(0, 0, A, lda, B, ldb, M, N, K, ks, e, st, tile, gm);
+    int ks_eff = 1;
+    const int rc = launch_gemm(0, 0, A, lda, B, ldb, M, N, K, p.ks, e, st, p.tile, p.group_m, &ks_eff);
     if (rc != CC_OK) return rc;
-    const int kt = K / G_BK, per = (kt + ks - 1) / ks, ks_eff = (kt + per - 1) / per;
     const size_t n8 = (size_t)M * (N >> 3);
     if (fix)
         hipLaunchKernelGGL(k_deepk_finish_lm, dim3((int)std::min<size_t>((n8 + 255) / 256, 2048)), dim3(256), 0, st, scratch, slab, ks_eff, M, N, *fix,
@@ -511,71 +390,35 @@ int gemm_nt_skinny(ActIn Aa, int lda, const op16_t* B, int ldb, int M, int N, in
     const op16_t* A;
     const int rca = nt_operand(cx, Aa, 0, 0, M, lda, ldb, K, A);
     if (rca != CC_OK) return rca;
-    const int tiles = ((M + G_BM - 1) / G_BM) * ((N + G_BN - 1) / G_BN);
     const size_t slab = (size_t)M * N;
-    const bool can_slab = scratch && slab && (K % G_BK) == 0 && scratch_bytes >= slab * sizeof(float);
     const bool fused = fuse && (fuse->ln_out16 || fuse->kcache);
     const op16_t* bimg = (fuse && !kX3) ? fuse->bimg : nullptr;
-    // decode-sized M: 64 x 64 tiles (gemm_nt_s64_kernel) put 2.5-5x the blocks on the chip; a block's K loop is bound by what one CU
-    // can pull through its L2->LDS path (~57 GB/s measured), so the job is to have every CU pulling
-    const bool s64 = g_gemm_s64 != 0 && (K % G_BK) == 0 && M <= 640 && tiles <= 256 && (lda & 7) == 0 && (ldb & 7) == 0;
-    int ks;
-    if (s64) {
-        const int t64 = ((M + 63) / 64) * ((N + 63) / 64);
-        ks = t64 >= 160 ? 1 : 256 / t64;                    // K slices only while they add blocks up to one per CU
-        const int kmax = K / (4 * G_BK);
-        if (ks > kmax) ks = kmax;
-    } else {
-        ks = 384 / (tiles > 0 ? tiles : 1);
-        const int kmax = K / (2 * G_BK);                    // at least 2 K-steps per slice
-        if (ks > kmax) ks = kmax;
-        // wide-enough grids go single-pass with the epilogue fused into the GEMM (4-stage small-grid kernel): one launch instead of two
-        if (!fused && tiles >= skinny_single_min_tiles()) ks = 1;
-    }
-    if (ks < 1) ks = 1;
-    if (can_slab) { const size_t fit = scratch_bytes / (slab * sizeof(float)); if ((size_t)ks > fit) ks = (int)fit; }
-    // K split over the waves of a block (gemm_nt_s64kw_kernel): pays from ~14 K-tiles per block, and only on grids of at most one
-    // block per CU (320 x 3072 x 1024: 9.0 -> 8.3 us, 320 x 1024 x 4096 in one slice: 23.6 -> 18.4 us; c_fc's 320 blocks: no gain)
-    // (round 5) a single-slice grid of 257-320 64 x 64 tiles that is <= 256 tiles of 80 x 64 (c_fc at M = 320: 5 x 64 -> 4 x 64) takes the
-    // 80-row form of the same kernel: one block per CU instead of two on a quarter of them (CC_SKINNY_80=0 in the lab build: off)
-    static const bool s80_on = []() { const char* e = cc_lab_env("CC_SKINNY_80"); return !e || atoi(e) != 0; }();
-    auto s64_form = [&](int slices) {
-        const int t64 = ((M + 63) / 64) * ((N + 63) / 64), t80 = ((M + 79) / 80) * ((N + 63) / 64);
-        if (g_gemm_s64 == 1 || K / G_BK / (slices > 0 ? slices : 1) < 14) return 1;
-        if ((long)t64 * slices <= 256) return 3;
-        return (s80_on && slices <= 1 && t80 <= 256) ? 4 : 1;      // (no weight-image variant: both operand paths run this kernel)
-    };
-    if (!can_slab || (ks <= 1 && !fused)) {
-        if (fused) return CC_ERR_SHAPE;                    // callers only request fusion when the slab path is available
-        if (s64) {
-            const int form = s64_form(1);
-            if (res) { EpiResid e{out32, res, bias, ldo, M, N}; return launch_gemm_s64(A, lda, B, ldb, M, N, K, 1, form, e, nullptr, st, bimg); }
-            if (out16) {
-                // decode's c_attn (plain) and c_fc (gelu_new) launches: the functors without run-time switches (round 6)
-                static const bool spec_on = []() { const char* v = cc_lab_env("CC_EPI_SPEC"); return !v || atoi(v) != 0; }();
-                if (spec_on && act == 0) { EpiBF16Plain e{out16, bias, ldo, M, N}; return launch_gemm_s64(A, lda, B, ldb, M, N, K, 1, form, e, nullptr, st, bimg); }
-                if (spec_on && act == 2) { EpiBF16T<2, 0> e{out16, nullptr, bias, ldo, M, N, 2}; return launch_gemm_s64(A, lda, B, ldb, M, N, K, 1, form, e, nullptr, st, bimg); }
-                EpiBF16 e{out16, nullptr, bias, ldo, M, N, act};
-                return launch_gemm_s64(A, lda, B, ldb, M, N, K, 1, form, e, nullptr, st, bimg);
-            }
-            EpiF32 e{out32, bias, ldo, M, N, 0, 1.0f};
-            return launch_gemm_s64(A, lda, B, ldb, M, N, K, 1, form, e, nullptr, st, bimg);
+    const cc_plan::SkinnyPlan p = cc_plan::plan_skinny(M, N, K, lda, ldb, scratch != nullptr, scratch_bytes, fused, res != nullptr, out16 != nullptr, act,
+                                                       gemm_modes(), cc_plan::gemm_knobs());
+    if (p.status != CC_OK) return p.status;
+    // one GEMM launch with functor e: on the 64-row kernels in the plan's form, else through the NT launcher
+    // (the two functors without run-time switches exist on the 64-row kernels only)
+    int ks_eff = 1;
+    auto run64 = [&](const auto& e) { return launch_gemm_s64(A, lda, B, ldb, M, N, K, p.ks, p.form, e, &ks_eff, st, bimg); };
+    auto run = [&](const auto& e) { return p.s64 ? run64(e) : launch_gemm(0, 0, A, lda, B, ldb, M, N, K, p.ks, e, st, -2, 0, &ks_eff); };
+    if (!p.slab) {
+        switch (p.functor) {
+        case cc_plan::SK_RESID: return run(EpiResid{out32, res, bias, ldo, M, N});
+        case cc_plan::SK_PLAIN: return run64(EpiBF16Plain{out16, bias, ldo, M, N});
+        case cc_plan::SK_GELU: return run64(EpiBF16T<2, 0>{out16, nullptr, bias, ldo, M, N, 2});
+        case cc_plan::SK_BF16: return run(EpiBF16{out16, nullptr, bias, ldo, M, N, act});
+        default: return run(EpiF32{out32, bias, ldo, M, N, 0, 1.0f});
         }
-        if (res) { EpiResid e{out32, res, bias, ldo, M, N}; return launch_gemm(0, 0, A, lda, B, ldb, M, N, K, 1, e, st); }
-        if (out16) { EpiBF16 e{out16, nullptr, bias, ldo, M, N, act}; return launch_gemm(0, 0, A, lda, B, ldb, M, N, K, 1, e, st); }
-        EpiF32 e{out32, bias, ldo, M, N, 0, 1.0f};
-        return launch_gemm(0, 0, A, lda, B, ldb, M, N, K, 1, e, st);
     }
     EpiF32 e{scratch, nullptr, N, M, N, 3, 1.0f};
     e.zstride = slab;
-    int rc = s64 ? launch_gemm_s64(A, lda, B, ldb, M, N, K, ks, s64_form(ks), e, nullptr, st, bimg) : launch_gemm(0, 0, A, lda, B, ldb, M, N, K, ks, e, st);
+    const int rc = run(e);
     if (rc != CC_OK) return rc;
-    const int kt = K / G_BK, per = (kt + ks - 1) / ks, ks_eff = (kt + per - 1) / per;
-    if (N <= 3072 && (N & 3) == 0) {
+    if (p.finish == cc_plan::FIN_REFUSE) return CC_ERR_SHAPE;
+    if (p.finish == cc_plan::FIN_ROW) {
         SkinnyFuse f = fuse ? *fuse : SkinnyFuse{};
         hipLaunchKernelGGL(k_splitk_finish_row, dim3(M), dim3(256), 0, st, scratch, slab, ks_eff, M, N, bias, act, res, out32, out16, ldo, f);
     } else {
-        if (fused) return CC_ERR_SHAPE;
         const size_t n8 = (size_t)M * (N >> 3);
         hipLaunchKernelGGL(k_splitk_finish, dim3((int)std::min<size_t>((n8 + 255) / 256, 2048)), dim3(256), 0, st, scratch, slab, ks_eff, M, N, bias,
                            act, res, out32, out16, ldo);

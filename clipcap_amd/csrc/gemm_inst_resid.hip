@@ -10,10 +10,7 @@ int gemm_resid(int al, int bl, ActIn A, int lda, const op16_t* B, int ldb, int M
     const int rca = nt_operand(cx, A, al, bl, M, lda, ldb, K, A16);
     if (rca != CC_OK) return rca;
     EpiResid e{out, res, bias, ld, M, N, drop};
-    // accumulators initialised from the residual (256-row kernels only read the flag): not with residual dropout, whose mask scales
-    // acc + bias but not the residual; CC_RESID_INIT=0 is the A/B switch
-    static const bool init_ok = []() { const char* v = cc_lab_env("CC_RESID_INIT"); return !v || atoi(v) != 0; }();
-    e.acc_init = init_ok && !drop.thresh;
+    e.acc_init = cc_plan::pick_resid_init(drop.thresh != 0, cc_plan::gemm_knobs());
     return launch_gemm(al, bl, A16, lda, B, ldb, M, N, K, 1, e, st);
 }
 }  // namespace CC_NS
