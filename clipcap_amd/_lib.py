@@ -105,6 +105,8 @@ SIGNATURES = {
     "cc_decode_reorder": (_I, [_GC, _I, _I, _I, _I, _P, _P, _P, _P]),
     "cc_beam_step": (_I, [_I, _I, _I, _P, _L, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cc_beam_ws_bytes": (_L, [_I, _I, _I]),
+    "cc_beam_group_ws_bytes": (_L, [_I, _I, _I, _I]),
+    "cc_beam_group_step": (_I, [_I, _I, _I, _I, _P, _L, _F, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cc_logits_constrain": (_I, [_P, _I, _I, _L, _P, _I, _P, _I, _L, _I, _I, _I, _P, _I, _P, _P]),
     "cc_embed_tokens": (_I, [_GC, _I, _P, _P, _P, _P]),
     "cc_embed_tokens_bwd": (_I, [_GC, _I, _P, _P, _P, _P]),

@@ -549,6 +549,219 @@ __global__ __launch_bounds__(256) void k_beam_fused(const float* __restrict__ lo
     }
 }
 
+// ---- diverse beam search: beam groups with a Hamming penalty (Vijayakumar et al., 2016; not in the reference) -------------------------
+// The `beam` rows of a sample are split into G beam groups of W consecutive rows; one step advances the groups one after the other, and a
+// candidate of beam group g whose token v was picked c(v) times AT THIS STEP by the beam groups before it loses penalty * c(v) of its
+// log-probability (before the length normalisation; a stopped beam's token-0 continuation is neither penalised nor counted).  Apart from
+// that a beam group's update is the one above on its own W rows: same arithmetic, tie rule and commit.
+//   k_beam_rowstats      : once for all rows, as above
+//   k_beam_group_partial : per beam group, grid (sample, chunk): top-W of a slice of the group's W * V candidates (k_beam_partial's two
+//                          passes and its insertion-list overflow path, with the row offset and the picks of the earlier groups)
+//   k_beam_group_final   : per beam group, one block per sample: merges the chunk winners, commits the group's W slots and leaves its
+//                          picks in the workspace for the groups after it
+// The launches are stream-ordered: beam group g + 1 starts after beam group g has written its picks.  The picks of the earlier groups
+// (at most beam - W ids) are loaded into LDS once per block, and a candidate is looked up in them only after the cheap key says it could
+// be kept: the penalty only lowers a value, so the unpenalised key stays an upper bound.
+constexpr int PICK_NONE = -1;      // a slot whose source beam had stopped: its token 0 is padding, not a pick
+
+__device__ __forceinline__ int picked_before(const int* picks, int n, int v) {
+    int c = 0;
+    for (int i = 0; i < n; i++) c += picks[i] == v ? 1 : 0;
+    return c;
+}
+// beam_val with the Hamming penalty: c = picks of token v by the earlier beam groups.  c == 0 applies no operation at all: one beam group
+// is bit-identical to beam_val.
+template <bool TEMP>
+__device__ __forceinline__ float beam_val_div(const BeamRow& g, int v, float xraw, float inv_temp, int first, int c, float penalty) {
+    if (g.st) return beam_stopped(g, v, first);
+    float lp = logf(expf((TEMP ? xraw * inv_temp : xraw) - g.m) / g.sum);
+    if (c > 0) lp -= penalty * (float)c;
+    return first ? lp : (g.sc + lp) / g.len;
+}
+// the same for the cheap key (an image of beam_val_div within ~1e-6, as beam_key is of beam_val)
+template <bool TEMP>
+__device__ __forceinline__ float beam_key_div(const BeamRow& g, int v, float xraw, float inv_temp, int first, int c, float penalty) {
+    if (g.st) return beam_stopped(g, v, first);
+    float d = ((TEMP ? xraw * inv_temp : xraw) - g.m) - g.lsum;
+    if (c > 0) d -= penalty * (float)c;
+    return first ? d : (g.sc + d) * (1.0f / g.len);
+}
+
+// TW = compile-time width of a beam group (0: run-time width).  `beam`: rows per sample; row0 = first row of this beam group inside the
+// sample; picks: int [S][beam], entries [0, row0) of a sample are the earlier groups' picks of this step.
+template <int TW>
+__global__ __launch_bounds__(256) void k_beam_group_partial(const float* __restrict__ logits, size_t ldl, int beam, int row0, int width_rt, int V,
+                                                            float inv_temp, float penalty, int first, const float* __restrict__ rs,
+                                                            const float* __restrict__ scores, const float* __restrict__ seq_len,
+                                                            const unsigned char* __restrict__ stopped, const int* __restrict__ picks,
+                                                            float* __restrict__ pval, int* __restrict__ pidx) {
+    __shared__ float red[8];
+    __shared__ int redi[8];
+    __shared__ float cval[TW > 0 ? 1 : 256 * BEAM_MAX];          // candidate arrays: run-time-width fallback only
+    __shared__ int cidx[TW > 0 ? 1 : 256 * BEAM_MAX];
+    __shared__ float sel_v[BEAM_MAX];
+    __shared__ int sel_i[BEAM_MAX];
+    __shared__ int s_pick[BEAM_MAX];
+    constexpr int LB = TW > 0 ? TW : BEAM_MAX;
+    const int width = TW > 0 ? TW : width_rt;
+    const int s = blockIdx.x, ch = blockIdx.y, tid = threadIdx.x;
+    const int nrows = first ? 1 : width;
+    const int total = nrows * V;
+    const int per = (total + BEAM_CHUNKS - 1) / BEAM_CHUNKS;
+    const int lo = ch * per, hi = min(total, lo + per);
+    const int r0 = s * beam + (first ? 0 : row0);                 // the first step reads row 0 of the sample in every beam group
+    const float* lg = logits + (size_t)r0 * ldl;
+    const int npick = row0;                                       // row0 < beam <= BEAM_MAX
+    if (tid < npick) s_pick[tid] = picks[s * beam + tid];
+    __syncthreads();
+    // scan(f): as in k_beam_partial, over the beam group's rows (b: row inside the group, idx = b * V + v)
+    auto scan = [&](auto&& f) {
+        for (int b = lo / V; b < nrows && b * V < hi; b++) {
+            const int seg_lo = max(lo, b * V), seg_hi = min(hi, (b + 1) * V);
+            BeamRow g;
+            g.st = !first && stopped[r0 + b];
+            g.m = rs[2 * (r0 + b)]; g.sum = rs[2 * (r0 + b) + 1];
+            g.lsum = logf(g.sum);
+            g.sc = first ? 0.f : scores[r0 + b];
+            g.len = first ? 1.f : (seq_len[r0 + b] + (g.st ? 0.f : 1.f));
+            const float* row = lg + (size_t)b * ldl - (size_t)b * V;      // row[idx] = lg[b * ldl + (idx - b V)]
+            constexpr int SU = 8;
+            for (int idx0 = seg_lo + tid; idx0 < seg_hi; idx0 += 256 * SU) {
+                float xs[SU];
+#pragma unroll
+                for (int u = 0; u < SU; u++) xs[u] = g.st ? 0.f : row[min(idx0 + u * 256, seg_hi - 1)];
+#pragma unroll
+                for (int u = 0; u < SU; u++) {
+                    const int idx = idx0 + u * 256;
+                    if (idx < seg_hi) f(idx, idx - b * V, g, xs[u]);
+                }
+            }
+        }
+    };
+    auto count = [&](const BeamRow& g, int v) { return (g.st || npick == 0) ? 0 : picked_before(s_pick, npick, v); };
+    bool done = false;
+    if constexpr (TW > 0) {
+        // k_beam_partial's two passes.  Pass 1 keeps the thread maximum of the PENALISED key (looked up only when the unpenalised key would
+        // raise the maximum), so its TW-th largest stays a lower bound of the chunk's TW-th best value; pass 2 filters on the unpenalised key,
+        // an upper bound of the value.
+        constexpr int FCAP = 1024;
+        __shared__ float fcv[FCAP];
+        __shared__ int fci[FCAP];
+        __shared__ int fcount;
+        float tmax = -INFINITY;
+        scan([&](int, int v, const BeamRow& g, float xraw) {
+            const float key = beam_key<true>(g, v, xraw, inv_temp, first);
+            if (key > tmax) {
+                const int c = count(g, v);
+                tmax = fmaxf(tmax, c ? beam_key_div<true>(g, v, xraw, inv_temp, first, c, penalty) : key);
+            }
+        });
+        if (tid == 0) fcount = 0;
+        const float thr = kth_bound<TW>(tmax, red);
+        scan([&](int idx, int v, const BeamRow& g, float xraw) {
+            const float key = beam_key<true>(g, v, xraw, inv_temp, first);
+            if (key > -INFINITY && key + 1e-3f >= thr) {
+                const int pos = atomicAdd(&fcount, 1);
+                if (pos < FCAP) { fcv[pos] = beam_val_div<true>(g, v, xraw, inv_temp, first, count(g, v), penalty); fci[pos] = idx; }
+            }
+        });
+        __syncthreads();
+        if (fcount <= FCAP) {
+            pick_from_list<256>(fcv, fci, fcount, TW, red, redi, sel_v, sel_i);
+            done = true;
+        }
+    }
+    if (!done) {
+        // sorted insertion list per thread: any width (TW = 0: run-time width), and the overflow path of the list above (e.g. all logits equal)
+        float lv[LB];
+        int li[LB];
+#pragma unroll
+        for (int k = 0; k < LB; k++) { lv[k] = -INFINITY; li[k] = 0x7fffffff; }
+        scan([&](int idx, int v, const BeamRow& g, float xraw) {
+            if (!g.st) {
+                const float worst = TW > 0 ? lv[LB - 1] : lv[width - 1];
+                if (beam_key<true>(g, v, xraw, inv_temp, first) + 1e-3f < worst) return;
+            }
+            const float val = beam_val_div<true>(g, v, xraw, inv_temp, first, count(g, v), penalty);
+            if constexpr (TW > 0) {
+                if (cand_better(val, idx, lv[LB - 1], li[LB - 1])) {
+                    lv[LB - 1] = val; li[LB - 1] = idx;
+#pragma unroll
+                    for (int k = LB - 1; k > 0; k--) {
+                        if (cand_better(lv[k], li[k], lv[k - 1], li[k - 1])) {
+                            const float tv = lv[k]; lv[k] = lv[k - 1]; lv[k - 1] = tv;
+                            const int ti = li[k]; li[k] = li[k - 1]; li[k - 1] = ti;
+                        }
+                    }
+                }
+            } else {
+                if (cand_better(val, idx, lv[width - 1], li[width - 1])) {
+                    int k = width - 1;
+                    while (k > 0 && cand_better(val, idx, lv[k - 1], li[k - 1])) { lv[k] = lv[k - 1]; li[k] = li[k - 1]; k--; }
+                    lv[k] = val; li[k] = idx;
+                }
+            }
+        });
+        if constexpr (TW > 0) {
+            // every thread's list is sorted, so the block's next best is the best list HEAD; the owner pops its list
+            for (int k = 0; k < TW; k++) {
+                float bv = lv[0];
+                int bi = li[0];
+                argmax_round<4>(k, bv, bi, red, redi, sel_v, sel_i);
+                if (li[0] == bi && bi != 0x7fffffff) {              // flat indices are unique: exactly one owner
+#pragma unroll
+                    for (int q = 0; q + 1 < LB; q++) { lv[q] = lv[q + 1]; li[q] = li[q + 1]; }
+                    lv[LB - 1] = -INFINITY; li[LB - 1] = 0x7fffffff;
+                }
+            }
+            __syncthreads();
+        } else {
+            for (int k = 0; k < width; k++) { cval[tid * width + k] = lv[k]; cidx[tid * width + k] = li[k]; }
+            __syncthreads();
+            pick_from_list<256>(cval, cidx, 256 * width, width, red, redi, sel_v, sel_i);
+        }
+    }
+    if (tid < width) {
+        pval[((size_t)s * BEAM_CHUNKS + ch) * width + tid] = sel_v[tid];
+        pidx[((size_t)s * BEAM_CHUNKS + ch) * width + tid] = sel_i[tid];
+    }
+}
+
+// k_beam_final for one beam group: slots and source rows are row0 .. row0 + width - 1 of the sample; src_row = the source row's index
+// inside the SAMPLE (what cc_beam_advance expects; 0 on the first step, which reads row 0), picks[slot] = the token, or PICK_NONE when
+// the source beam had stopped.
+__global__ __launch_bounds__(64) void k_beam_group_final(int beam, int row0, int width, int V, int first, int stop_token, const float* __restrict__ pval,
+                                                         const int* __restrict__ pidx, float* __restrict__ scores, float* __restrict__ seq_len,
+                                                         unsigned char* __restrict__ stopped, int* __restrict__ next_tok, int* __restrict__ src_row,
+                                                         int* __restrict__ picks) {
+    __shared__ float red[2];
+    __shared__ int redi[2];
+    __shared__ float cval[BEAM_CHUNKS * BEAM_MAX];
+    __shared__ int cidx[BEAM_CHUNKS * BEAM_MAX];
+    __shared__ float sel_v[BEAM_MAX];
+    __shared__ int sel_i[BEAM_MAX];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const int ncand = BEAM_CHUNKS * width;
+    for (int c = tid; c < ncand; c += 64) { cval[c] = pval[(size_t)s * ncand + c]; cidx[c] = pidx[(size_t)s * ncand + c]; }
+    __syncthreads();
+    pick_from_list<64>(cval, cidx, ncand, width, red, redi, sel_v, sel_i);
+    // the source beams' state goes to registers before the barrier, the slots are written after it
+    const int idx = (tid < width && sel_i[tid] != 0x7fffffff) ? sel_i[tid] : 0;      // fewer than `width` candidates: row 0, token 0 at -inf
+    const int b = first ? 0 : row0 + idx / V, v = idx % V;
+    int st = 0;
+    float len = 1.f;
+    if (tid < width && !first) {
+        st = stopped[s * beam + b];
+        len = seq_len[s * beam + b] + (st ? 0.f : 1.f);
+    }
+    __syncthreads();
+    if (tid < width) {
+        const int o = s * beam + row0 + tid;
+        beam_commit(o, sel_v[tid], b, v, first, stop_token, len, st, scores, seq_len, stopped, next_tok, src_row);
+        picks[o] = st ? PICK_NONE : v;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -615,6 +828,51 @@ int CC_API(cc_beam_step_p)(int32_t S, int32_t beam, int32_t V, const float* logi
 #undef BEAM_PARTIAL
     hipLaunchKernelGGL(k_beam_final, dim3(S), dim3(64), 0, st, beam, V, first, stop_token, pval, pidx, scores, seq_lengths, has_stopped, next_tokens,
                        src_rows);
+    return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
+}
+
+// workspace of cc_beam_group_step: row statistics | chunk winners of ONE beam group (values, flat indices) | this step's picks
+int64_t CC_API(cc_beam_group_ws_bytes)(int32_t S, int32_t beam, int32_t groups, int32_t V) {
+    (void)V;
+    if (S <= 0 || beam <= 0 || beam > BEAM_MAX || groups < 1 || beam % groups) return CC_ERR_SHAPE;
+    const int width = beam / groups;
+    return (int64_t)S * beam * 2 * sizeof(float) + (int64_t)S * BEAM_CHUNKS * width * (sizeof(float) + sizeof(int)) + (int64_t)S * beam * sizeof(int) + 512;
+}
+
+int CC_API(cc_beam_group_step)(int32_t S, int32_t beam, int32_t groups, int32_t V, const float* logits, int64_t ldl, float temperature,
+                               float diversity_penalty, int32_t first, int32_t stop_token, float* scores, float* seq_lengths, uint8_t* has_stopped,
+                               int32_t* next_tokens, int32_t* src_rows, void* ws, void* stream) {
+    if (S < 0 || beam <= 0 || beam > BEAM_MAX || groups < 1 || beam % groups || V <= 0 || !logits || ldl < V || !scores || !seq_lengths ||
+        !has_stopped || !next_tokens || !src_rows || !ws || !(diversity_penalty >= 0.f && diversity_penalty <= 3.402823466e38f))
+        return CC_ERR_ARG;
+    if (S == 0) return CC_OK;
+    hipStream_t st = S_(stream);
+    const int width = beam / groups;
+    const float inv_temp = 1.0f / (temperature > 0.f ? temperature : 1.0f);   // base.py:83
+    float* rs = static_cast<float*>(ws);
+    float* pval = rs + (size_t)S * beam * 2;
+    int* pidx = reinterpret_cast<int*>(pval + (size_t)S * BEAM_CHUNKS * width);
+    int* picks = pidx + (size_t)S * BEAM_CHUNKS * width;
+    if ((ldl & 3) || ((uintptr_t)logits & 15))
+        hipLaunchKernelGGL(k_beam_rowstats<false>, dim3(S * beam), dim3(512), 0, st, logits, (size_t)ldl, V, inv_temp, rs);
+    else
+        hipLaunchKernelGGL(k_beam_rowstats<true>, dim3(S * beam), dim3(512), 0, st, logits, (size_t)ldl, V, inv_temp, rs);
+    for (int g = 0; g < groups; g++) {
+        const int row0 = g * width;
+#define BEAM_GROUP_PARTIAL(TW) hipLaunchKernelGGL(k_beam_group_partial<TW>, dim3(S, BEAM_CHUNKS), dim3(256), 0, st, logits, (size_t)ldl, beam, row0, width, V, inv_temp, diversity_penalty, first, rs, scores, seq_lengths, has_stopped, picks, pval, pidx)
+        switch (width) {
+            case 1: BEAM_GROUP_PARTIAL(1); break;
+            case 2: BEAM_GROUP_PARTIAL(2); break;
+            case 3: BEAM_GROUP_PARTIAL(3); break;
+            case 4: BEAM_GROUP_PARTIAL(4); break;
+            case 5: BEAM_GROUP_PARTIAL(5); break;
+            case 8: BEAM_GROUP_PARTIAL(8); break;
+            default: BEAM_GROUP_PARTIAL(0); break;
+        }
+#undef BEAM_GROUP_PARTIAL
+        hipLaunchKernelGGL(k_beam_group_final, dim3(S), dim3(64), 0, st, beam, row0, width, V, first, stop_token, pval, pidx, scores, seq_lengths,
+                           has_stopped, next_tokens, src_rows, picks);
+    }
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 

@@ -933,6 +933,30 @@ def beam_step(logits: torch.Tensor, samples: int, beam: int, temperature: float,
     return nt, sr
 
 
+def beam_group_buffers(device, samples: int, beam: int, groups: int, V: int) -> tuple:
+    """beam_buffers for beam_group_step: (next_tokens, src_rows, scratch of cc_beam_group_ws_bytes).  Owned by ONE decode, like those."""
+    nbytes = _lib.lib().cc_beam_group_ws_bytes(samples, beam, groups, V)
+    check(nbytes, "cc_beam_group_ws_bytes")
+    return (torch.empty(samples * beam, dtype=torch.int32, device=device), torch.empty(samples * beam, dtype=torch.int32, device=device),
+            torch.empty(nbytes, dtype=torch.uint8, device=device))
+
+
+def beam_group_step(logits: torch.Tensor, samples: int, beam: int, groups: int, temperature: float, diversity_penalty: float, first: bool,
+                    stop_token: int, scores: torch.Tensor, seq_lengths: torch.Tensor, has_stopped: torch.Tensor, bufs: Optional[tuple] = None):
+    """One device-side update of diverse beam search (cc_beam_group_step; Vijayakumar et al., 2016): the ``beam`` rows of every sample are
+    ``groups`` beam groups of beam // groups consecutive rows, advanced one after the other; a token that earlier beam groups picked at
+    this step c times loses ``diversity_penalty`` * c of its log-probability in the later ones.  Arguments, in-place state and the result
+    (next_tokens, src_rows — the source row inside the sample) are beam_step's; ``bufs``: the caller's beam_group_buffers(...).
+    groups == 1 is beam_step without partials, bit for bit."""
+    dev = logits.device
+    V = logits.shape[1]
+    nt, sr, ws = bufs if bufs is not None else beam_group_buffers(dev, samples, beam, groups, V)
+    check(_lib.lib().cc_beam_group_step(samples, beam, groups, V, _p(logits), logits.stride(0), float(temperature), float(diversity_penalty),
+                                       int(first), int(stop_token), _p(scores), _p(seq_lengths), _p(has_stopped), _p(nt), _p(sr), _p(ws),
+                                       _stream(dev)), "cc_beam_group_step")
+    return nt, sr
+
+
 def constrain_logits(logits: torch.Tensor, *, lpart: Optional[tuple] = None, history: Optional[torch.Tensor] = None, hist_len: int = 0,
                      no_repeat_ngram: int = 0, ban_token: int = -1, suppress: Optional[torch.Tensor] = None,
                      skip_rows: Optional[torch.Tensor] = None) -> torch.Tensor:

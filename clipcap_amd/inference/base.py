@@ -11,6 +11,13 @@ Not in the reference: every decoder takes three keyword-only constraints, all of
   * ``suppress_tokens``: ids that are never generated.
 A ban sets the logit to -inf before the softmax, temperature, penalties and filters (cc_logits_constrain, one launch per step, which also
 repairs the lm_head partials the fused beam update reads); with all three off a decoder launches exactly what it launched without them.
+
+Not in the reference either: diverse beam search (Vijayakumar et al., 2016) on the beam decoders, keyword-only and off by default —
+  * ``num_beam_groups`` = G > 1: the beam_size beams are G beam groups of beam_size / G beams, advanced one after the other inside a step;
+  * ``diversity_penalty`` > 0: what a token's log-probability loses in a beam group per earlier beam group pick of that token at this step
+    (cc_beam_group_step; the two come together);
+  * ``num_return_sequences`` = n (generate_beam): the n best beams of every prefix instead of the best one.
+With G == 1 the beam decoders launch exactly what they launched without these options.
 """
 from __future__ import annotations
 
@@ -18,9 +25,10 @@ from typing import Callable, List, Optional, Tuple, Union
 
 import torch
 
-from clipcap_amd.engine import DecodeSession, beam_buffers, beam_step, constrain_logits, embed_tokens, sample_step
+from clipcap_amd.engine import (DecodeSession, beam_buffers, beam_group_buffers, beam_group_step, beam_step, constrain_logits, embed_tokens,
+                                sample_step)
 from clipcap_amd.inference.utils import (nucleus_distribution, repetition_penalty_apply, sentence_length_penalty_apply,  # noqa: F401
-                                         top_k_top_p_filtering, validate_constraints)
+                                         top_k_top_p_filtering, validate_beam_groups, validate_constraints)
 
 
 def _persistent_decode_on() -> bool:
@@ -64,7 +72,8 @@ def _bans(V: int, stop_token: int, no_repeat_ngram_size: int, min_length: int, s
 @torch.no_grad()
 def generate_beam_rounds(model, embeds: torch.Tensor, beam_size: int = 5, entry_length: int = 67, temperature: float = 1.0,
                          stop_token: int = 50256, rounds: int = 1, *, no_repeat_ngram_size: int = 0, min_length: int = 0,
-                         suppress_tokens=None) -> List[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
+                         suppress_tokens=None, num_beam_groups: int = 1,
+                         diversity_penalty: float = 0.0) -> List[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
     """Token-level beam search for a batch of prefixes, embeds fp32 (S, L, D), as ``rounds`` consecutive generations with LIVE state —
     the reference's ``for _ in range(number_to_generate)`` around its entry_length loop (base.py:79-130): a later round continues the beams
     of the one before (token histories, has_stopped, seq_lengths, the KV cache), its running ``scores`` are the previous round's scores
@@ -72,6 +81,8 @@ def generate_beam_rounds(model, embeds: torch.Tensor, beam_size: int = 5, entry_
     tokens, and a round that starts with every beam stopped still takes one step (base.py:80-121) before it breaks.
     The constraints (module docstring) see a beam row's own generated tokens after the reorder; histories and the min_length count carry
     on across rounds like the rest of the state.  Text-prefix tokens are not part of the history: they enter as embeddings.
+    ``num_beam_groups`` > 1 with ``diversity_penalty`` > 0 (module docstring): beam rows g * W .. (g + 1) * W - 1, W = beam_size /
+    num_beam_groups, of every prefix are beam group g; a step is then the plain decode forward, the bans and cc_beam_group_step.
     Returns one (tokens int64 (S, beam, n_r), scores (S, beam) length-normalised, seq_lengths (S, beam)) per round."""
     lm = model.language_model
     g = lm.engine
@@ -81,6 +92,8 @@ def generate_beam_rounds(model, embeds: torch.Tensor, beam_size: int = 5, entry_
     R = S * beam_size
     V = g.dims["V"]
     rounds = max(1, int(rounds))
+    validate_beam_groups(beam_size, num_beam_groups, diversity_penalty)
+    G = int(num_beam_groups)
     bans = _bans(V, stop_token, no_repeat_ngram_size, min_length, suppress_tokens, dev)
     # positions are allocated up to n_positions; like the reference (base.py:79-130), a large number_to_generate only fails if generation
     # actually REACHES the position limit — beams normally stop far earlier
@@ -97,10 +110,13 @@ def generate_beam_rounds(model, embeds: torch.Tensor, beam_size: int = 5, entry_
     logits0 = sess.forward(embeds)                                              # (S, V)
     lg = torch.empty(R, V, dtype=torch.float32, device=dev)
     lg[::beam_size] = logits0                                                   # row 0 of every beam set
-    bufs = beam_buffers(dev, S, beam_size, V)                                   # this decode's own step outputs + scratch
+    bufs = beam_buffers(dev, S, beam_size, V) if G == 1 else beam_group_buffers(dev, S, beam_size, G, V)   # this decode's own step outputs + scratch
     if bans is not None:
         bans.apply(lg[::beam_size], 0)                                          # the rows the first update reads; no history yet
-    next_tok, src = beam_step(lg, S, beam_size, temperature, True, stop_token, scores, seq_lengths, has_stopped, bufs)
+    if G == 1:
+        next_tok, src = beam_step(lg, S, beam_size, temperature, True, stop_token, scores, seq_lengths, has_stopped, bufs)
+    else:
+        next_tok, src = beam_group_step(lg, S, beam_size, G, temperature, diversity_penalty, True, stop_token, scores, seq_lengths, has_stopped, bufs)
     sess = sess.expand((base // beam_size).to(torch.int32), R)
     # token histories (int32, ping-pong), the next input embedding and the cache ancestry are advanced by one launch per step
     tok = [torch.zeros(R, total, dtype=torch.int32, device=dev) for _ in range(2)]
@@ -117,10 +133,17 @@ def generate_beam_rounds(model, embeds: torch.Tensor, beam_size: int = 5, entry_
                 break
             if n >= total:
                 raise RuntimeError(f"generation reached n_positions = {g.dims['NPOS']} ({L0}-position prefix + {n} tokens; round {r + 1} of {rounds})")
-            logits = sess.forward(x, partials=True, group=beam_size)            # x = wte[next_tokens] (base.py:117)
-            if bans is not None:                                                # a stopped beam's logits are ignored by the update: skipped
-                bans.apply(logits, n, tok[(n - 1) & 1], n, sess.lpart, has_stopped)
-            next_tok, src = beam_step(logits, S, beam_size, temperature, False, stop_token, scores, seq_lengths, has_stopped, bufs, sess.lpart)
+            if G == 1:
+                logits = sess.forward(x, partials=True, group=beam_size)        # x = wte[next_tokens] (base.py:117)
+                if bans is not None:                                            # a stopped beam's logits are ignored by the update: skipped
+                    bans.apply(logits, n, tok[(n - 1) & 1], n, sess.lpart, has_stopped)
+                next_tok, src = beam_step(logits, S, beam_size, temperature, False, stop_token, scores, seq_lengths, has_stopped, bufs, sess.lpart)
+            else:                                                               # beam groups: the update reads the logits, not the partials
+                logits = sess.forward(x, group=beam_size)
+                if bans is not None:
+                    bans.apply(logits, n, tok[(n - 1) & 1], n, None, has_stopped)
+                next_tok, src = beam_group_step(logits, S, beam_size, G, temperature, diversity_penalty, False, stop_token, scores, seq_lengths,
+                                                has_stopped, bufs)
             sess.beam_advance(beam_size, next_tok, src, wte, n, tok[(n - 1) & 1], tok[n & 1], x)   # base.py:104-117
             n += 1
         final = scores / seq_lengths                                            # base.py:123
@@ -134,30 +157,43 @@ def generate_beam_rounds(model, embeds: torch.Tensor, beam_size: int = 5, entry_
 
 def generate_beam_tokens(model, embeds: torch.Tensor, beam_size: int = 5, entry_length: int = 67, temperature: float = 1.0,
                          stop_token: int = 50256, *, no_repeat_ngram_size: int = 0, min_length: int = 0,
-                         suppress_tokens=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                         suppress_tokens=None, num_beam_groups: int = 1,
+                         diversity_penalty: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """One generation (the reference's number_to_generate = 1): (tokens int64 (S, beam, n), scores (S, beam) length-normalised,
     seq_lengths (S, beam))."""
     return generate_beam_rounds(model, embeds, beam_size, entry_length, temperature, stop_token, 1, no_repeat_ngram_size=no_repeat_ngram_size,
-                                min_length=min_length, suppress_tokens=suppress_tokens)[0]
+                                min_length=min_length, suppress_tokens=suppress_tokens, num_beam_groups=num_beam_groups,
+                                diversity_penalty=diversity_penalty)[0]
+
+
+def best_beams(scores: torch.Tensor, n: int = 1) -> torch.Tensor:
+    """Indices (S, n) of the n best beams of every row of final ``scores`` (S, beam), best first; ties go to the lower beam index."""
+    if n == 1:
+        return scores.argmax(dim=1, keepdim=True)     # == argsort(descending)[0]; ties resolve to the first beam like a stable sort
+    return torch.sort(scores, dim=1, descending=True, stable=True).indices[:, :n]
 
 
 def generate_beam(model, tokenizer: Callable, embeds: torch.Tensor, number_to_generate: int = 1,
                   text_prefix_tokens: Optional[torch.Tensor] = None, beam_size: int = 5, entry_length: int = 67,
-                  temperature: float = 1.0, *, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None) -> List[str]:
-    """Reference signature (base.py:55-64) plus the keyword-only constraints (module docstring).  For the reference's batch-1 input: ``number_to_generate`` texts, the best beam after each of
+                  temperature: float = 1.0, *, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None,
+                  num_beam_groups: int = 1, diversity_penalty: float = 0.0, num_return_sequences: int = 1) -> List[str]:
+    """Reference signature (base.py:55-64) plus the keyword-only constraints and diverse-beam-search options (module docstring).  For the reference's batch-1 input: ``number_to_generate`` texts, the best beam after each of
     the consecutive generations (base.py:79-130, see generate_beam_rounds).  A batch of prefixes (S > 1, an extension — the reference is
-    batch-1) returns the best caption of every prefix row, round-major when number_to_generate > 1."""
+    batch-1) returns the best caption of every prefix row, round-major when number_to_generate > 1.
+    ``num_return_sequences`` = n > 1: for every prefix row (and round) its n best beams by final score, best first, next to each other."""
     stop = _stop_id(tokenizer)
     embeds = _with_text_prefix(model, embeds, text_prefix_tokens)
+    validate_beam_groups(beam_size, num_beam_groups, diversity_penalty, num_return_sequences)
     out = []
     for tokens, scores, lengths in generate_beam_rounds(model, embeds, beam_size, entry_length, temperature, stop, number_to_generate,
                                                         no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length,
-                                                        suppress_tokens=suppress_tokens):
-        best = scores.argmax(dim=1)     # == argsort(descending)[0]; ties resolve to the first beam like a stable sort
+                                                        suppress_tokens=suppress_tokens, num_beam_groups=num_beam_groups,
+                                                        diversity_penalty=diversity_penalty):
+        best = best_beams(scores, int(num_return_sequences)).cpu()
         for s in range(tokens.shape[0]):
-            b = int(best[s])
-            n = int(lengths[s, b])
-            out.append(tokenizer.decode(tokens[s, b, :n].cpu().numpy()))
+            for b in best[s].tolist():
+                n = int(lengths[s, b])
+                out.append(tokenizer.decode(tokens[s, b, :n].cpu().numpy()))
     return out
 
 

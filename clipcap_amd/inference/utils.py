@@ -97,3 +97,27 @@ def validate_constraints(vocab_size: int, stop_token: int, no_repeat_ngram_size:
     if m == 0 and int(stop_token) in ids:
         raise ValueError(f"suppress_tokens contains the stop token {stop_token} and min_length is 0: this decode can never stop")
     return ids
+
+
+# ---- diverse beam search (not in the reference: num_beam_groups / diversity_penalty / num_return_sequences of the beam decoders) --------
+
+def validate_beam_groups(beam_size: int, num_beam_groups: int = 1, diversity_penalty: float = 0.0, num_return_sequences: int = 1) -> None:
+    """Checks the diverse-beam-search options of the beam decoders.  ValueError for num_beam_groups < 1 or not a divisor of beam_size, a
+    penalty that is negative or not finite, beam groups without a penalty (with a penalty of 0 all beam groups would hold the same
+    hypotheses after the first step), a penalty without beam groups (it would have nothing to act on), and num_return_sequences outside
+    [1, beam_size].  Pure: touches no device."""
+    import math
+    b, g, n = int(beam_size), int(num_beam_groups), int(num_return_sequences)
+    p = float(diversity_penalty)
+    if g < 1:
+        raise ValueError(f"num_beam_groups must be >= 1, got {num_beam_groups}")
+    if b % g:
+        raise ValueError(f"beam_size {beam_size} is not a multiple of num_beam_groups {num_beam_groups}")
+    if not math.isfinite(p) or p < 0:
+        raise ValueError(f"diversity_penalty must be finite and >= 0, got {diversity_penalty}")
+    if g > 1 and p == 0:
+        raise ValueError(f"num_beam_groups = {g} needs diversity_penalty > 0: without a penalty every beam group finds the same hypotheses")
+    if g == 1 and p > 0:
+        raise ValueError(f"diversity_penalty = {p} needs num_beam_groups > 1: the penalty acts between beam groups")
+    if not 1 <= n <= b:
+        raise ValueError(f"num_return_sequences must be in [1, beam_size = {beam_size}], got {num_return_sequences}")

@@ -66,8 +66,8 @@ extern "C" {
  * cc_gemm_dact, cc_gemm_f32, cc_gemm_wgrad_split, and the attention test hooks cc_attention_fwd_x, cc_attention_bwd_x; operand mode ADDED: CC_OP_BF16X3.  Round 6 (still 3): the default-off decode experiments
  * (cc_decode_image*, cc_decode_xt_image*, cc_decode_fwd_x, cc_decode_ws_check, cc_decode_last_path) moved to include/clipcap_hip_lab.h —
  * the lab library exports them, the product library does not.  ADDED since (still 3: no existing entry point changed): cc_lmhead_score,
- * cc_grad_norm_scratch_floats, cc_grad_sqnorm, cc_grad_clip_coef, cc_adamw_step_clip, cc_logits_constrain, and the decode-attention
- * test hook cc_decode_attention. */
+ * cc_grad_norm_scratch_floats, cc_grad_sqnorm, cc_grad_clip_coef, cc_adamw_step_clip, cc_logits_constrain, cc_beam_group_step,
+ * cc_beam_group_ws_bytes, and the decode-attention test hook cc_decode_attention. */
 #define CC_ABI_VERSION 3
 int cc_abi_version(void);
 
@@ -264,6 +264,23 @@ int cc_beam_step_p(int32_t S, int32_t beam, int32_t V, const float* logits, int6
                    float temperature, int32_t first, int32_t stop_token, float* scores, float* seq_lengths, uint8_t* has_stopped,
                    int32_t* next_tokens, int32_t* src_rows, void* ws, void* stream);
 int64_t cc_beam_ws_bytes(int32_t S, int32_t beam, int32_t V);
+/* Diverse beam search (since 3, added without a version bump; not in the reference: Vijayakumar et al., 2016): cc_beam_step with the `beam`
+ * rows of every sample split into `groups` beam groups of W = beam / groups consecutive rows (beam % groups == 0, beam <= 16); beam group
+ * g owns rows and output slots g W .. (g + 1) W - 1.  One call advances the beam groups in the order 0 .. groups - 1; beam group g takes
+ * cc_beam_step's update on its own W rows (first != 0: on row 0 of the sample, in every beam group), with one change: the log-probability
+ * log(softmax(x / T))[v] of a non-stopped row's token v loses diversity_penalty * c(v) in fp32 before the length normalisation, c(v) =
+ * how many slots of beam groups 0 .. g - 1 of the sample took token v AT THIS CALL from a source row that had not stopped (the token-0
+ * continuation of a stopped beam is padding: neither counted nor penalised).  c(v) == 0 applies no operation, so groups == 1 is
+ * cc_beam_step bit for bit, for any penalty, and diversity_penalty == 0 is cc_beam_step at width W on every beam group's rows.  The W
+ * best of a beam group's W V candidates fill its slots best first (ties: lowest flat index b_local V + v); the penalised value is what
+ * scores keeps.  src_rows = the source row's index inside the SAMPLE (g W + b_local), as cc_beam_advance takes it.
+ * 1 + 2 groups launches (row statistics once, then per beam group a selection over 16 slices and a merge + commit), stream-ordered.
+ * ws: cc_beam_group_ws_bytes(S, beam, groups, V) bytes.  CC_ERR_ARG: NULL pointers, S < 0, beam outside [1, 16], groups < 1 or not a
+ * divisor of beam, V < 1, ldl < V, a penalty that is negative or not finite.  S == 0: CC_OK, nothing is launched. */
+int64_t cc_beam_group_ws_bytes(int32_t S, int32_t beam, int32_t groups, int32_t V);
+int cc_beam_group_step(int32_t S, int32_t beam, int32_t groups, int32_t V, const float* logits, int64_t ldl, float temperature,
+                       float diversity_penalty, int32_t first, int32_t stop_token, float* scores, float* seq_lengths, uint8_t* has_stopped,
+                       int32_t* next_tokens, int32_t* src_rows, void* ws, void* stream);
 /* Constrained decoding (since 3, added without a version bump): token bans on one step's logits [R][ldl], in place, BEFORE the beam update
  * or the sampling step.  A ban sets the token's logit to -inf, i.e. before the softmax (the convention of the reference's
  * top_k_top_p_filtering, utils.py:5-30): its mass is renormalised over the allowed tokens.  The banned set of row r:

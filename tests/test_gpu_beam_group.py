@@ -1,0 +1,280 @@
+"""cc_beam_group_step (diverse beam search: beam groups with a Hamming penalty, clipcap_amd/csrc/beam.hip) on the device: against the
+float64 statement of its semantics (tests/beam_group_ref.py), bit for bit against cc_beam_step where the two must agree (one beam group;
+a penalty of 0), on the all-ties overflow path, with banned (-inf) logits, from run to run, and end to end through the beam decoders on
+the beam_tiny golden model against a CPU search built from the oracle's full re-forward and the float64 step."""
+import pytest
+import torch
+
+from clipcap_amd.engine import beam_group_buffers, beam_group_step, beam_step
+from tests.beam_group_ref import beam_group_search_ref, beam_group_step_ref
+from tests.util import load_golden, sd_of
+
+pytestmark = pytest.mark.gpu
+
+# (beam, beam groups, V, row stride): group widths at the compile-time widths 1-4 and the run-time width 6, padded and unpadded rows
+SHAPES = [(6, 3, 50257, 50304), (4, 2, 50257, 50257), (8, 4, 1001, 1001), (12, 2, 4099, 4104), (16, 4, 4099, 4104), (4, 4, 130, 136)]
+S, STEPS, TEMP, STOP, PENALTY = 3, 5, 0.9, 17, 0.7
+MIN_MARGIN = 2e-5          # ten times the 2e-6 first-step error tests/test_gpu_beam.py asserts for this arithmetic
+# Largest deviation of a score from the float64 statement over the six shapes, five steps each (measure_scores below, on an MI355X;
+# inputs and kernels are deterministic, so the figures repeat):
+#   cc_beam_step (the whole beam as one pool, against the float64 statement with one beam group):  2.626e-6  (shape 4x2x50257x50257)
+#   cc_beam_group_step (the shapes' beam groups, penalty 0.7):                                     2.015e-6  (shape 12x2x4099x4104)
+# The grouped kernel has the same arithmetic plus one fused subtraction: it is allowed twice the plain kernel's deviation.
+PLAIN_SCORE_ERR = 2.626e-6
+GROUP_SCORE_ERR_MEASURED = 2.015e-6
+SCORE_TOL = 2 * PLAIN_SCORE_ERR
+
+
+def _inputs(beam, groups, V, ld, steps=STEPS, samples=S):
+    """The steps' logits (R, ld) fp32, generated on the CPU: randn * 3, from step 1 on +25 on the stop logit of every third row."""
+    g = torch.Generator().manual_seed(beam * 1000 + V + groups)
+    out = []
+    for step in range(steps):
+        buf = torch.randn(samples * beam, ld, generator=g) * 3.0
+        if step >= 1:
+            buf[::3, STOP] += 25.0
+        out.append(buf)
+    return out
+
+
+def _reference(bufs, beam, groups, V, penalty, samples=S):
+    """The float64 statement, sample by sample with its own float64 state -> per step (tokens, src, scores, lengths, stopped), and the
+    smallest decision margin of any beam group of any sample at any step."""
+    state = [None] * samples
+    steps, margin = [], float("inf")
+    for i, buf in enumerate(bufs):
+        rs = []
+        for s in range(samples):
+            lg = buf[s * beam:(s + 1) * beam, :V]
+            sc, ln, st = state[s] if state[s] is not None else (None, None, None)
+            r = beam_group_step_ref(lg, sc, ln, st, beam=beam, groups=groups, temperature=TEMP, penalty=penalty, first=i == 0, stop_token=STOP)
+            state[s] = (r.scores, r.lengths, r.stopped)
+            margin = min(margin, min(r.margins))
+            rs.append(r)
+        steps.append(tuple(torch.cat([getattr(r, f) for r in rs]) for f in ("tokens", "src", "scores", "lengths", "stopped")))
+    return steps, margin
+
+
+_REF = {}
+
+
+def _shared_reference(shape):
+    if shape not in _REF:                      # computed once per shape, shared by the tests that need it, never modified
+        bufs = _inputs(*shape)
+        _REF[shape] = (bufs, _reference(bufs, shape[0], shape[1], shape[2], PENALTY), _reference(bufs, shape[0], 1, shape[2], PENALTY))
+    return _REF[shape]
+
+
+def _state(R):
+    return torch.zeros(R, device="cuda"), torch.ones(R, device="cuda"), torch.zeros(R, dtype=torch.uint8, device="cuda")
+
+
+def measure_scores(shape):
+    """-> (largest |score - float64| of cc_beam_step with the beam as one pool, of cc_beam_group_step with the shape's beam groups)."""
+    beam, groups, V, ld = shape
+    bufs, (ref_g, _), (ref_1, _) = _shared_reference(shape)
+    errs = []
+    for G, ref in ((1, ref_1), (groups, ref_g)):
+        scores, seql, stopped = _state(S * beam)
+        err = 0.0
+        for i, buf in enumerate(bufs):
+            lg = buf.cuda()[:, :V]
+            if G == 1:
+                beam_step(lg, S, beam, TEMP, i == 0, STOP, scores, seql, stopped)
+            else:
+                beam_group_step(lg, S, beam, G, TEMP, PENALTY, i == 0, STOP, scores, seql, stopped)
+            err = max(err, (scores.cpu().double() - ref[i][2]).abs().max().item())
+        errs.append(err)
+    return tuple(errs)
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_group_step_matches_the_float64_statement(shape):
+    """Tokens, source rows, lengths and stop flags equal the float64 statement's at every step; scores within SCORE_TOL = 5.25e-6: twice
+    the 2.626e-6 that cc_beam_step's scores deviate from the same float64 statement with one beam group on these inputs (measured on an
+    MI355X, as was the grouped kernel's own largest deviation, 2.015e-6)."""
+    beam, groups, V, ld = shape
+    bufs, (ref, margin), _ = _shared_reference(shape)
+    assert margin >= MIN_MARGIN, margin            # a condition on the inputs: no near-tie can excuse a mismatch
+    assert ref[-1][4].any()                         # stopped rows occur
+    scores, seql, stopped = _state(S * beam)
+    ws = beam_group_buffers("cuda", S, beam, groups, V)
+    for i, buf in enumerate(bufs):
+        lg = buf.cuda()[:, :V]
+        nt, sr = beam_group_step(lg, S, beam, groups, TEMP, PENALTY, i == 0, STOP, scores, seql, stopped, ws)
+        want = ref[i]
+        err = (scores.cpu().double() - want[2]).abs().max().item()
+        print(f"shape {shape} step {i}: margin {margin:.2e} score error {err:.2e}")
+        assert torch.equal(nt.cpu().long(), want[0]), i
+        assert torch.equal(sr.cpu().long(), want[1]), i
+        assert torch.equal(seql.cpu().double(), want[3]) and torch.equal(stopped.cpu().bool(), want[4]), i
+        assert err <= SCORE_TOL, (i, err)
+
+
+@pytest.mark.parametrize("beam", [5, 6, 8, 1])
+def test_one_beam_group_is_bit_identical_to_beam_step(beam):
+    """G = 1 with a penalty: torch.equal outputs and state to cc_beam_step's three-kernel path, through stopped beams."""
+    V, ld = 4099, 4104
+    bufs = _inputs(beam, 1, V, ld, steps=4)
+    a, b = _state(S * beam), _state(S * beam)
+    for i, buf in enumerate(bufs):
+        lg = buf.cuda()[:, :V]
+        nt0, sr0 = beam_step(lg, S, beam, TEMP, i == 0, STOP, *a)
+        nt1, sr1 = beam_group_step(lg, S, beam, 1, TEMP, PENALTY, i == 0, STOP, *b)
+        assert torch.equal(nt0, nt1) and torch.equal(sr0, sr1), i
+        assert all(torch.equal(x.view(torch.int32) if x.dtype == torch.float32 else x, y.view(torch.int32) if y.dtype == torch.float32 else y)
+                   for x, y in zip(a, b)), i
+    assert a[2].any() or beam == 1
+
+
+def test_penalty_zero_is_beam_step_on_every_beam_group():
+    """Penalty 0, beam 6 in 3 beam groups: every beam group's slots and state are bit-equal to cc_beam_step at width 2 on its rows; on the
+    first step (every beam group reads row 0) all beam groups are equal."""
+    beam, groups, V, ld, W = 6, 3, 4099, 4104, 2
+    bufs = _inputs(beam, groups, V, ld, steps=4)
+    full = _state(S * beam)
+    part = [_state(S * W) for _ in range(groups)]
+    bits = lambda t: t.view(torch.int32) if t.dtype == torch.float32 else t  # noqa: E731
+    for i, buf in enumerate(bufs):
+        dev = buf.cuda()
+        nt, sr = beam_group_step(dev[:, :V], S, beam, groups, TEMP, 0.0, i == 0, STOP, *full)
+        for g in range(groups):
+            rows = dev.view(S, beam, ld)[:, (0 if i == 0 else g * W):(0 if i == 0 else g * W) + W].reshape(S * W, ld).contiguous()
+            pnt, psr = beam_step(rows[:, :V], S, W, TEMP, i == 0, STOP, *part[g])
+            sl = (slice(None), slice(g * W, (g + 1) * W))
+            assert torch.equal(nt.view(S, beam)[sl], pnt.view(S, W)), (i, g)
+            assert torch.equal(sr.view(S, beam)[sl], psr.view(S, W) + (0 if i == 0 else g * W)), (i, g)
+            for x, y in zip(full, part[g]):
+                assert torch.equal(bits(x).view(S, beam)[sl], bits(y).view(S, W)), (i, g)
+        if i == 0:
+            for g in range(1, groups):
+                assert torch.equal(nt.view(S, beam)[:, g * W:(g + 1) * W], nt.view(S, beam)[:, :W])
+                assert torch.equal(bits(full[0]).view(S, beam)[:, g * W:(g + 1) * W], bits(full[0]).view(S, beam)[:, :W])
+    assert full[2].any()
+
+
+def test_all_logits_equal_takes_the_overflow_path_in_index_order():
+    """All logits equal at GPT-2's vocabulary (a slice's candidates overflow the list: the per-thread insertion lists), penalty 1, beam 4
+    in 2 beam groups: beam group 0 takes tokens 0 and 1, beam group 1, which finds them penalised, tokens 2 and 3."""
+    beam, groups, V, samples = 4, 2, 50257, 2
+    lg = torch.zeros(samples * beam, V)
+    scores, seql, stopped = _state(samples * beam)
+    state = [None] * samples
+    for first in (True, False):
+        nt, sr = beam_group_step(lg.cuda(), samples, beam, groups, 1.0, 1.0, first, V - 1, scores, seql, stopped)
+        if first:
+            assert nt.view(samples, beam).cpu().tolist() == [[0, 1, 2, 3]] * samples and sr.cpu().tolist() == [0] * (samples * beam)
+        else:       # rows 0 and 1 (2 and 3) carry equal scores: the lowest flat index is row 0 (2) of the beam group
+            assert nt.view(samples, beam).cpu().tolist() == [[0, 1, 2, 3]] * samples
+            assert sr.view(samples, beam).cpu().tolist() == [[0, 0, 2, 2]] * samples
+        for s in range(samples):
+            sc, ln, st = state[s] if state[s] is not None else (None, None, None)
+            r = beam_group_step_ref(lg[s * beam:(s + 1) * beam], sc, ln, st, beam=beam, groups=groups, penalty=1.0, first=first, stop_token=V - 1)
+            state[s] = (r.scores, r.lengths, r.stopped)
+            sl = slice(s * beam, (s + 1) * beam)
+            assert torch.equal(nt[sl].cpu().long(), r.tokens) and torch.equal(sr[sl].cpu().long(), r.src)
+            assert torch.allclose(scores[sl].cpu().double(), r.scores, rtol=1e-5, atol=3e-5)
+
+
+def test_banned_logits_are_never_picked():
+    """-inf logits, as the token bans leave them, the best tokens of every row among them: never picked, and no NaN in the scores."""
+    beam, groups, V, ld, samples = 4, 2, 1001, 1001, 2
+    g = torch.Generator().manual_seed(77)
+    scores, seql, stopped = _state(samples * beam)
+    for i in range(4):
+        lg = torch.randn(samples * beam, ld, generator=g) * 3.0
+        lg[torch.rand(lg.shape, generator=g) < 0.3] = float("-inf")
+        lg.scatter_(1, lg.topk(3, dim=1).indices, float("-inf"))                   # what an unconstrained step would have picked
+        if i >= 1:
+            lg[::3, STOP] = 25.0                                                    # some beams stop
+        was_stopped = stopped.cpu().bool()
+        nt, sr = beam_group_step(lg.cuda(), samples, beam, groups, TEMP, PENALTY, i == 0, STOP, scores, seql, stopped)
+        rows = (torch.arange(samples * beam) // beam) * beam + sr.cpu().long()
+        live = ~was_stopped[rows] if i else torch.ones(samples * beam, dtype=torch.bool)
+        assert torch.isfinite(lg[rows, nt.cpu().long()][live]).all(), i
+        assert (nt.cpu()[~live] == 0).all()                                         # a stopped beam continues with its padding token
+        assert torch.isfinite(scores).all(), i
+    assert stopped.any()
+
+
+def _seeded_run():
+    shape = (6, 3, 4099, 4104)
+    beam, groups, V, ld = shape
+    scores, seql, stopped = _state(S * beam)
+    out = []
+    for i, buf in enumerate(_inputs(*shape)):
+        nt, sr = beam_group_step(buf.cuda()[:, :V], S, beam, groups, TEMP, PENALTY, i == 0, STOP, scores, seql, stopped)
+        out += [nt.cpu(), sr.cpu(), scores.cpu().view(torch.int32), seql.cpu().view(torch.int32), stopped.cpu()]
+    assert stopped.any()
+    return out
+
+
+def test_group_step_is_bit_identical_from_run_to_run():
+    a, b = _seeded_run(), _seeded_run()
+    assert len(a) == len(b) == 5 * STEPS and all(torch.equal(x, y) for x, y in zip(a, b))
+
+
+# ---- end to end: the beam decoders on the beam_tiny golden model (split-bf16 operands) against a CPU search ----------------------------
+# Prefixes: the golden cases 1 and 2 (their stop token 50, 12 tokens).  Chosen on the CPU: the CPU search's decision margins are 2.0e-2 and
+# 5.9e-1 unconstrained, 3.8e-3 and 1.2e-2 with the bans; 1e-3, asserted below, is the project's bar for split-bf16 logits against fp32.
+E2E_CASES, E2E_BEAM, E2E_GROUPS, E2E_PENALTY = ("1", "2"), 4, 2, 1.0
+
+
+def _e2e():
+    from types import SimpleNamespace
+    from clipcap_amd.model.gpt2 import GPT2LM
+    g = load_golden("beam_tiny")
+    D, n_layer, n_head, V, npos = [int(v) for v in g["cfg"]]
+    lm = GPT2LM(n_embd=D, n_layer=n_layer, n_head=n_head, vocab_size=V, n_positions=npos, precision=32)
+    lm.load_state_dict(sd_of(g), strict=False)
+    sd = {"language_model." + k: v for k, v in sd_of(g).items()}
+    metas = {tuple(int(v) for v in g[f"beam{c}.meta"][:2]) for c in E2E_CASES}
+    assert len(metas) == 1
+    stop, entry = metas.pop()
+    pref = torch.cat([torch.from_numpy(g[f"beam{c}.prefix"]) for c in E2E_CASES])
+    return SimpleNamespace(language_model=lm.to("cuda")), sd, pref, dict(n_head=n_head, n_layer=n_layer), stop, entry, V
+
+
+@pytest.mark.parametrize("bans", [{}, dict(no_repeat_ngram_size=2, min_length=3)], ids=["free", "bans"])
+def test_diverse_beam_search_equals_the_cpu_search(bans):
+    from clipcap_amd.inference.base import generate_beam_tokens
+    model, sd, pref, dims, stop, entry, _ = _e2e()
+    toks, scores, lens = generate_beam_tokens(model, pref.cuda(), E2E_BEAM, entry, 1.0, stop, num_beam_groups=E2E_GROUPS, diversity_penalty=E2E_PENALTY,
+                                              **bans)
+    toks, scores, lens = toks.cpu(), scores.cpu(), lens.cpu()
+    moved = False
+    for s in range(pref.shape[0]):
+        ot, osc, ol, margin = beam_group_search_ref(sd, pref[s:s + 1], beam=E2E_BEAM, groups=E2E_GROUPS, penalty=E2E_PENALTY, entry_length=entry,
+                                                    stop_token=stop, **dims, **bans)
+        assert margin >= 1e-3, (s, margin)
+        assert torch.equal(lens[s].double(), ol), s
+        for b in range(E2E_BEAM):
+            n = int(ol[b])
+            assert toks[s, b, :n].tolist() == ot[b, :n].tolist(), (s, b)
+            assert abs(float(scores[s, b]) - float(osc[b])) <= 1e-3, (s, b)      # split-bf16 logits are within ~1e-4 of fp32: so are mean log-probabilities
+            if bans:
+                seq = ot[b, :n].tolist()
+                assert stop not in seq[:3] and len({tuple(seq[i:i + 2]) for i in range(n - 1)}) == max(0, n - 1), seq
+        plain = beam_group_search_ref(sd, pref[s:s + 1], beam=E2E_BEAM, groups=E2E_GROUPS, penalty=0.0, entry_length=entry, stop_token=stop, **dims, **bans)
+        moved |= plain[0].shape != ot.shape or not torch.equal(plain[0], ot)
+    assert moved                                                                   # the penalty changes what the beam groups find
+
+
+def test_generate_beam_returns_the_beams_in_score_order_and_defaults_change_nothing():
+    from tests.test_api_surface import FakeTokenizer
+    from clipcap_amd.inference.base import generate_beam, generate_beam_tokens
+    model, _, pref, _, stop, entry, V = _e2e()
+    tk = FakeTokenizer(V, stop)
+    kw = dict(num_beam_groups=E2E_GROUPS, diversity_penalty=E2E_PENALTY)
+    toks, scores, lens = (t.cpu() for t in generate_beam_tokens(model, pref.cuda(), E2E_BEAM, entry, 1.0, stop, **kw))
+    texts = generate_beam(model, tk, pref.cuda(), beam_size=E2E_BEAM, entry_length=entry, num_return_sequences=4, **kw)
+    assert len(texts) == 4 * pref.shape[0]
+    for s in range(pref.shape[0]):
+        order = sorted(range(E2E_BEAM), key=lambda b: (-float(scores[s, b]), b))
+        assert texts[4 * s:4 * s + 4] == [tk.decode(toks[s, b, :int(lens[s, b])].numpy()) for b in order], s
+        assert len(set(texts[4 * s:4 * s + 4])) > 1
+    assert generate_beam(model, tk, pref.cuda(), beam_size=E2E_BEAM, entry_length=entry, **kw) == texts[::4]
+    # the defaults: exactly the call without the options
+    a = generate_beam_tokens(model, pref.cuda(), E2E_BEAM, entry, 1.0, stop)
+    b = generate_beam_tokens(model, pref.cuda(), E2E_BEAM, entry, 1.0, stop, num_beam_groups=1, diversity_penalty=0.0)
+    assert all(torch.equal(x, y) for x, y in zip(a, b))
