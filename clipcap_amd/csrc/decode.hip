@@ -473,6 +473,53 @@ __global__ __launch_bounds__(256) void k_beam_advance(int beam, int D, const flo
     for (int c = tid; c < (D >> 2); c += 256) reinterpret_cast<float4*>(x_out + (size_t)r * D)[c] = w[c];
 }
 
+// cc_decode_hidden_unit: out[r * ld_row + t * ld_pos + :] = ln_f(x[r * Tn + t]) / |ln_f(x[r * Tn + t])|_2 — k_ln_fwd's arithmetic (one wave per
+// row, the row in registers, 16-B loads and stores), then one more wave reduction for the norm.  A zero vector stays zero.
+template <int NV>   // float4 per lane: D <= 256 NV
+__global__ __launch_bounds__(256) void k_ln_unit(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                 float* __restrict__ out, int rows, int Tn, int D, size_t ld_row, size_t ld_pos) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;                                            // wave-uniform
+    const float* xr = x + (size_t)row * D;
+    float4 v[NV], g[NV], bt[NV];
+#pragma unroll
+    for (int it = 0; it < NV; it++) {
+        const int c = lane * 4 + it * 256;
+        v[it] = c < D ? *reinterpret_cast<const float4*>(xr + c) : make_float4(0, 0, 0, 0);
+        g[it] = c < D ? *reinterpret_cast<const float4*>(gamma + c) : make_float4(0, 0, 0, 0);
+        bt[it] = c < D ? *reinterpret_cast<const float4*>(beta + c) : make_float4(0, 0, 0, 0);
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int it = 0; it < NV; it++) s += v[it].x + v[it].y + v[it].z + v[it].w;
+    const float mu = wave_sum(s) / D;
+    float q = 0.f;
+#pragma unroll
+    for (int it = 0; it < NV; it++) {
+        if (lane * 4 + it * 256 < D) {
+            const float a = v[it].x - mu, b = v[it].y - mu, c2 = v[it].z - mu, d = v[it].w - mu;
+            q += a * a + b * b + c2 * c2 + d * d;
+        }
+    }
+    const float rs = rsqrtf(wave_sum(q) / D + 1e-5f);
+    float n2 = 0.f;
+#pragma unroll
+    for (int it = 0; it < NV; it++) {                                   // columns >= D: gamma = beta = 0 -> 0
+        v[it] = make_float4((v[it].x - mu) * rs * g[it].x + bt[it].x, (v[it].y - mu) * rs * g[it].y + bt[it].y,
+                            (v[it].z - mu) * rs * g[it].z + bt[it].z, (v[it].w - mu) * rs * g[it].w + bt[it].w);
+        n2 += (v[it].x * v[it].x + v[it].y * v[it].y) + (v[it].z * v[it].z + v[it].w * v[it].w);
+    }
+    n2 = wave_sum(n2);
+    const float inv = n2 > 0.f ? 1.0f / sqrtf(n2) : 0.f;
+    float* o = out + (size_t)(row / Tn) * ld_row + (size_t)(row % Tn) * ld_pos;
+#pragma unroll
+    for (int it = 0; it < NV; it++) {
+        const int c = lane * 4 + it * 256;
+        if (c < D) *reinterpret_cast<float4*>(o + c) = make_float4(v[it].x * inv, v[it].y * inv, v[it].z * inv, v[it].w * inv);
+    }
+}
+
 struct DecWS {
     float *x, *x1;
     act_t *xn, *qkv, *att, *hact, *hf;
@@ -856,6 +903,29 @@ int CC_API(cc_beam_advance)(const cc_gpt2_cfg* c, int32_t R, int32_t beam, const
         return CC_ERR_ARG;
     hipLaunchKernelGGL(k_beam_advance, dim3(R), dim3(256), 0, S_(stream), beam, c->D, w32, next_tokens, src_rows, pos, ctx_max, row_map_in, row_map_out,
                        step, tok_ld, tokens_in, tokens_out, x_out);
+    return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
+}
+
+// The final hidden states of the last forward on this workspace, as unit vectors (contrastive search).  Every path of decode_fwd_impl's
+// layer loop ends a layer with mlp.c_proj + residual stored to DecWS::x in fp32 for all R * Tn rows (gemm_nt_skinny's out32: the plain
+// epilogue, k_splitk_finish and k_splitk_finish_row all store it before any fused LayerNorm), whether ln_f then runs fused (hf) or as
+// ln_fwd over the last rows.  The lab library's persistent engines keep the stream elsewhere: refused.
+int CC_API(cc_decode_hidden_unit)(const cc_gpt2_cfg* c, int32_t R, int32_t Tn, const float* w32, void* ws, float* out, int64_t ld_row, int64_t ld_pos,
+                                  void* stream) {
+    if (!gpt2_dims_ok(c) || R < 0 || Tn <= 0 || !w32 || !ws || !out || (reinterpret_cast<uintptr_t>(out) & 15)) return CC_ERR_ARG;
+    const int D = c->D;
+    if (ld_pos < D || ld_row < (int64_t)(Tn - 1) * ld_pos + D) return CC_ERR_ARG;
+    if (D > 2048 || (D & 3) || (ld_row & 3) || (ld_pos & 3)) return CC_ERR_SHAPE;
+    if (cc_shared::g_decode_mode & 6) return CC_ERR_STATE;
+    if (R == 0) return CC_OK;
+    DecWS w;
+    dec_carve(c, R, Tn, ws, w);
+    const Gpt2Off o(c);
+    const int rows = R * Tn;
+    const dim3 gr((rows + 3) / 4);
+#define CC_LNU(NV) hipLaunchKernelGGL(k_ln_unit<NV>, gr, dim3(256), 0, S_(stream), w.x, w32 + o.lnf_w, w32 + o.lnf_b, out, rows, Tn, D, (size_t)ld_row, (size_t)ld_pos)
+    if (D <= 256) CC_LNU(1); else if (D <= 512) CC_LNU(2); else if (D <= 768) CC_LNU(3); else if (D <= 1024) CC_LNU(4); else CC_LNU(8);
+#undef CC_LNU
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 

@@ -837,7 +837,28 @@ class DecodeSession:
                                             _p(self.row_map), grp, _p(self._workspace(tn)), _p(logits), Vp,
                                             _p(self._lpart) if partials else None, _stream(g.arena.device)), "cc_decode_fwd_g")
         self.pos += tn
+        self._last_tn = tn
         return logits[:, : g.dims["V"]]
+
+    def hidden_unit(self, out: torch.Tensor, ld_row: int, ld_pos: int) -> torch.Tensor:
+        """The final hidden states of the last forward(), all R * Tnew positions, as fp32 unit vectors (cc_decode_hidden_unit; contrastive
+        search): out[r * ld_row + t * ld_pos : + D] = ln_f(residual) / its L2 norm, from the fp32 residual stream the forward left in its
+        workspace — not from the 16-bit rows the lm_head reads, so the operand mode enters only through the residual itself.  ``out``: a
+        contiguous fp32 device tensor that covers those elements (strides in floats, multiples of 4; ld_pos >= D).  Valid until the
+        next forward() of this session; RuntimeError before the first one and while the lab library's persistent decode engines are on
+        (they keep the residual stream elsewhere).  Returns ``out``."""
+        tn = getattr(self, "_last_tn", None)
+        if tn is None:
+            raise RuntimeError("hidden_unit() needs a forward() on this session first")
+        if _lib.lib().cc_decode_mode(-1) & 6:
+            raise RuntimeError("hidden_unit() does not support the persistent decode engines (cc_decode_mode bits 1 and 2)")
+        g = self.g
+        D = g.dims["D"]
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.device == g.arena.w32.device
+        assert out.numel() >= (self.R - 1) * ld_row + (tn - 1) * ld_pos + D
+        check(_lib.lib().cc_decode_hidden_unit(C.byref(g.cfg), self.R, tn, _p(g.arena.w32), _p(self._ws[tn]), _p(out), int(ld_row), int(ld_pos),
+                                              _stream(g.arena.device)), "cc_decode_hidden_unit")
+        return out
 
     def check(self, tn: int = 1) -> None:
         """Lab library: synchronises and raises if the last single-position step on this session's workspace gave up on an in-launch
@@ -984,6 +1005,54 @@ def constrain_logits(logits: torch.Tensor, *, lpart: Optional[tuple] = None, his
                                         _p(suppress) if suppress is not None else None, suppress.numel() if suppress is not None else 0,
                                         _p(skip_rows) if skip_rows is not None else None, _stream(dev)), "cc_logits_constrain")
     return logits
+
+
+def contrastive_buffers(device, S: int, k: int, D: int, ctx_max: int, entry_length: int):
+    """The device state of ONE contrastive-search decode of S captions with k candidates each (never shared between decodes, streams or
+    threads), as a namespace: cand_tok int32 (S*k,), cand_prob fp32 (S*k,), cand_h fp32 (S*k, D) — the candidates of the step;
+    hist fp32 (S, ctx_max, D) — the unit hidden states of the context, row j = position j; stopped uint8 (S,), lengths int32 (S,),
+    sel int32 (S,), src_rows int32 (S*k,), skip_rows uint8 (S*k,) — contrastive_select's outputs; captions int32 (S, entry_length) and
+    scores fp32 (entry_length, S) — token and score of every step (zeros where nothing was generated)."""
+    from types import SimpleNamespace
+    z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=device)  # noqa: E731
+    return SimpleNamespace(cand_tok=z(S * k, dtype=torch.int32), cand_prob=z(S * k, dtype=torch.float32), cand_h=z(S * k, D, dtype=torch.float32),
+                           hist=z(S, ctx_max, D, dtype=torch.float32), stopped=z(S, dtype=torch.uint8), lengths=z(S, dtype=torch.int32),
+                           sel=z(S, dtype=torch.int32), src_rows=z(S * k, dtype=torch.int32), skip_rows=z(S * k, dtype=torch.uint8),
+                           captions=z(S, entry_length, dtype=torch.int32), scores=z(entry_length, S, dtype=torch.float32))
+
+
+def contrastive_topk(logits: torch.Tensor, S: int, rows_per: int, sel: Optional[torch.Tensor], k: int, stopped: Optional[torch.Tensor],
+                     cand_tok: torch.Tensor, cand_prob: torch.Tensor):
+    """The k candidates of S captions in one launch (cc_contrastive_topk; Su et al., 2022): caption s reads row s * rows_per + sel[s]
+    (``sel`` None: the first) of fp32 ``logits`` (S * rows_per, V) (a view with a row stride is fine).  cand_tok[s*k + c] = the ids of the k
+    largest logits, largest first, ties to the lower id; cand_prob[s*k + c] = their softmax probabilities over the whole row (banned,
+    -inf, entries contribute nothing).  A slot without a finite logit, and every slot of a caption with a non-zero ``stopped`` entry
+    (uint8 (S,), may be None; its row is not read), holds token 0 and probability -1 = invalid.  Returns (cand_tok, cand_prob)."""
+    dev = logits.device
+    R, V = logits.shape
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and R == S * rows_per
+    assert cand_tok.dtype == torch.int32 and cand_prob.dtype == torch.float32 and cand_tok.numel() == S * k == cand_prob.numel()
+    assert sel is None or (sel.dtype == torch.int32 and sel.numel() == S)
+    assert stopped is None or (stopped.dtype == torch.uint8 and stopped.numel() == S)
+    check(_lib.lib().cc_contrastive_topk(_p(logits), logits.stride(0), S, rows_per, _p(sel) if sel is not None else None, V, int(k),
+                                        _p(stopped) if stopped is not None else None, _p(cand_tok), _p(cand_prob), _stream(dev)), "cc_contrastive_topk")
+    return cand_tok, cand_prob
+
+
+def contrastive_select(bufs, k: int, hist_lo: int, hist_n: int, alpha: float, stop_token: int, step: int) -> None:
+    """One selection step of contrastive search for every caption of ``bufs`` (contrastive_buffers), in one launch
+    (cc_contrastive_select): with deg(c) = the largest dot product of candidate c's unit vector bufs.cand_h[s*k + c] with
+    bufs.hist[s, hist_lo:hist_n] (0 for an empty range), the slot with the largest (1 - alpha) * cand_prob - alpha * deg among the valid
+    ones wins, ties to the lowest slot.  IN PLACE: sel[s] = the winner, captions[s, step] = its token, scores[step, s] = its score,
+    hist[s, hist_n] = its vector, lengths[s] += 1, stopped[s] = (token == stop_token), src_rows[s*k + c] = the winner (what beam_advance
+    takes), skip_rows[s*k + c] = 1 except on the winner's row of a caption that goes on (what constrain_logits takes).  A caption without a
+    valid slot stops with ``stop_token``; one that had stopped before gets padding (token 0, score 0) and keeps its state."""
+    S, n, D = bufs.hist.shape
+    assert bufs.cand_h.shape == (S * k, D) and bufs.captions.shape[0] == S and bufs.scores.shape[1] == S
+    check(_lib.lib().cc_contrastive_select(S, int(k), D, _p(bufs.cand_h), _p(bufs.cand_prob), _p(bufs.cand_tok), _p(bufs.hist), n, int(hist_lo), int(hist_n),
+                                          float(alpha), int(stop_token), _p(bufs.stopped), _p(bufs.lengths), _p(bufs.sel), _p(bufs.src_rows),
+                                          _p(bufs.skip_rows), _p(bufs.captions), bufs.captions.stride(0), int(step), _p(bufs.scores[step]),
+                                          _stream(bufs.hist.device)), "cc_contrastive_select")
 
 
 def sample_step(logits: torch.Tensor, u: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 0.0, mode: int = 0,

@@ -18,6 +18,9 @@ Not in the reference either: diverse beam search (Vijayakumar et al., 2016) on t
     (cc_beam_group_step; the two come together);
   * ``num_return_sequences`` = n (generate_beam): the n best beams of every prefix instead of the best one.
 With G == 1 the beam decoders launch exactly what they launched without these options.
+
+Contrastive search (Su et al., 2022), the deterministic decoder with a degeneration penalty, lives in inference/contrastive.py
+(generate_contrastive, generate_contrastive_tokens); it takes the same three constraints.
 """
 from __future__ import annotations
 

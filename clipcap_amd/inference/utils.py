@@ -121,3 +121,23 @@ def validate_beam_groups(beam_size: int, num_beam_groups: int = 1, diversity_pen
         raise ValueError(f"diversity_penalty = {p} needs num_beam_groups > 1: the penalty acts between beam groups")
     if not 1 <= n <= b:
         raise ValueError(f"num_return_sequences must be in [1, beam_size = {beam_size}], got {num_return_sequences}")
+
+
+# ---- contrastive search (not in the reference: top_k / penalty_alpha of generate_contrastive) ------------------------------------------
+
+MAX_CONTRASTIVE_TOP_K = 8       # the candidates per caption cc_contrastive_topk / cc_contrastive_select accept
+
+
+def validate_contrastive(top_k: int, penalty_alpha: float) -> None:
+    """Checks the options of the contrastive-search decoders.  ValueError for a top_k that is not an int in [1, MAX_CONTRASTIVE_TOP_K] and
+    for a penalty_alpha that is not finite or outside [0, 1] (0: no penalty, greedy decoding; 1: the model's probabilities are ignored).
+    Pure: touches no device."""
+    import math
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= MAX_CONTRASTIVE_TOP_K:
+        raise ValueError(f"top_k must be an int in [1, {MAX_CONTRASTIVE_TOP_K}], got {top_k!r}")
+    try:
+        a = float(penalty_alpha)
+    except (TypeError, ValueError):
+        raise ValueError(f"penalty_alpha must be a number in [0, 1], got {penalty_alpha!r}") from None
+    if not math.isfinite(a) or not 0.0 <= a <= 1.0:
+        raise ValueError(f"penalty_alpha must be finite and in [0, 1], got {penalty_alpha!r}")

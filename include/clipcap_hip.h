@@ -67,7 +67,8 @@ extern "C" {
  * (cc_decode_image*, cc_decode_xt_image*, cc_decode_fwd_x, cc_decode_ws_check, cc_decode_last_path) moved to include/clipcap_hip_lab.h —
  * the lab library exports them, the product library does not.  ADDED since (still 3: no existing entry point changed): cc_lmhead_score,
  * cc_grad_norm_scratch_floats, cc_grad_sqnorm, cc_grad_clip_coef, cc_adamw_step_clip, cc_logits_constrain, cc_beam_group_step,
- * cc_beam_group_ws_bytes, and the decode-attention test hook cc_decode_attention. */
+ * cc_beam_group_ws_bytes, cc_decode_hidden_unit, cc_contrastive_topk, cc_contrastive_select, and the decode-attention test hook
+ * cc_decode_attention. */
 #define CC_ABI_VERSION 3
 int cc_abi_version(void);
 
@@ -301,6 +302,54 @@ int cc_beam_group_step(int32_t S, int32_t beam, int32_t groups, int32_t V, const
 int cc_logits_constrain(float* logits, int32_t R, int32_t V, int64_t ldl, float* lpart, int32_t npart, const void* history,
                         int32_t hist_elem_bytes, int64_t hist_stride, int32_t hist_len, int32_t no_repeat_ngram, int32_t ban_token,
                         const int32_t* suppress, int32_t n_suppress, const uint8_t* skip_rows, void* stream);
+/* Contrastive search (since 3, added without a version bump; not in the reference: Su et al., 2022, "A Contrastive Framework for Neural
+ * Text Generation"): at every step the k most probable tokens of a caption are run through the model as k rows of one group, and the
+ * token kept is the one with the largest  (1 - alpha) p(c) - alpha max_j cos(h_c, h_j),  h_c = the candidate's final hidden state, h_j =
+ * the final hidden states of the context so far.  Three entry points, all fp32 / integer work:
+ *
+ * cc_decode_hidden_unit: the final hidden states of the LAST cc_decode_fwd / _p / _g call made on `ws` (same cfg, R and Tnew), for all
+ * R * Tnew positions: out[r * ld_row + t * ld_pos + 0..D) = ln_f(x) / |ln_f(x)|_2, x = the fp32 residual stream the forward left in the
+ * workspace, eps 1e-5, fp32 arithmetic throughout (LayerNorm as every other LayerNorm here: one wave per row, the row in registers); a
+ * zero vector stays zero.  The 16-bit ln_f rows the lm_head reads are NOT used: they exist for the last position only and are rounded to
+ * the operand type, and the similarity must not depend on the operand mode more than the residual itself does.  Valid after any call
+ * sequence that ends in a forward on this ws with these R, Tnew — prefill (Tnew > 1), a single position, with or without group / lpart:
+ * every path of the product's forward (fused finishing passes or separate LayerNorm launches) stores the final residual of all R * Tnew
+ * rows in fp32 before ln_f is applied.  NOT valid after a forward with other R / Tnew on the same ws (the carving differs), nor after the
+ * lab library's persistent engines (cc_decode_mode bits 1 and 2: CC_ERR_STATE while either is on).  One launch.  CC_ERR_ARG: bad cfg, NULL
+ * pointers, R < 0, Tnew < 1, out not 16-byte aligned, ld_pos < D, ld_row < (Tnew - 1) * ld_pos + D.  CC_ERR_SHAPE: D > 2048, D % 4,
+ * ld_row % 4 or ld_pos % 4.  R == 0: CC_OK, nothing is launched. */
+int cc_decode_hidden_unit(const cc_gpt2_cfg* cfg, int32_t R, int32_t Tnew, const float* w32, void* ws, float* out, int64_t ld_row,
+                          int64_t ld_pos, void* stream);
+/* cc_contrastive_topk: the candidates of S captions.  Caption s reads logits row s * rows_per + (sel ? sel[s] : 0) (fp32 [.][ldl], V real
+ * columns; after the prefill rows_per = 1, sel NULL; at a step rows_per = k and sel = cc_contrastive_select's winners).
+ * cand_tok[s * k + c] = the ids of the k largest logits, largest first, ties to the lower id (fp32 comparisons: exact);
+ * cand_prob[s * k + c] = softmax(row)[id] in fp32, max-subtracted, -inf entries (token bans) contributing nothing.  A slot whose logit is
+ * -inf (fewer than k finite logits) holds token 0 and probability -1 = invalid.  A stopped caption (stopped[s] != 0; stopped may be NULL)
+ * gets token 0 / probability -1 in every slot and its row is not read.  One launch, one workgroup per caption, the row read once.
+ * CC_ERR_ARG: NULL logits / cand_tok / cand_prob, S < 0, rows_per < 1, k outside [1, 8], V < 1, ldl < V.  CC_ERR_SHAPE: V > 2097152.
+ * S == 0: CC_OK, nothing is launched. */
+int cc_contrastive_topk(const float* logits, int64_t ldl, int32_t S, int32_t rows_per, const int32_t* sel, int32_t V, int32_t k,
+                        const uint8_t* stopped, int32_t* cand_tok, float* cand_prob, void* stream);
+/* cc_contrastive_select: the degeneration penalty, the scores and the winner.  cand_h fp32 [S * k][D] unit vectors (cc_decode_hidden_unit
+ * of the k candidate rows), hist fp32 [S][hist_ld][D] unit vectors of the context.  For a caption that has not stopped:
+ *   deg(c) = max over j in [hist_lo, hist_n) of dot(cand_h[s, c], hist[s, j])   (empty range: 0)
+ *   score(c) = (1 - alpha) * cand_prob[s, c] - alpha * deg(c)                   over the slots with cand_prob >= 0
+ * the winner w has the largest score, ties to the lowest c.  Written: sel[s] = w; captions[s * cap_ld + step] = cand_tok[s, w];
+ * hist[s][hist_n] = cand_h[s, w] (a copy, bit for bit); lengths[s] += 1; stopped[s] = (token == stop_token); sel_score[s] = score(w)
+ * (sel_score may be NULL); src_rows[s * k + c] = w for every c (what cc_beam_advance takes); skip_rows[s * k + c] = (c != w) ||
+ * stopped[s] with the NEW flag (what cc_logits_constrain takes).  No valid slot: the caption stops with stop_token (length + 1, w = 0,
+ * score 0, every row skipped, hist untouched).  A caption that had stopped before the call: sel = 0, src_rows = 0, captions[...] = 0
+ * (padding, as beam search pads), sel_score = 0, skip_rows = 1; hist, lengths and stopped untouched.
+ * One launch, one workgroup (4 waves) per caption: the k candidate vectors sit in LDS (k * D * 4 bytes, 64 KB at k = 8, D = 2048: the
+ * largest workgroup allocation, of gfx950's 160 KB per CU; the wave maxima reuse the front of that buffer afterwards), every wave walks its
+ * share of the history positions and reads a history row ONCE, in 16-byte loads, for all k dot products.  No float atomics, fixed
+ * reduction order: results do not depend on wave scheduling.
+ * CC_ERR_ARG: NULL pointers (sel_score excepted), S < 0, k outside [1, 8], D < 4, not 0 <= hist_lo <= hist_n < hist_ld, alpha outside
+ * [0, 1] or not finite, step outside [0, cap_ld).  CC_ERR_SHAPE: D % 4, D > 2048.  S == 0: CC_OK, nothing is launched. */
+int cc_contrastive_select(int32_t S, int32_t k, int32_t D, const float* cand_h, const float* cand_prob, const int32_t* cand_tok, float* hist,
+                          int32_t hist_ld, int32_t hist_lo, int32_t hist_n, float alpha, int32_t stop_token, uint8_t* stopped, int32_t* lengths,
+                          int32_t* sel, int32_t* src_rows, uint8_t* skip_rows, int32_t* captions, int32_t cap_ld, int32_t step, float* sel_score,
+                          void* stream);
 /* gathers wte rows for next tokens: out fp32 [R, D] (base.py:117) */
 int cc_embed_tokens(const cc_gpt2_cfg* cfg, int32_t R, const float* w32, const int32_t* tokens, float* out, void* stream);
 /* its gradient: dwte fp32 [Vp, D] += scatter of dout fp32 [R, D] by tokens (rows sharing an id accumulate).  The non-deterministic form:
