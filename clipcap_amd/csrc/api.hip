@@ -1,5 +1,5 @@
 // C ABI (include/clipcap_hip.h) — orchestration of the mapper and GPT-2 training/inference passes out of the HIP
-// kernels in gemm.hip.h / kernels.hip / layernorm.hip / reduce.hip / loss.hip / attention.hip.  No state, no allocation, no synchronisation: everything is enqueued on the
+// kernels in gemm.hip.h / kernels.hip / layernorm.hip / reduce.hip / loss.hip / smooth.hip / attention.hip.  No state, no allocation, no synchronisation: everything is enqueued on the
 // caller's stream and lives in caller-owned arenas / workspaces.
 #include "../../include/clipcap_hip.h"
 #include "gemm_api.h"
@@ -702,8 +702,60 @@ int CC_API(cc_gpt2_logits)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const f
     return gemm_f32out(0, 0, w.hf16, D, W16(w16, o.wte), D, M, Ns, D, logits, (int)ldl, nullptr, 0, 1.0f, 1, cx);
 }
 
+namespace {
+// Label smoothing (cc_lmhead_ce_fwd_smooth / cc_lmhead_ce_bwd_smooth): the caller's scratch, carved.  part: the slice partials of wbar.
+struct SmoothScratch {
+    float *wbar, *hsum, *zbar, *term, *coef, *part;
+    int64_t floats;
+    SmoothScratch(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, float* base) {
+        const size_t D = c->D, Mc = ((size_t)s->B * (s->T - s->L) + 3) & ~size_t(3);      // every block starts 16-byte aligned
+        size_t off = 0;
+        const auto take = [&](size_t n) { float* r = base ? base + off : nullptr; off += n; return r; };
+        wbar = take(D); hsum = take(D); zbar = take(Mc); term = take(Mc); coef = take(2 * Mc);
+        part = take((size_t)smooth_wbar_slices(c->V) * D);
+        floats = (int64_t)off;
+    }
+};
+// eps in [0, 1) and a usable scratch; written so that a NaN fails
+inline bool smooth_ok(float eps, const float* scratch) { return eps >= 0.f && eps < 1.f && scratch && !((uintptr_t)scratch & 15); }
+
+// cc_lmhead_ce_fwd (scratch == nullptr: stats of 2 floats) and cc_lmhead_ce_fwd_smooth (stats of 3) share this body
+static int lmhead_ce_fwd_body(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const int64_t* tokens,
+                       float eps, float* scratch, float* stats, void* stream);
+static int lmhead_ce_bwd_body(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const float* denom,
+                       const float* loss_scale, float eps, float* scratch, float* g32, void* stream);
+}  // namespace
+
 int CC_API(cc_lmhead_ce_fwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const int64_t* tokens,
                      float* stats, void* stream) {
+    return lmhead_ce_fwd_body(c, s, w32, w16, ws, tokens, 0.f, nullptr, stats, stream);
+}
+
+int64_t CC_API(cc_lmhead_smooth_scratch_floats)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s) {
+    if (!gpt2_cfg_ok(c) || !shape_ok(c, s)) return CC_ERR_SHAPE;
+    return SmoothScratch(c, s, nullptr).floats;
+}
+
+int CC_API(cc_lmhead_ce_fwd_smooth)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const int64_t* tokens,
+                            float eps, float* scratch, float* stats3, void* stream) {
+    if (!smooth_ok(eps, scratch)) return CC_ERR_ARG;
+    return lmhead_ce_fwd_body(c, s, w32, w16, ws, tokens, eps, scratch, stats3, stream);
+}
+
+int CC_API(cc_lmhead_ce_bwd_smooth)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const float* denom,
+                            const float* loss_scale, float eps, float* scratch, float* g32, void* stream) {
+    if (!smooth_ok(eps, scratch)) return CC_ERR_ARG;
+    return lmhead_ce_bwd_body(c, s, w32, w16, ws, denom, loss_scale, eps, scratch, g32, stream);
+}
+
+int CC_API(cc_lmhead_ce_bwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const float* denom,
+                     const float* loss_scale, float* g32, void* stream) {
+    return lmhead_ce_bwd_body(c, s, w32, w16, ws, denom, loss_scale, 0.f, nullptr, g32, stream);
+}
+
+namespace {
+static int lmhead_ce_fwd_body(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const int64_t* tokens,
+                       float eps, float* scratch, float* stats, void* stream) {
     if (!gpt2_cfg_ok(c) || !shape_ok(c, s) || s->mode < 1 || s->L < 1 || !w32 || !w16 || !ws || !tokens || !stats) return CC_ERR_ARG;
     const int cap = s->T - s->L;
     if (cap != s->cap) return CC_ERR_SHAPE;  // the loss consumes every token column (model.py:108-109)
@@ -720,8 +772,15 @@ int CC_API(cc_lmhead_ce_fwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const
     CC_TIMED(CC_SITE_LMHEAD_FWD, st, gemm_lmhead(w.hf16, D, W16(w16, o.wte), D, Mc, c->Vp, c->V, D, lm_logits(c, s, w.logits16), c->Vp, w.pmax, w.psum, npart, w.target, w.tgt_logit, cx,
                                                  ef ? w.cref : nullptr));
     CC_TRY(ce_rows(w.pmax, w.psum, npart, w.target, ef ? w.cref : w.tgt_logit, w.lse_row, w.row_loss, stats, Mc, st));   // cref IS the target logit
-    return CC_OK;
+    if (!scratch) return CC_OK;
+    if (eps == 0.f)      // the plain chain, and the third float
+        return hipMemcpyAsync(stats + 2, stats, sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
+    // + eps (z_t - zbar) per kept row: wbar from the rows the lm_head GEMM read, zbar a GEMV over the stored hf — no pass over V
+    const SmoothScratch sm(c, s, scratch);
+    CC_TRY(smooth_wbar(reinterpret_cast<const act_t*>(wte_rows), c->V, D, sm.part, sm.wbar, st));
+    return smooth_rows(w.hf16, sm.wbar, D, w.target, ef ? w.cref : w.tgt_logit, eps, sm.zbar, sm.term, stats, Mc, st);
 }
+}  // namespace
 
 int CC_API(cc_lmhead_score)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const int64_t* tokens,
                     int32_t ignore_zero, float* token_logprob, float* sample_stats, void* stream) {
@@ -740,8 +799,9 @@ int CC_API(cc_lmhead_score)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const 
     return score_rows(w.pmax, w.psum, npart, w.keep, w.tgt_logit, w.lse_row, token_logprob, sample_stats, s->B, cap, st);
 }
 
-int CC_API(cc_lmhead_ce_bwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const float* denom,
-                     const float* loss_scale, float* g32, void* stream) {
+namespace {
+static int lmhead_ce_bwd_body(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const float* denom,
+                       const float* loss_scale, float eps, float* scratch, float* g32, void* stream) {
     if (!gpt2_cfg_ok(c) || !shape_ok(c, s) || s->mode < 1 || !w32 || !w16 || !ws || !denom || (s->mode == 2 && !g32)) return CC_ERR_ARG;
     const int cap = s->T - s->L;
     Gpt2Pass ps(c, s, cap, ws, stream);
@@ -782,6 +842,18 @@ int CC_API(cc_lmhead_ce_bwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const
             CC_TRY(gemm_wgrad(lg, c->Vp, w.hf16, D, c->Vp, D, Mc, g32 + o.wte, D, w.wg_scratch, cx));
         }
     }
+    if (scratch && eps != 0.f) {
+        // label smoothing, a pass of its own after the input-gradient GEMM and its fix: d hf += c (wte[t] - wbar) with the forward's wbar;
+        // tied lm_head: d wte[t] += c hf (a row scatter, as the one-hot term above) and d wte[v < V] -= (sum of c hf) / V (one vector)
+        const SmoothScratch sm(c, s, scratch);
+        CC_TRY(smooth_dhf(w.dhf16, w.target, denom, loss_scale, eps, reinterpret_cast<const act_t*>(fix.wte), sm.wbar, sm.coef, D, Mc, st));
+        if (full) {
+            ScatterSrc sc;
+            sc.ids32 = w.target; sc.act = w.hf16; sc.fac = sm.coef;
+            CC_TRY(scatter_rows(sc, Mc, D, c->Vp, g32 + o.wte, w.scat, st));
+            CC_TRY(smooth_dwte_bcast(w.hf16, sm.coef, D, Mc, c->V, sm.hsum, g32 + o.wte, cx));
+        }
+    }
     if (hipMemsetAsync(w.dx32, 0, (size_t)M * D * sizeof(float), st) != hipSuccess) return CC_ERR_LAUNCH;
     const size_t dx16_bytes = (size_t)M * D * (w.dx16.img ? 3 * sizeof(op16_t) : sizeof(act_t));     // (an image where the top layer's backward reads one)
     if (hipMemsetAsync(w.dx16.p, 0, dx16_bytes, st) != hipSuccess) return CC_ERR_LAUNCH;
@@ -789,6 +861,7 @@ int CC_API(cc_lmhead_ce_bwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const
                   full ? g32 + o.lnf_b : nullptr, Mc, D, cx));
     return CC_OK;
 }
+}  // namespace
 
 // Test hooks around the lm_head / loss chain (tests/lm_ref.py): carve and copy, no kernels of their own.
 int CC_API(cc_lmhead_put_x)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, void* ws, const float* x, void* stream) {

@@ -111,6 +111,21 @@ int lm_rowfac(const float* cref, const float* lse, const int* target, const floa
 int lm_dgrad_fix(act_t* dhf, const float* fac, const int* target, const op16_t* wte, int D, int M, hipStream_t st);
 int lm_scale_rows(const act_t* hf, const float* fac, act_t* out, int D, int M, hipStream_t st);
 
+// Label smoothing around the chain above (smooth.hip; include/clipcap_hip.h cc_lmhead_ce_fwd_smooth for the algebra).  wte: the rows as
+// they are read elementwise ([V][D] of the operand image; bf16x3: of the fp32 master).  All sums in a fixed order, no atomics.
+//   smooth_wbar       wbar[d] = (sum over v < V of wte[v][d]) / V: slice partials in part (smooth_wbar_slices(V) * D floats), then folded in one fixed order
+//   smooth_rows       zbar[m] = hf[m] . wbar; term[m] = target[m] != 0 ? eps (tgt[m] - zbar[m]) : 0; stats3[2] = stats3[0], stats3[0] += sum of term
+//   smooth_dhf        coef[m] = {0, -c_m}, c_m = (target[m] != 0) eps loss_scale / max(denom, 1); dhf[m][:] += c_m (wte[target[m]][:] - wbar[:])
+//   smooth_dwte_bcast hsum[:] = sum of c_m hf[m][:] (partials in the call's reduction scratch, fold_partials); dwte[v][:] -= hsum[:] / V, v < V
+//                     (the other half, dwte[target[m]][:] += c_m hf[m][:], is scatter_rows' act form fed coef)
+inline int smooth_wbar_slices(int V) { return std::max(1, std::min((V + 127) / 128, 256)); }
+int smooth_wbar(const act_t* wte, int V, int D, float* part, float* wbar, hipStream_t st);
+int smooth_rows(const act_t* hf, const float* wbar, int D, const int* target, const float* tgt, float eps, float* zbar, float* term,
+                float* stats3, int M, hipStream_t st);
+int smooth_dhf(act_t* dhf, const int* target, const float* denom, const float* loss_scale, float eps, const act_t* wte, const float* wbar,
+               float* coef, int D, int M, hipStream_t st);
+int smooth_dwte_bcast(const act_t* hf, const float* coef, int D, int M, int V, float* hsum, float* dwte, Call& cx);
+
 int adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, float wd, int step, float gscale,
           const float* loss_scale, const float* found_inf, hipStream_t st, op16_t* w16 = nullptr,   // w16: also store the 16-bit copy of the updated parameters
           const float* clip = nullptr);            // clip (device, nullable): the gradient is also multiplied by clip[0] (grad_clip_coef)

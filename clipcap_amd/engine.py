@@ -566,6 +566,14 @@ class Gpt2Engine:
         return dx0
 
 
+def check_label_smoothing(eps) -> float:
+    """eps of a label-smoothed loss as a float in [0, 1); ValueError otherwise (NaN included), before anything is launched"""
+    e = float(eps)
+    if not 0.0 <= e < 1.0:
+        raise ValueError(f"label_smoothing must lie in [0, 1), got {eps!r}")
+    return e
+
+
 class ClipCapEngine:
     """Training step of ClipCapModel (reference model.py:94-113) as straight-line forward + backward kernel chains."""
 
@@ -580,6 +588,11 @@ class ClipCapEngine:
         # global-norm clipping (optimizer_step(max_grad_norm=...)): built on first use; last_grad_norm views its device-side norm
         self.clipper: Optional[GradClipper] = None
         self.last_grad_norm: Optional[torch.Tensor] = None
+        # label smoothing (forward_backward(label_smoothing=...)): the 3-float stats and the scratch of cc_lmhead_ce_*_smooth, built on
+        # first use; last_nll = the mean plain NLL of the last step (a device scalar; equal to the returned loss without smoothing)
+        self.stats3: Optional[torch.Tensor] = None
+        self.smooth_scratch: Optional[torch.Tensor] = None
+        self.last_nll: Optional[torch.Tensor] = None
 
     def _clipper(self, dev, max_norm: float) -> GradClipper:
         if self.clipper is None or self.clipper.device != dev:
@@ -628,7 +641,7 @@ class ClipCapEngine:
             sc.update()
 
     def forward_backward(self, tokens: torch.Tensor, embeds: torch.Tensor, reduce_stats=None, backward: bool = True,
-                         on_grads_ready=None, dropout=None) -> torch.Tensor:
+                         on_grads_ready=None, dropout=None, label_smoothing: float = 0.0) -> torch.Tensor:
         """tokens int64 (B,cap) padded with -1; embeds fp32 (B,E)/(B,W,E).
 
         Returns the mean loss over kept targets (device scalar).  Gradients are ACCUMULATED into the arenas' g32.
@@ -642,7 +655,12 @@ class ClipCapEngine:
         cc_gpt2_shape, so concurrent engines on other streams are unaffected).
         With fp16 operands the gradients left in the arenas are multiplied by the current loss scale (self.scaler.scale);
         optimizer_step() divides it out.
+        ``label_smoothing``: eps in [0, 1) of F.cross_entropy(..., ignore_index=0, label_smoothing=eps) over the real vocabulary.  0.0
+        makes exactly the calls (and the 2-float stats) of a step without the option; a positive value goes through
+        cc_lmhead_ce_fwd_smooth / cc_lmhead_ce_bwd_smooth with a 3-float stats [smoothed loss sum, kept count, plain NLL sum], returns
+        the smoothed mean as torch does and leaves the mean plain NLL (what perplexity is made of) in ``last_nll``, a device scalar.
         """
+        eps = check_label_smoothing(label_smoothing)
         l = _lib.lib()
         g, m = self.gpt2, self.mapper
         dev = g.arena.device
@@ -658,23 +676,41 @@ class ClipCapEngine:
         st = _stream(dev)
         ga = g.arena
         prefix = m.forward(embeds, save=True)
-        return self._forward_backward(l, g, m, ga, shp, ws, st, prefix, tokens, reduce_stats, backward, on_grads_ready, dev)
+        return self._forward_backward(l, g, m, ga, shp, ws, st, prefix, tokens, reduce_stats, backward, on_grads_ready, dev, eps)
 
-    def _forward_backward(self, l, g, m, ga, shp, ws, st, prefix, tokens, reduce_stats, backward, on_grads_ready, dev):
+    def _smooth_buffers(self, l, g, shp, dev) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(3-float stats, scratch) of the label-smoothed loss: the caller's buffers of cc_lmhead_ce_*_smooth, kept between steps"""
+        n = check(l.cc_lmhead_smooth_scratch_floats(C.byref(g.cfg), C.byref(shp)), "cc_lmhead_smooth_scratch_floats")
+        if self.stats3 is None or self.stats3.device != dev:
+            self.stats3 = torch.zeros(3, dtype=torch.float32, device=dev)
+        if self.smooth_scratch is None or self.smooth_scratch.device != dev or self.smooth_scratch.numel() < n:
+            self.smooth_scratch = torch.empty(n, dtype=torch.float32, device=dev)
+        return self.stats3, self.smooth_scratch
+
+    def _forward_backward(self, l, g, m, ga, shp, ws, st, prefix, tokens, reduce_stats, backward, on_grads_ready, dev, eps=0.0):
         check(l.cc_gpt2_embed(C.byref(g.cfg), C.byref(shp), _p(ga.w32), _p(prefix), _p(tokens), _p(ws), st), "cc_gpt2_embed")
         check(l.cc_gpt2_fwd(C.byref(g.cfg), C.byref(shp), _p(ga.w32), _p(ga.w16), _p(ws), st), "cc_gpt2_fwd")
-        if self.stats is None or self.stats.device != dev:
-            self.stats = torch.zeros(2, dtype=torch.float32, device=dev)
-        stats = self.stats
-        check(l.cc_lmhead_ce_fwd(C.byref(g.cfg), C.byref(shp), _p(ga.w32), _p(ga.w16), _p(ws), _p(tokens), _p(stats), st), "cc_lmhead_ce_fwd")
+        if eps > 0.0:
+            stats, scratch = self._smooth_buffers(l, g, shp, dev)
+            check(l.cc_lmhead_ce_fwd_smooth(C.byref(g.cfg), C.byref(shp), _p(ga.w32), _p(ga.w16), _p(ws), _p(tokens), eps, _p(scratch),
+                                            _p(stats), st), "cc_lmhead_ce_fwd_smooth")
+        else:
+            if self.stats is None or self.stats.device != dev:
+                self.stats = torch.zeros(2, dtype=torch.float32, device=dev)
+            stats = self.stats
+            check(l.cc_lmhead_ce_fwd(C.byref(g.cfg), C.byref(shp), _p(ga.w32), _p(ga.w16), _p(ws), _p(tokens), _p(stats), st), "cc_lmhead_ce_fwd")
         if reduce_stats is not None:
             reduce_stats(stats)
         if backward:
             g32 = ga.grads() if self.train_lm else None
             denom = stats[1:2]
             sc = self._scaler(dev)
-            check(l.cc_lmhead_ce_bwd(C.byref(g.cfg), C.byref(shp), _p(ga.w32), _p(ga.w16), _p(ws), _p(denom),
-                                     _p(sc.scale) if sc is not None else None, _p(g32), st), "cc_lmhead_ce_bwd")
+            if eps > 0.0:
+                check(l.cc_lmhead_ce_bwd_smooth(C.byref(g.cfg), C.byref(shp), _p(ga.w32), _p(ga.w16), _p(ws), _p(denom),
+                                                _p(sc.scale) if sc is not None else None, eps, _p(scratch), _p(g32), st), "cc_lmhead_ce_bwd_smooth")
+            else:
+                check(l.cc_lmhead_ce_bwd(C.byref(g.cfg), C.byref(shp), _p(ga.w32), _p(ga.w16), _p(ws), _p(denom),
+                                         _p(sc.scale) if sc is not None else None, _p(g32), st), "cc_lmhead_ce_bwd")
             dprefix = torch.empty_like(prefix)
             if on_grads_ready is None or not self.train_lm:
                 check(l.cc_gpt2_bwd(C.byref(g.cfg), C.byref(shp), _p(ga.w32), _p(ga.w16), _p(ws), _p(tokens), _p(dprefix), _p(g32), st), "cc_gpt2_bwd")
@@ -689,7 +725,9 @@ class ClipCapEngine:
                     on_grads_ready(1, g.layer_span(lo)[0] if lo > 0 else 0, g.layer_span(hi - 1)[1])   # lo == 0: + wte / wpe
                     hi = lo
             m.backward(dprefix, on_layers_done=(None if on_grads_ready is None else (lambda lo, hi: on_grads_ready(0, lo, hi))))
-        return stats[0] / stats[1].clamp_min(1.0)
+        loss = stats[0] / stats[1].clamp_min(1.0)
+        self.last_nll = loss if eps == 0.0 else stats[2] / stats[1].clamp_min(1.0)
+        return loss
 
     @torch.no_grad()
     def score(self, tokens: torch.Tensor, embeds: Optional[torch.Tensor] = None, *, prefix: Optional[torch.Tensor] = None,

@@ -19,7 +19,7 @@ from typing import Optional, Tuple
 import torch
 import torch.nn as nn
 
-from clipcap_amd.engine import ClipCapEngine
+from clipcap_amd.engine import ClipCapEngine, check_label_smoothing
 from clipcap_amd.model.config import Config, TrainingConfig
 from clipcap_amd.model.gpt2 import GPT2LM
 from clipcap_amd.model.mapper import TransformerMapper, TransformerMapperWindowed
@@ -57,6 +57,10 @@ class _StepLoss(torch.autograd.Function):
 
 class ClipCapModel(nn.Module):
     _train_lm = True
+    # eps of F.cross_entropy(..., label_smoothing=eps) in training_step / fused_step: the reference's training_step with one more argument.
+    # A plain attribute (not a Config field): set it on the model, or on the namespace handed to train().  evaluate() and score_captions
+    # keep reporting the plain likelihood.
+    label_smoothing = 0.0
 
     def __init__(self, config: Config, language_model: Optional[GPT2LM] = None):
         super().__init__()
@@ -99,20 +103,24 @@ class ClipCapModel(nn.Module):
         rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
         return ps + (int(torch.randint(0, 2 ** 48, (1,)).item()) ^ (rank << 50),)
 
-    def fused_step(self, batch: Tuple[torch.Tensor, torch.Tensor], lr: float, reducer=None, max_grad_norm: Optional[float] = None) -> torch.Tensor:
+    def fused_step(self, batch: Tuple[torch.Tensor, torch.Tensor], lr: float, reducer=None, max_grad_norm: Optional[float] = None,
+                   label_smoothing: Optional[float] = None) -> torch.Tensor:
         """One optimizer step: zero grads -> forward+backward kernel chains -> (all-reduce) -> fused AdamW. Returns the loss.
         ``max_grad_norm``: global gradient-norm clipping on the device (Lightning's gradient_clip_val; inf: only report the norm);
-        the norm of this step's gradients is then ``last_grad_norm``."""
+        the norm of this step's gradients is then ``last_grad_norm``.
+        ``label_smoothing``: eps of F.cross_entropy(..., label_smoothing=eps) for this step (None: the ``label_smoothing`` attribute);
+        the returned loss is the smoothed one, ``last_nll`` the plain mean NLL."""
         tokens, embeds = batch
+        eps = check_label_smoothing(self.label_smoothing if label_smoothing is None else label_smoothing)
         eng = self.engine
         eng.zero_grad()
         if reducer is not None:
             reducer.begin()
             loss = eng.forward_backward(tokens, embeds, reduce_stats=reducer.reduce_stats, on_grads_ready=reducer.on_grads_ready,
-                                        dropout=self._dropout())
+                                        dropout=self._dropout(), label_smoothing=eps)
             reducer.finish()
         else:
-            loss = eng.forward_backward(tokens, embeds, dropout=self._dropout())
+            loss = eng.forward_backward(tokens, embeds, dropout=self._dropout(), label_smoothing=eps)
         self._opt_step += 1
         # partitioned gradients (ZeRO stage 2): a rank holds the reduced sum of its own slices only, so the squared norms are summed
         partitioned = reducer is not None and reducer.owners is not None
@@ -124,6 +132,12 @@ class ClipCapModel(nn.Module):
     def last_grad_norm(self) -> Optional[torch.Tensor]:
         """1-element device tensor: the global gradient norm of the last step taken with ``max_grad_norm`` (None before the first)."""
         return self.engine.last_grad_norm
+
+    @property
+    def last_nll(self) -> Optional[torch.Tensor]:
+        """device scalar: the mean plain NLL of the last step (what perplexity is made of; the returned loss itself when
+        ``label_smoothing`` is 0; None before the first step)."""
+        return self.engine.last_nll
 
     def _weight_decay(self) -> float:
         """model.py:72-77: ``--enable-deepspeed`` swaps torch.optim.AdamW (weight_decay 0.01) for DeepSpeed's
@@ -165,7 +179,7 @@ class ClipCapModel(nn.Module):
         tokens, embeds = batch
         eng = self.engine
         eng.zero_grad()
-        loss = eng.forward_backward(tokens, embeds, dropout=self._dropout())
+        loss = eng.forward_backward(tokens, embeds, dropout=self._dropout(), label_smoothing=check_label_smoothing(self.label_smoothing))
         self.last_loss = loss
         if torch.is_grad_enabled():
             return _StepLoss.apply(self, loss, *[self._lookup(o, n) for o, n in self._param_index])

@@ -18,6 +18,7 @@ from clipcap_amd.train.args import add_training_args
 from clipcap_amd.train.callback import CheckpointSaver, resume
 from clipcap_amd.train.dataloader import DevicePrefetcher, get_dataloader
 from clipcap_amd._lib import OP_BF16, OP_FP16, OP_X3
+from clipcap_amd.engine import check_label_smoothing
 from clipcap_amd.train.ddp import GradReducer, ZeroShard, zero_stage
 
 
@@ -106,6 +107,12 @@ def train(args: Namespace, tokenizer=None, language_model=None, step_hook=None) 
     clip_val = float(clip_val) if clip_val else None
     if clip_val is not None and rank == 0:
         print(f"clipcap_amd: gradients clipped to a global norm of {clip_val:g} on the device", flush=True)
+    # F.cross_entropy's label_smoothing, the same way: not a CLI flag of the reference, a caller of train() sets it on the namespace
+    smoothing = getattr(args, "label_smoothing", None)
+    if smoothing is not None:
+        model.label_smoothing = check_label_smoothing(smoothing)
+    if model.label_smoothing > 0.0 and rank == 0:
+        print(f"clipcap_amd: label smoothing {model.label_smoothing:g} in the fused lm_head loss (the logged nll is the plain likelihood)", flush=True)
     logger = None
     if args.enable_wandb and rank == 0:
         try:
@@ -135,9 +142,12 @@ def _run_epochs(args, model, dataset, device, sched, reducer, saver, sharded, ra
             if rank == 0 and step % max(1, args.logging_frequency) == 0:
                 val = float(loss)
                 record = {"loss": val}
+                smooth = model.label_smoothing > 0.0
+                if smooth:                                # the plain likelihood beside the smoothed objective
+                    record["nll"] = float(model.last_nll)
                 if clip_val is not None:                  # read here only, where float(loss) has already synchronised
                     record["grad_norm"] = float(model.last_grad_norm)
-                print(f"epoch {epoch} step {step}/{args.total_steps} loss {val:.4f}"
+                print(f"epoch {epoch} step {step}/{args.total_steps} loss {val:.4f}" + (f" nll {record['nll']:.4f}" if smooth else "")
                       + (f" grad_norm {record['grad_norm']:.4f}" if clip_val is not None else ""), flush=True)
                 if logger is not None:
                     logger.log(record, step=step)

@@ -67,8 +67,8 @@ extern "C" {
  * (cc_decode_image*, cc_decode_xt_image*, cc_decode_fwd_x, cc_decode_ws_check, cc_decode_last_path) moved to include/clipcap_hip_lab.h —
  * the lab library exports them, the product library does not.  ADDED since (still 3: no existing entry point changed): cc_lmhead_score,
  * cc_grad_norm_scratch_floats, cc_grad_sqnorm, cc_grad_clip_coef, cc_adamw_step_clip, cc_logits_constrain, cc_beam_group_step,
- * cc_beam_group_ws_bytes, cc_decode_hidden_unit, cc_contrastive_topk, cc_contrastive_select, and the decode-attention test hook
- * cc_decode_attention. */
+ * cc_beam_group_ws_bytes, cc_decode_hidden_unit, cc_contrastive_topk, cc_contrastive_select, the decode-attention test hook
+ * cc_decode_attention, and the label-smoothed loss cc_lmhead_smooth_scratch_floats, cc_lmhead_ce_fwd_smooth, cc_lmhead_ce_bwd_smooth. */
 #define CC_ABI_VERSION 3
 int cc_abi_version(void);
 
@@ -212,6 +212,23 @@ int cc_lmhead_score(const cc_gpt2_cfg* cfg, const cc_gpt2_shape* shp, const floa
  * g32 may be NULL unless mode 2. */
 int cc_lmhead_ce_bwd(const cc_gpt2_cfg* cfg, const cc_gpt2_shape* shp, const float* w32, const uint16_t* w16, void* ws,
                      const float* denom, const float* loss_scale, float* g32, void* stream);
+/* The same loss with label smoothing, F.cross_entropy(..., ignore_index=0, label_smoothing=eps) over the V real classes, as rank-one
+ * corrections around the chain above (the GEMMs, their epilogues and the stored logits are the plain chain's):
+ *   loss_row(eps) = loss_row(0) + eps (z_t - zbar),  zbar = hf . wbar,  wbar = the mean of the first V rows of wte (rows V..Vp-1 take no
+ *   part in it, receive no gradient and stay bit-untouched);  d hf += c (wte[t] - wbar);  mode 2: d wte[t] += c hf,
+ *   d wte[v] -= (sum over kept rows of c hf) / V for v < V;  c = eps * loss_scale / max(denom, 1) on kept rows, 0 elsewhere.
+ * eps in [0, 1).  scratch: cc_lmhead_smooth_scratch_floats(cfg, shp) device floats of the caller's, 16-byte aligned; the forward call
+ * leaves wbar and zbar there and the backward call of the same pass reads them, so hand both the same buffer (the workspace of
+ * (cfg, shp) does not grow).  stats3 (3 device floats, fully written): [0] the smoothed loss sum, [1] kept rows, [2] the plain NLL sum
+ * = what cc_lmhead_ce_fwd puts in stats[0].  denom = stats3 + 1 (or its all-reduced copy), as above.  eps == 0 launches exactly what
+ * cc_lmhead_ce_fwd / cc_lmhead_ce_bwd launch, plus the store of stats3[2].  Every sum runs in a fixed order (no atomics): a mode-2 step is
+ * bit-reproducible from run to run.  CC_ERR_ARG with nothing written: eps < 0, eps >= 1 or NaN, a NULL or misaligned scratch, mode 0, and
+ * whatever the plain entry points refuse.  cc_lmhead_smooth_scratch_floats: CC_ERR_SHAPE for a cfg / shape the library refuses. */
+int64_t cc_lmhead_smooth_scratch_floats(const cc_gpt2_cfg* cfg, const cc_gpt2_shape* shp);
+int cc_lmhead_ce_fwd_smooth(const cc_gpt2_cfg* cfg, const cc_gpt2_shape* shp, const float* w32, const uint16_t* w16, void* ws,
+                            const int64_t* tokens, float eps, float* scratch, float* stats3, void* stream);
+int cc_lmhead_ce_bwd_smooth(const cc_gpt2_cfg* cfg, const cc_gpt2_shape* shp, const float* w32, const uint16_t* w16, void* ws,
+                            const float* denom, const float* loss_scale, float eps, float* scratch, float* g32, void* stream);
 /* backward through the blocks.  dprefix fp32 [B, L, D] receives d loss / d prefix (rows 0..L-1 of d x0).
  * mode 2 additionally accumulates all GPT-2 weight gradients (incl. wte/wpe) into g32. */
 int cc_gpt2_bwd(const cc_gpt2_cfg* cfg, const cc_gpt2_shape* shp, const float* w32, const uint16_t* w16, void* ws,
