@@ -130,6 +130,7 @@ SIGNATURES = {
     "cc_grad_sqnorm": (_I, [_P, _L, _P, _P, _P]),
     "cc_grad_clip_coef": (_I, [_P, _F, _F, _P, _P, _P]),
     "cc_adamw_step_clip": (_I, [_I, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _F, _P, _P, _P, _P, _P]),
+    "cc_adamw_step_ema": (_I, [_I, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _F, _P, _P, _P, _P, _P, _F, _P]),
     "cc_dropout_mask": (_I, [C.c_uint64, _I, _I, _F, _L, _P, _P]),
     "cc_sample_step": (_I, [_P, _I, _I, _I, _F, _I, _F, _I, _P, _I, _I, _F, _P, _P, _P, _P]),
     "cc_sample_step_lp": (_I, [_P, _I, _I, _I, _F, _I, _F, _I, _P, _I, _I, _F, _I, _F, _P, _P, _P, _P]),

@@ -1012,6 +1012,18 @@ int CC_API(cc_adamw_step_clip)(float* p32, const float* g32, float* m, float* v,
     return adamw(p32, g32, m, v, (size_t)n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, loss_scale, found_inf, S_(stream), w16, clip);
 }
 
+int CC_API(cc_adamw_step_ema)(float* p32, const float* g32, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                      float weight_decay, int32_t step, float grad_scale, const float* loss_scale, const float* found_inf, const float* clip,
+                      uint16_t* w16, float* ema, float ema_decay, void* stream) {
+    if (!p32 || !g32 || !m || !v || n < 0 || step < 0 || (step == 0 && !loss_scale)) return CC_ERR_ARG;
+    if (w16 && kX3) return CC_ERR_ARG;      // as cc_adamw_step_cast: no flat cast in the bf16x3 mode
+    if (!ema || (reinterpret_cast<uintptr_t>(ema) & 15) || !(ema_decay >= 0.f && ema_decay < 1.f)) return CC_ERR_ARG;      // (NaN fails both comparisons)
+    const uintptr_t e0 = reinterpret_cast<uintptr_t>(ema), p0 = reinterpret_cast<uintptr_t>(p32), bytes = (uintptr_t)n * sizeof(float);
+    if (e0 == p0 || (e0 < p0 + bytes && p0 < e0 + bytes)) return CC_ERR_ARG;      // the average must not alias the parameters
+    return adamw(p32, g32, m, v, (size_t)n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, loss_scale, found_inf, S_(stream), w16, clip, ema,
+                 ema_decay);
+}
+
 int64_t CC_API(cc_grad_norm_scratch_floats)(void) { return (int64_t)GRAD_NORM_BLOCKS; }
 
 int CC_API(cc_cast_op16)(const float* src, uint16_t* dst, int64_t n, void* stream) {

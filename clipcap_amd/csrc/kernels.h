@@ -128,7 +128,8 @@ int smooth_dwte_bcast(const act_t* hf, const float* coef, int D, int M, int V, f
 
 int adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, float wd, int step, float gscale,
           const float* loss_scale, const float* found_inf, hipStream_t st, op16_t* w16 = nullptr,   // w16: also store the 16-bit copy of the updated parameters
-          const float* clip = nullptr);            // clip (device, nullable): the gradient is also multiplied by clip[0] (grad_clip_coef)
+          const float* clip = nullptr,            // clip (device, nullable): the gradient is also multiplied by clip[0] (grad_clip_coef)
+          float* ema = nullptr, float ema_decay = 0.f);      // ema (device, nullable, n floats, not aliasing p): ema = d * ema + (1 - d) * p after an applied step
 // grad_sqnorm (grads.hip, behind cc_grad_sqnorm): sumsq[0] += sum of g[i]^2, i < n (n % 4 == 0), bit for bit the same from run to run
 // and from box to box: the grid depends on n alone.
 // scratch: GRAD_NORM_BLOCKS floats of device scratch for this call.  The order, with n4 = n / 4 float4 groups,

@@ -261,14 +261,16 @@ int f32_to_op16_pad(const float* src, long long lds, int V, act_t* dst, int ldd,
 // parameter.  inv_scale (device, nullable) = loss scale to divide out of the gradients; found_inf (device, nullable) != 0 skips
 // the whole step (the GradScaler rule for an overflowed fp16 backward).
 // ------------------------------------------------------------------------------------------------------------
-template <bool DEVSTEP>      // DEVSTEP: Adam's step number is read from the loss scaler's device-side count (a separate instantiation: the
+template <bool DEVSTEP, bool EMA>      // DEVSTEP: Adam's step number is read from the loss scaler's device-side count (a separate instantiation: the
                              // pow evaluation must not cost the common kernel its registers — it measured 184 -> 223 us as a run-time branch)
+                             // EMA: also ema = d * ema + (1 - d) * p over the parameters just written (+4 B read, +4 B written per parameter); a
+                             // separate instantiation for the same reason, so the two plain forms compile from the text they always had
 __global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                float* __restrict__ v, size_t n4, float lr, float b1, float b2, float eps, float wd, float bc1,
                                                float bc2_sqrt, float gscale, const float* __restrict__ loss_scale,
                                                const float* __restrict__ found_inf, op16_t* __restrict__ w16,
-                                               const float* __restrict__ clip) {
-    if (found_inf && found_inf[0] != 0.f) return;
+                                               const float* __restrict__ clip, float* __restrict__ ema, float d) {
+    if (found_inf && found_inf[0] != 0.f) return;      // a skipped step skips the average too
     if (loss_scale) gscale /= loss_scale[0];
     if (clip) gscale *= clip[0];      // global-norm clip coefficient (k_grad_clip_coef); 1.0f leaves gscale's bits as they are
     if constexpr (DEVSTEP) {      // step number = 1 + the loss scaler's count of APPLIED steps (loss_scale[2]): a skipped step does not advance Adam's bias correction
@@ -279,6 +281,8 @@ __global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const floa
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         float4 P = reinterpret_cast<float4*>(p)[i], G = reinterpret_cast<const float4*>(g)[i];
         float4 M = reinterpret_cast<float4*>(m)[i], V = reinterpret_cast<float4*>(v)[i];
+        float4 E;
+        if constexpr (EMA) E = reinterpret_cast<float4*>(ema)[i];
         float* pp = &P.x; float* gg = &G.x; float* mm = &M.x; float* vv = &V.x;
 #pragma unroll
         for (int e = 0; e < 4; e++) {
@@ -294,10 +298,15 @@ __global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const floa
         reinterpret_cast<float4*>(v)[i] = V;
         // the 16-bit operand copy of the updated parameters, while they are in registers: saves the separate cast pass over the arena
         if (w16) reinterpret_cast<uint2*>(w16)[i] = make_uint2(pack2op(P.x, P.y), pack2op(P.z, P.w));
+        if constexpr (EMA) {      // the convex form (d = 0 gives ema == p exactly), never e + (1 - d)(p - e): p - e can overflow or cancel
+            const float omd = 1.0f - d;
+            E.x = d * E.x + omd * P.x; E.y = d * E.y + omd * P.y; E.z = d * E.z + omd * P.z; E.w = d * E.w + omd * P.w;
+            reinterpret_cast<float4*>(ema)[i] = E;
+        }
     }
 }
 int adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, float wd, int step, float gscale,
-          const float* loss_scale, const float* found_inf, hipStream_t st, op16_t* w16, const float* clip) {
+          const float* loss_scale, const float* found_inf, hipStream_t st, op16_t* w16, const float* clip, float* ema, float ema_decay) {
     if (n & 3) return CC_ERR_SHAPE;
     if (!n) return CC_OK;
     if (step < 1 && !loss_scale) return CC_ERR_ARG;
@@ -305,8 +314,14 @@ int adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, floa
     const float bc2s = sqrtf(1.0f - powf(b2, (float)std::max(step, 1)));
     const size_t n4 = n >> 2;
     const dim3 gr = flat_grid(n4, 256, 4096);
-    if (step < 1) hipLaunchKernelGGL(k_adamw<true>, gr, dim3(256), 0, st, p, g, m, v, n4, lr, b1, b2, eps, wd, bc1, bc2s, gscale, loss_scale, found_inf, w16, clip);
-    else hipLaunchKernelGGL(k_adamw<false>, gr, dim3(256), 0, st, p, g, m, v, n4, lr, b1, b2, eps, wd, bc1, bc2s, gscale, loss_scale, found_inf, w16, clip);
+#define CC_ADAMW_(DEVSTEP, EMA) \
+    hipLaunchKernelGGL((k_adamw<DEVSTEP, EMA>), gr, dim3(256), 0, st, p, g, m, v, n4, lr, b1, b2, eps, wd, bc1, bc2s, gscale, loss_scale, found_inf, w16, clip, ema, ema_decay)
+    if (ema) {
+        if (step < 1) CC_ADAMW_(true, true);
+        else CC_ADAMW_(false, true);
+    } else if (step < 1) CC_ADAMW_(true, false);
+    else CC_ADAMW_(false, false);
+#undef CC_ADAMW_
     return CC_OK;
 }
 

@@ -54,6 +54,9 @@ class _Arena:
         self.g32: Optional[torch.Tensor] = None
         self.m: Optional[torch.Tensor] = None
         self.v: Optional[torch.Tensor] = None
+        # exponential moving average of the master (enable_ema / adamw_step(ema_decay=...)); None: no average is kept.  Like m / v it
+        # covers the own range only once the optimizer state is sharded
+        self.ema: Optional[torch.Tensor] = None
         self._w16_version = -1
         # optimizer-state sharding (train/ddp.py ZeroShard): (rank, [(lo, hi)] per rank, gather(t, ranges)).  m / v then cover the own range only
         self.zero = None
@@ -95,11 +98,11 @@ class _Arena:
             self._w16_version = -1
 
     def moved_to(self, device, sync_fn) -> "_Arena":
-        """A copy of this arena on `device` carrying the master, the gradient arena and the AdamW moments (resume() followed by
-        .to(device) must not lose the optimizer state)."""
+        """A copy of this arena on `device` carrying the master, the gradient arena, the AdamW moments and the weight average (resume()
+        followed by .to(device) must not lose the optimizer state)."""
         new = _Arena(self.n, device, sync_fn, self.op_dtype)
         new.w32.copy_(self.w32)
-        for name in ("g32", "m", "v"):
+        for name in ("g32", "m", "v", "ema"):
             t = getattr(self, name)
             if t is not None:
                 setattr(new, name, t.to(new.device))
@@ -109,11 +112,12 @@ class _Arena:
         """ZeRO stage 1 (the reference's --deepspeed-strategy, clipcap/train/args.py:87-92, which Lightning hands to DeepSpeed): this rank
         keeps the AdamW moments of elements [lo, hi) of the arena only and steps only those; ``gather(w32, ranges)`` then broadcasts every
         owner's updated slice (ddp.ZeroShard).  Gradients stay all-reduced over the whole arena, so the update of an element is the one
-        the unsharded step computes, bit for bit.  Full moments already present (a resumed run) are cut down to the own range."""
+        the unsharded step computes, bit for bit.  Full moments already present (a resumed run) are cut down to the own range, and so is
+        a full weight average."""
         per = (((self.n + world - 1) // world) + 7) // 8 * 8
         ranges = [(min(self.n, r * per), min(self.n, (r + 1) * per)) for r in range(world)]
         lo, hi = ranges[rank]
-        for name in ("m", "v"):
+        for name in ("m", "v", "ema"):
             t = getattr(self, name)
             if t is not None and t.numel() == self.n:
                 setattr(self, name, t[lo:hi].clone())
@@ -125,33 +129,68 @@ class _Arena:
         one slice, not two more full-size arenas on every rank (which is what sharding was meant to save)."""
         if self.zero is None or self.m is None:
             return self.m, self.v
+        return self._full_host(self.m), self._full_host(self.v)
+
+    def _full_host(self, t: torch.Tensor) -> torch.Tensor:
+        """Sharded state ``t`` (own range) over the whole arena as a HOST tensor, one owner's slice at a time (a collective)."""
+        rank, ranges, gather = self.zero
+        full = torch.empty(self.n, dtype=torch.float32)                  # host
+        for r, (a, b) in enumerate(ranges):
+            if b <= a:
+                continue
+            piece = t if r == rank else torch.empty(b - a, dtype=torch.float32, device=self.device)
+            gather(piece, [(0, b - a) if q == r else (0, 0) for q in range(len(ranges))])     # one broadcast: owner r's slice
+            full[a:b].copy_(piece)
+            del piece
+        return full
+
+    def enable_ema(self) -> None:
+        """Start the weight average at the current master: ema_0 = p_0.  With sharded optimizer state: the own range only.  A no-op if
+        an average is already kept."""
+        if self.ema is not None:
+            return
+        if self.zero is not None:
+            lo, hi = self.zero[1][self.zero[0]]
+            self.ema = self.w32[lo:hi].clone()
+        else:
+            self.ema = self.w32.clone()
+
+    def full_ema(self) -> Optional[torch.Tensor]:
+        """The weight average over the whole arena.  Replicated state: the device tensor itself.  Sharded state: a COLLECTIVE like
+        full_moments, returning a HOST tensor filled one owner's slice at a time."""
+        if self.zero is None or self.ema is None:
+            return self.ema
+        return self._full_host(self.ema)
+
+    def ema_on_device(self) -> Optional[torch.Tensor]:
+        """The weight average over the whole arena on the device.  Sharded state: a COLLECTIVE — a full-size buffer, the own slice copied
+        in, the owners' slices exchanged as the parameters are after a step."""
+        if self.zero is None or self.ema is None:
+            return self.ema
         rank, ranges, gather = self.zero
         lo, hi = ranges[rank]
-        out = []
-        for t in (self.m, self.v):
-            full = torch.empty(self.n, dtype=torch.float32)                  # host
-            for r, (a, b) in enumerate(ranges):
-                if b <= a:
-                    continue
-                piece = t if r == rank else torch.empty(b - a, dtype=torch.float32, device=self.device)
-                gather(piece, [(0, b - a) if q == r else (0, 0) for q in range(len(ranges))])     # one broadcast: owner r's slice
-                full[a:b].copy_(piece)
-                del piece
-            out.append(full)
-        return out[0], out[1]
+        buf = torch.empty(self.n, dtype=torch.float32, device=self.device)
+        buf[lo:hi].copy_(self.ema)
+        gather(buf, ranges)
+        return buf
 
     def grads(self) -> torch.Tensor:
         if self.g32 is None:
             self.g32 = torch.zeros(self.n, dtype=torch.float32, device=self.device)
         return self.g32
 
-    def _adamw(self, p, g, m, v, n, w16, lr, step, betas, eps, weight_decay, grad_scale, scaler, clip) -> None:
-        """One AdamW launch over n elements; w16 None: no cast.  ``clip`` None: the entry points every step used before clipping existed."""
+    def _adamw(self, p, g, m, v, n, w16, lr, step, betas, eps, weight_decay, grad_scale, scaler, clip, ema_decay=None) -> None:
+        """One AdamW launch over n elements; w16 None: no cast.  ``clip`` None: the entry points every step used before clipping existed.
+        ``ema_decay`` given: cc_adamw_step_ema (clip nullable), which also averages self.ema — the n elements matching p."""
         l, st = _lib.lib(), _stream(self.device)
         step = 0 if scaler is not None else step      # with a loss scaler the step number is its device-side count of applied steps
         ls = _p(scaler.scale) if scaler is not None else None
         fi = _p(scaler.found_inf) if scaler is not None else None
-        if clip is not None:
+        if ema_decay is not None:
+            assert self.ema.numel() == n
+            check(l.cc_adamw_step_ema(self.op_dtype, _p(p), _p(g), _p(m), _p(v), n, lr, betas[0], betas[1], eps, weight_decay, step, grad_scale,
+                                      ls, fi, _p(clip), _p(w16), _p(self.ema), ema_decay, st), "cc_adamw_step_ema")
+        elif clip is not None:
             check(l.cc_adamw_step_clip(self.op_dtype, _p(p), _p(g), _p(m), _p(v), n, lr, betas[0], betas[1], eps, weight_decay, step, grad_scale,
                                        ls, fi, _p(clip), _p(w16), st), "cc_adamw_step_clip")
         elif w16 is None:
@@ -169,11 +208,17 @@ class _Arena:
         return 0, self.n
 
     def adamw_step(self, lr: float, step: int, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, grad_scale: float = 1.0,
-                   scaler: Optional["LossScaler"] = None, clip: Optional[torch.Tensor] = None):
+                   scaler: Optional["LossScaler"] = None, clip: Optional[torch.Tensor] = None, ema_decay: Optional[float] = None):
         """torch.optim.AdamW math (reference model.py:73-77) over the whole arena, refreshing the 16-bit operand copy.
         ``scaler`` (fp16 operands): the gradients carry its loss scale, and a step whose backward overflowed is skipped on the device.
-        ``clip``: device float[1], the global-norm clip coefficient the gradients are also multiplied by (GradClipper.coef)."""
-        kw = (lr, step, betas, eps, weight_decay, grad_scale, scaler, clip)
+        ``clip``: device float[1], the global-norm clip coefficient the gradients are also multiplied by (GradClipper.coef).
+        ``ema_decay``: d in [0, 1) — the same launch also updates the weight average, ema = d * ema + (1 - d) * p over the parameters
+        it just wrote (cc_adamw_step_ema; enabled at the current master on first use); a step skipped on the device skips the average,
+        a sharded step averages the own slice.  None: exactly the launches of a step without the option."""
+        ema_decay = check_ema_decay(ema_decay)
+        if ema_decay is not None:
+            self.enable_ema()
+        kw = (lr, step, betas, eps, weight_decay, grad_scale, scaler, clip, ema_decay)
         if self.zero is not None:                       # sharded optimizer state: own slice, then the owners' slices travel
             rank, ranges, gather = self.zero
             lo, hi = ranges[rank]
@@ -574,6 +619,23 @@ def check_label_smoothing(eps) -> float:
     return e
 
 
+def check_ema_decay(value) -> Optional[float]:
+    """decay of the weight average: None (no average) or a float in [0, 1); ValueError otherwise (NaN included), before an engine, the
+    library or a device is touched"""
+    if value is None:
+        return None
+    d = float(value)
+    if not 0.0 <= d < 1.0:
+        raise ValueError(f"ema_decay must be None or lie in [0, 1), got {value!r}")
+    return d
+
+
+def ema_decay_at(decay: float, t: int, warmup: bool) -> float:
+    """d_t of optimizer step t (1-based, the host's count): ``decay``, or with warm-up min(decay, (1 + t) / (10 + t)) — the average
+    forgets its starting point quickly while the weights still move fast"""
+    return min(decay, (1.0 + t) / (10.0 + t)) if warmup else decay
+
+
 class ClipCapEngine:
     """Training step of ClipCapModel (reference model.py:94-113) as straight-line forward + backward kernel chains."""
 
@@ -619,7 +681,9 @@ class ClipCapEngine:
         ``max_grad_norm``: clip the gradients of all trained arenas together to this global 2-norm (clip_grad_norm_'s rule; inf: only
         measure it) and leave the norm on the device in ``last_grad_norm``; None: the step launches exactly what it launched without
         this option.  ``sync_norm(sumsq)``: the same in-place 1-float SUM over the ranks, given exactly when the gradients are
-        partitioned — each rank then squares only the slice it owns; with whole reduced arenas every rank computes the same bits alone."""
+        partitioned — each rank then squares only the slice it owns; with whole reduced arenas every rank computes the same bits alone.
+        ``ema_decay`` (forwarded to every trained arena's adamw_step with the other ``adamw_kw``): d in [0, 1) — each arena's weight
+        average is updated inside its AdamW launch, ema = d * ema + (1 - d) * p; a step the loss scaler skips leaves it untouched."""
         sc = self.scaler
         if sc is not None:
             for a in self.arenas():

@@ -13,13 +13,14 @@ written against the reference.
 """
 from __future__ import annotations
 
+import contextlib
 from types import SimpleNamespace
 from typing import Optional, Tuple
 
 import torch
 import torch.nn as nn
 
-from clipcap_amd.engine import ClipCapEngine, check_label_smoothing
+from clipcap_amd.engine import ClipCapEngine, check_ema_decay, check_label_smoothing, ema_decay_at
 from clipcap_amd.model.config import Config, TrainingConfig
 from clipcap_amd.model.gpt2 import GPT2LM
 from clipcap_amd.model.mapper import TransformerMapper, TransformerMapperWindowed
@@ -61,6 +62,13 @@ class ClipCapModel(nn.Module):
     # A plain attribute (not a Config field): set it on the model, or on the namespace handed to train().  evaluate() and score_captions
     # keep reporting the plain likelihood.
     label_smoothing = 0.0
+    # Exponential moving average of the trained parameters, updated inside fused_step's AdamW launch: ema = d * ema + (1 - d) * p after
+    # every applied step, started at the weights of the first averaged step.  ema_decay None: no average.  ema_warmup: d of host step t is
+    # min(ema_decay, (1 + t) / (10 + t)).  Plain attributes like label_smoothing (not Config fields): set them on the model, or on the
+    # namespace handed to train().  ema_weights() / ema_state_dict() read the average.
+    ema_decay = None
+    ema_warmup = False
+    ema_updates = 0      # host count of optimizer steps taken with the average on (skipped fp16 steps included: the device decides those)
 
     def __init__(self, config: Config, language_model: Optional[GPT2LM] = None):
         super().__init__()
@@ -104,14 +112,17 @@ class ClipCapModel(nn.Module):
         return ps + (int(torch.randint(0, 2 ** 48, (1,)).item()) ^ (rank << 50),)
 
     def fused_step(self, batch: Tuple[torch.Tensor, torch.Tensor], lr: float, reducer=None, max_grad_norm: Optional[float] = None,
-                   label_smoothing: Optional[float] = None) -> torch.Tensor:
+                   label_smoothing: Optional[float] = None, ema_decay: Optional[float] = None) -> torch.Tensor:
         """One optimizer step: zero grads -> forward+backward kernel chains -> (all-reduce) -> fused AdamW. Returns the loss.
         ``max_grad_norm``: global gradient-norm clipping on the device (Lightning's gradient_clip_val; inf: only report the norm);
         the norm of this step's gradients is then ``last_grad_norm``.
         ``label_smoothing``: eps of F.cross_entropy(..., label_smoothing=eps) for this step (None: the ``label_smoothing`` attribute);
-        the returned loss is the smoothed one, ``last_nll`` the plain mean NLL."""
+        the returned loss is the smoothed one, ``last_nll`` the plain mean NLL.
+        ``ema_decay``: decay of the weight average for this step (None: the ``ema_decay`` attribute; both None: no average, and the
+        step launches what it always did).  With ``ema_warmup`` the step uses min(decay, (1 + t) / (10 + t)), t = this step's number."""
         tokens, embeds = batch
         eps = check_label_smoothing(self.label_smoothing if label_smoothing is None else label_smoothing)
+        decay = check_ema_decay(getattr(self, "ema_decay", None) if ema_decay is None else ema_decay)
         eng = self.engine
         eng.zero_grad()
         if reducer is not None:
@@ -124,9 +135,56 @@ class ClipCapModel(nn.Module):
         self._opt_step += 1
         # partitioned gradients (ZeRO stage 2): a rank holds the reduced sum of its own slices only, so the squared norms are summed
         partitioned = reducer is not None and reducer.owners is not None
+        ema_kw = {}
+        if decay is not None:
+            ema_kw["ema_decay"] = ema_decay_at(decay, self._opt_step, self.ema_warmup)
+            self.ema_updates += 1
         eng.optimizer_step(lr, self._opt_step, weight_decay=self._weight_decay(), sync_flag=(reducer.reduce_flag if reducer is not None else None),
-                           max_grad_norm=max_grad_norm, sync_norm=(reducer.reduce_flag if partitioned else None))
+                           max_grad_norm=max_grad_norm, sync_norm=(reducer.reduce_flag if partitioned else None), **ema_kw)
         return loss
+
+    # ---- weight average ----
+    def _trained_modules(self):
+        return [self.transformer_mapper] + ([self.language_model] if self._train_lm else [])
+
+    def ema_state_dict(self) -> dict:
+        """``state_dict()`` with the trained arenas' tensors taken from the weight average (the untrained ones as they are): the same
+        keys and shapes, so ``load(..., from_checkpoint=True)`` reads a checkpoint made of it.  A trained arena without an average yet
+        contributes its weights.  With sharded optimizer state this is a COLLECTIVE (every rank calls it) and the averaged tensors are
+        host tensors."""
+        sd = self.state_dict()
+        for prefix, mod in (("transformer_mapper.", self.transformer_mapper), ("language_model.", self.language_model)):
+            a = mod.engine.arena
+            if mod not in self._trained_modules() or a.ema is None:
+                continue
+            for name, view in mod.engine.views(a.full_ema()).items():
+                if prefix + name in sd:
+                    sd[prefix + name] = view.detach().clone()
+            if prefix + "lm_head.weight" in sd:            # tied to wte (gpt2._TiedHead): the same averaged tensor
+                sd[prefix + "lm_head.weight"] = sd[prefix + "transformer.wte.weight"]
+        return sd
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the fp32 masters of the trained arenas hold the weight average, so evaluate(), score_captions and every
+        decoder run on it unchanged; on exit (an exception included) the trained weights are back, bit for bit.  A trained arena without
+        an average keeps its weights.  With sharded optimizer state every rank enters (collecting the average is a collective)."""
+        swapped = []
+        try:
+            for mod in self._trained_modules():
+                a = mod.engine.arena
+                avg = a.ema_on_device()
+                if avg is None:
+                    continue
+                keep = a.w32.clone()
+                swapped.append((a, keep))
+                a.w32.copy_(avg)
+                a.mark_dirty()
+            yield self
+        finally:
+            for a, keep in swapped:
+                a.w32.copy_(keep)
+                a.mark_dirty()
 
     @property
     def last_grad_norm(self) -> Optional[torch.Tensor]:

@@ -22,11 +22,14 @@ def linear_warmup_decay(num_warmup_steps: int, num_training_steps: int) -> Calla
 
 class ArenaAdamW(torch.optim.Optimizer):
     def __init__(self, arena_modules: List, lr: float = 2e-5, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01,
-                 max_grad_norm: Optional[float] = None):
+                 max_grad_norm: Optional[float] = None, ema_decay: Optional[float] = None):
         """``max_grad_norm``: clip the gradients of all arenas together to this global 2-norm before the step, on the device
-        (engine.GradClipper; inf: only measure); the norm is then ``last_grad_norm`` (1-element device tensor)."""
+        (engine.GradClipper; inf: only measure); the norm is then ``last_grad_norm`` (1-element device tensor).
+        ``ema_decay``: d in [0, 1) — every step also updates each arena's weight average (``arena.ema``) inside its AdamW launch."""
+        from clipcap_amd.engine import check_ema_decay
         self.arena_modules = list(arena_modules)
         self.max_grad_norm = max_grad_norm
+        self.ema_decay = check_ema_decay(ema_decay)
         self._clipper = None
         params = [p for m in self.arena_modules for p in m._arena_params.values()]
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
@@ -58,7 +61,8 @@ class ArenaAdamW(torch.optim.Optimizer):
             cl.finish()
             clip = cl.coef
         for m in self.arena_modules:
-            m.engine.arena.adamw_step(g["lr"], self._t, betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"], clip=clip)
+            m.engine.arena.adamw_step(g["lr"], self._t, betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"], clip=clip,
+                                      ema_decay=self.ema_decay)
         return loss
 
     @property

@@ -18,7 +18,7 @@ from clipcap_amd.train.args import add_training_args
 from clipcap_amd.train.callback import CheckpointSaver, resume
 from clipcap_amd.train.dataloader import DevicePrefetcher, get_dataloader
 from clipcap_amd._lib import OP_BF16, OP_FP16, OP_X3
-from clipcap_amd.engine import check_label_smoothing
+from clipcap_amd.engine import check_ema_decay, check_label_smoothing
 from clipcap_amd.train.ddp import GradReducer, ZeroShard, zero_stage
 
 
@@ -76,6 +76,8 @@ def train(args: Namespace, tokenizer=None, language_model=None, step_hook=None) 
             if a.m is not None:
                 torch.distributed.broadcast(a.m, src=0)
                 torch.distributed.broadcast(a.v, src=0)
+            if a.ema is not None:
+                torch.distributed.broadcast(a.ema, src=0)
 
     saver = CheckpointSaver(args.output_folder, args.checkpoint_filename_prefix, save_every_n_epochs=args.checkpoint_save_frequency)
     if rank == 0:
@@ -113,6 +115,15 @@ def train(args: Namespace, tokenizer=None, language_model=None, step_hook=None) 
         model.label_smoothing = check_label_smoothing(smoothing)
     if model.label_smoothing > 0.0 and rank == 0:
         print(f"clipcap_amd: label smoothing {model.label_smoothing:g} in the fused lm_head loss (the logged nll is the plain likelihood)", flush=True)
+    # an exponential moving average of the trained weights, the same way (no CLI flag): args.ema_decay in [0, 1), args.ema_warmup.  The
+    # model's attributes carry it into fused_step, whose AdamW launch updates the average
+    ema_decay = check_ema_decay(getattr(args, "ema_decay", None))
+    if ema_decay is not None:
+        model.ema_decay = ema_decay
+        model.ema_warmup = bool(getattr(args, "ema_warmup", False))
+    if model.ema_decay is not None and rank == 0:
+        print(f"clipcap_amd: ema of the trained weights, decay {model.ema_decay:g}" + (" after warm-up (1 + t) / (10 + t)" if model.ema_warmup else "")
+              + f", updated inside the AdamW step; written to {args.checkpoint_filename_prefix}_final_ema.ckpt", flush=True)
     logger = None
     if args.enable_wandb and rank == 0:
         try:
@@ -126,8 +137,11 @@ def train(args: Namespace, tokenizer=None, language_model=None, step_hook=None) 
         if hasattr(dataset, "close"):
             dataset.close()          # the reader's worker processes (do not leave them to interpreter exit)
     opt = CheckpointSaver.optimizer_state(model) if sharded else None
+    kw = {"optimizer_state": opt} if opt is not None else {}
+    if sharded and CheckpointSaver.has_ema(model):          # collectives, like the moments: every rank takes part, rank 0 writes
+        kw.update(ema_state=CheckpointSaver.ema_state(model), ema_state_dict=model.ema_state_dict())
     if rank == 0:
-        saver.save_final_checkpoint(model, step=step, **({"optimizer_state": opt} if opt is not None else {}))
+        saver.save_final_checkpoint(model, step=step, **kw)
     return 0
 
 
@@ -153,21 +167,29 @@ def _run_epochs(args, model, dataset, device, sched, reducer, saver, sharded, ra
                     logger.log(record, step=step)
         # with sharded optimizer state, collecting the moments is a collective: every rank takes part, rank 0 writes
         opt = CheckpointSaver.optimizer_state(model) if sharded and epoch % saver.save_every_n_epochs == 0 else None
+        kw = {"optimizer_state": opt} if opt is not None else {}
+        if opt is not None and CheckpointSaver.has_ema(model):
+            kw["ema_state"] = CheckpointSaver.ema_state(model)
         if rank == 0:
-            saver.on_epoch_end(model, epoch, step=step, **({"optimizer_state": opt} if opt is not None else {}))
+            saver.on_epoch_end(model, epoch, step=step, **kw)
     return step
 
 
 @torch.no_grad()
-def evaluate(model, dataset_path: str, batch_size: int = 256, max_batches=None, *, tokenizer=None, max_token_length: int = 64) -> dict:
+def evaluate(model, dataset_path: str, batch_size: int = 256, max_batches=None, *, tokenizer=None, max_token_length: int = 64,
+             ema: bool = False) -> dict:
     """Held-out loss of ``model`` over a dataset folder (the layout train() reads): {"loss", "perplexity", "tokens"}.
 
     ``loss`` is the training objective (model.py:94-113: mean cross-entropy over the kept targets, ignore_index = 0, pads -> 0) on data
     the model is not being trained on — token-weighted over the batches, from the forward-only scoring pass (ClipCapEngine.score with
     ignore_zero), so it needs no gradient arenas and no training workspace.  ``perplexity`` = exp(loss); ``tokens`` = kept targets seen.
     ``max_batches``: stop after that many batches.  ``tokenizer`` / ``max_token_length``: as get_dataloader takes them (default: the
-    tokenizer of model.config.language_model)."""
+    tokenizer of model.config.language_model).  ``ema``: evaluate the weight average instead of the last iterate (inside
+    model.ema_weights(); with sharded optimizer state every rank calls it)."""
     import math
+    if ema:
+        with model.ema_weights():
+            return evaluate(model, dataset_path, batch_size, max_batches, tokenizer=tokenizer, max_token_length=max_token_length)
     dataset, _ = get_dataloader(dataset_path, model.config.language_model, batch_size, tokenizer=tokenizer, max_token_length=max_token_length)
     device = model.language_model.engine.arena.device
     total = torch.zeros(2, dtype=torch.float64, device=device)          # [sum of kept log-probs, kept count]

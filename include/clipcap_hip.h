@@ -68,7 +68,8 @@ extern "C" {
  * the lab library exports them, the product library does not.  ADDED since (still 3: no existing entry point changed): cc_lmhead_score,
  * cc_grad_norm_scratch_floats, cc_grad_sqnorm, cc_grad_clip_coef, cc_adamw_step_clip, cc_logits_constrain, cc_beam_group_step,
  * cc_beam_group_ws_bytes, cc_decode_hidden_unit, cc_contrastive_topk, cc_contrastive_select, the decode-attention test hook
- * cc_decode_attention, and the label-smoothed loss cc_lmhead_smooth_scratch_floats, cc_lmhead_ce_fwd_smooth, cc_lmhead_ce_bwd_smooth. */
+ * cc_decode_attention, and the label-smoothed loss cc_lmhead_smooth_scratch_floats, cc_lmhead_ce_fwd_smooth, cc_lmhead_ce_bwd_smooth,
+ * and the weight-averaging optimizer step cc_adamw_step_ema. */
 #define CC_ABI_VERSION 3
 int cc_abi_version(void);
 
@@ -446,6 +447,16 @@ int cc_grad_clip_coef(const float* sumsq, float max_norm, float grad_scale, cons
 int cc_adamw_step_clip(int32_t op_dtype, float* p32, const float* g32, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                        float eps, float weight_decay, int32_t step, float grad_scale, const float* loss_scale, const float* found_inf,
                        const float* clip, uint16_t* w16 /* nullable: no cast */, void* stream);
+/* Exponential moving average of the parameters, updated where they sit in registers: cc_adamw_step_clip (p32, m, v and w16 come out
+ * bit for bit as it leaves them) plus, after an APPLIED step, ema[i] = ema_decay * ema[i] + (1 - ema_decay) * p32[i] over the
+ * parameters the step just wrote — the convex form in fp32, 1 - ema_decay formed in fp32, so ema_decay = 0 gives ema == p32 as numbers
+ * and one update stays within 4 * 2^-24 * max(|ema|, |p32|) of the exact value.  A step skipped on *found_inf leaves ema untouched.
+ * ema: n floats on the device, 16-byte aligned, not overlapping p32; ema NULL / misaligned / overlapping, or ema_decay outside [0, 1)
+ * (NaN included): CC_ERR_ARG before any launch.  n % 4 != 0: CC_ERR_SHAPE; n == 0: no-op.  w16 given in the bf16x3 mode: CC_ERR_ARG.
+ * Costs 4 B read + 4 B written per parameter on top of the step's 16 B + 12 B. */
+int cc_adamw_step_ema(int32_t op_dtype, float* p32, const float* g32, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                      float eps, float weight_decay, int32_t step, float grad_scale, const float* loss_scale, const float* found_inf,
+                      const float* clip /* nullable */, uint16_t* w16 /* nullable */, float* ema, float ema_decay, void* stream);
 
 /* test hook for the dropout of cc_gpt2_shape: keep flags of one mask stream — site 0 embd [B*T*D], 1 attention [B*H*T*T],
  * 2 residual after attn.c_proj [B*T*D], 3 residual after mlp.c_proj [B*T*D]. */
