@@ -1109,6 +1109,27 @@ def constrain_logits(logits: torch.Tensor, *, lpart: Optional[tuple] = None, his
     return logits
 
 
+def guide_logits(cond: torch.Tensor, uncond: torch.Tensor, scale: float, *, out: Optional[torch.Tensor] = None,
+                 skip_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Classifier-free guidance on one step's logits, before the bans and beam_step / sample_step (cc_logits_guide, one launch):
+    out = log_softmax(uncond) + scale * (log_softmax(cond) - log_softmax(uncond)) for fp32 ``cond`` / ``uncond`` (R, V), the logits of the
+    stream that saw the prefix and of the one that did not.  An entry that is -inf in either input is -inf in the result.  ``out`` None:
+    IN PLACE on ``cond``; otherwise an fp32 (R, V) tensor.  Rows with a non-zero ``skip_rows`` entry (uint8 (R,), e.g. has_stopped) are not
+    written.  Views with a row stride are fine for all three (decode logits, the first beam step's lg[::beam]).  Returns the tensor written."""
+    dev = cond.device
+    R, V = cond.shape
+    dst = cond if out is None else out
+    for t in (cond, uncond, dst):
+        assert t.dtype == torch.float32 and t.dim() == 2 and tuple(t.shape) == (R, V) and t.device == dev
+        assert V == 1 or t.stride(1) == 1
+    if skip_rows is not None:
+        assert skip_rows.dtype == torch.uint8 and skip_rows.numel() == R and skip_rows.is_contiguous() and skip_rows.device == dev
+    ld = lambda t: t.stride(0) if R > 1 else max(t.stride(0), V)  # noqa: E731   (a one-row view may report any row stride)
+    check(_lib.lib().cc_logits_guide(_p(cond), ld(cond), _p(uncond), ld(uncond), R, V, float(scale), _p(dst), ld(dst),
+                                    _p(skip_rows) if skip_rows is not None else None, _stream(dev)), "cc_logits_guide")
+    return dst
+
+
 def contrastive_buffers(device, S: int, k: int, D: int, ctx_max: int, entry_length: int):
     """The device state of ONE contrastive-search decode of S captions with k candidates each (never shared between decodes, streams or
     threads), as a namespace: cand_tok int32 (S*k,), cand_prob fp32 (S*k,), cand_h fp32 (S*k, D) — the candidates of the step;

@@ -19,6 +19,19 @@ Not in the reference either: diverse beam search (Vijayakumar et al., 2016) on t
   * ``num_return_sequences`` = n (generate_beam): the n best beams of every prefix instead of the best one.
 With G == 1 the beam decoders launch exactly what they launched without these options.
 
+Not in the reference either: classifier-free guidance at decode time (Kornblith et al., ICCV 2023; Sanchez et al., 2023) on the beam and
+sampling decoders, keyword-only and off by default —
+  * ``guidance_scale`` = g != 1: the language model runs a second time on the same generated tokens behind ``negative_embeds`` instead of
+    the prefix, in a second DecodeSession that follows the first one's ancestry, and every step scores
+    log_softmax(uncond) + g * (log_softmax(cond) - log_softmax(uncond)) (cc_logits_guide, one launch) in place of the logits: g > 1 rewards
+    a token for what the prefix adds to its probability.  The order within a step is forward x 2, guidance, bans, then the step with its
+    temperature, penalties and filters; the step's own softmax renormalises the guided scores.  The beam decoders then read the logits,
+    not the lm_head partials, as diverse beam search does;
+  * ``negative_embeds``: the unconditional context, fp32 (S, Ln, D) or (1, Ln, D) for all prefixes, Ln >= 1.  None: the functions that
+    have a tokenizer take one position, the input embedding of ``tokenizer.bos_token``, and append a text prefix to it as they do to the
+    prefix; the token-level functions need it whenever g != 1.
+With g == 1 a decoder launches exactly what it launched without these options and allocates nothing more.
+
 Contrastive search (Su et al., 2022), the deterministic decoder with a degeneration penalty, lives in inference/contrastive.py
 (generate_contrastive, generate_contrastive_tokens); it takes the same three constraints.
 """
@@ -28,10 +41,11 @@ from typing import Callable, List, Optional, Tuple, Union
 
 import torch
 
+from clipcap_amd import engine
 from clipcap_amd.engine import (DecodeSession, beam_buffers, beam_group_buffers, beam_group_step, beam_step, constrain_logits, embed_tokens,
                                 sample_step)
 from clipcap_amd.inference.utils import (nucleus_distribution, repetition_penalty_apply, sentence_length_penalty_apply,  # noqa: F401
-                                         top_k_top_p_filtering, validate_beam_groups, validate_constraints)
+                                         top_k_top_p_filtering, validate_beam_groups, validate_constraints, validate_guidance)
 
 
 def _persistent_decode_on() -> bool:
@@ -72,11 +86,36 @@ def _bans(V: int, stop_token: int, no_repeat_ngram_size: int, min_length: int, s
     return _Bans(int(no_repeat_ngram_size), int(min_length), int(stop_token), torch.tensor(ids, dtype=torch.int32, device=dev) if ids else None)
 
 
+def _negative_rows(negative_embeds: Optional[torch.Tensor], guidance_scale: float, rows: int, D: int, dev, who: str):
+    """(scale, the unconditional context as fp32 (rows, Ln, D) on ``dev``) of a token-level decoder; (1.0, None) when guidance is off.
+    Validated once, before anything touches the device."""
+    gs = validate_guidance(guidance_scale)
+    if gs == 1.0:
+        return gs, None
+    if negative_embeds is None:
+        raise ValueError(f"{who}: guidance_scale = {gs} needs negative_embeds, the unconditional context (fp32 ({rows}, Ln, {D}) or (1, Ln, {D}))")
+    if negative_embeds.dim() != 3 or negative_embeds.shape[0] not in (1, rows) or negative_embeds.shape[1] < 1 or negative_embeds.shape[2] != D:
+        raise ValueError(f"{who}: negative_embeds must be ({rows}, Ln, {D}) or (1, Ln, {D}) with Ln >= 1, got {tuple(negative_embeds.shape)}")
+    return gs, negative_embeds.to(dev, torch.float32).expand(rows, -1, -1)
+
+
+def _negative_context(model, tokenizer, negative_embeds: Optional[torch.Tensor], text_prefix_tokens, guidance_scale: float):
+    """The unconditional context of a decoder that has a tokenizer: ``negative_embeds``, or one position holding the input embedding of
+    tokenizer.bos_token, with the text prefix appended exactly as it is to the prefix.  None (and nothing computed) when guidance is off."""
+    if validate_guidance(guidance_scale) == 1.0:
+        return None
+    emb = model.language_model.get_input_embeddings()
+    if negative_embeds is None:
+        bos = tokenizer.encode(tokenizer.bos_token)[0]
+        negative_embeds = emb.weight.detach()[int(bos)].view(1, 1, -1)
+    return _with_text_prefix(model, negative_embeds.to(emb.weight.device, torch.float32), text_prefix_tokens)
+
+
 @torch.no_grad()
 def generate_beam_rounds(model, embeds: torch.Tensor, beam_size: int = 5, entry_length: int = 67, temperature: float = 1.0,
                          stop_token: int = 50256, rounds: int = 1, *, no_repeat_ngram_size: int = 0, min_length: int = 0,
-                         suppress_tokens=None, num_beam_groups: int = 1,
-                         diversity_penalty: float = 0.0) -> List[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
+                         suppress_tokens=None, num_beam_groups: int = 1, diversity_penalty: float = 0.0, guidance_scale: float = 1.0,
+                         negative_embeds: Optional[torch.Tensor] = None) -> List[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
     """Token-level beam search for a batch of prefixes, embeds fp32 (S, L, D), as ``rounds`` consecutive generations with LIVE state —
     the reference's ``for _ in range(number_to_generate)`` around its entry_length loop (base.py:79-130): a later round continues the beams
     of the one before (token histories, has_stopped, seq_lengths, the KV cache), its running ``scores`` are the previous round's scores
@@ -86,6 +125,9 @@ def generate_beam_rounds(model, embeds: torch.Tensor, beam_size: int = 5, entry_
     on across rounds like the rest of the state.  Text-prefix tokens are not part of the history: they enter as embeddings.
     ``num_beam_groups`` > 1 with ``diversity_penalty`` > 0 (module docstring): beam rows g * W .. (g + 1) * W - 1, W = beam_size /
     num_beam_groups, of every prefix are beam group g; a step is then the plain decode forward, the bans and cc_beam_group_step.
+    ``guidance_scale`` != 1 with ``negative_embeds`` (module docstring; needed here, there is no tokenizer to build a default from): a second
+    session of the same rows, prefilled with the negative context and fed the same token embeddings, is fanned out and advanced with the
+    first; a step is then the plain decode forward of both, cc_logits_guide (stopped beams skipped), the bans and the update on the logits.
     Returns one (tokens int64 (S, beam, n_r), scores (S, beam) length-normalised, seq_lengths (S, beam)) per round."""
     lm = model.language_model
     g = lm.engine
@@ -97,6 +139,8 @@ def generate_beam_rounds(model, embeds: torch.Tensor, beam_size: int = 5, entry_
     rounds = max(1, int(rounds))
     validate_beam_groups(beam_size, num_beam_groups, diversity_penalty)
     G = int(num_beam_groups)
+    gs, neg = _negative_rows(negative_embeds, guidance_scale, S, D, dev, "generate_beam_rounds")
+    guided = neg is not None
     bans = _bans(V, stop_token, no_repeat_ngram_size, min_length, suppress_tokens, dev)
     # positions are allocated up to n_positions; like the reference (base.py:79-130), a large number_to_generate only fails if generation
     # actually REACHES the position limit — beams normally stop far earlier
@@ -112,7 +156,11 @@ def generate_beam_rounds(model, embeds: torch.Tensor, beam_size: int = 5, entry_
     sess = DecodeSession(g, S, L0 + total)
     logits0 = sess.forward(embeds)                                              # (S, V)
     lg = torch.empty(R, V, dtype=torch.float32, device=dev)
-    lg[::beam_size] = logits0                                                   # row 0 of every beam set
+    if guided:                                                                  # the unconditional stream: its own positions, from 0
+        usess = DecodeSession(g, S, neg.shape[1] + total)
+        engine.guide_logits(logits0, usess.forward(neg), gs, out=lg[::beam_size])   # the S prefill rows, written where the first update reads
+    else:
+        lg[::beam_size] = logits0                                               # row 0 of every beam set
     bufs = beam_buffers(dev, S, beam_size, V) if G == 1 else beam_group_buffers(dev, S, beam_size, G, V)   # this decode's own step outputs + scratch
     if bans is not None:
         bans.apply(lg[::beam_size], 0)                                          # the rows the first update reads; no history yet
@@ -121,10 +169,13 @@ def generate_beam_rounds(model, embeds: torch.Tensor, beam_size: int = 5, entry_
     else:
         next_tok, src = beam_group_step(lg, S, beam_size, G, temperature, diversity_penalty, True, stop_token, scores, seq_lengths, has_stopped, bufs)
     sess = sess.expand((base // beam_size).to(torch.int32), R)
+    if guided:
+        usess = usess.expand((base // beam_size).to(torch.int32), R)
     # token histories (int32, ping-pong), the next input embedding and the cache ancestry are advanced by one launch per step
     tok = [torch.zeros(R, total, dtype=torch.int32, device=dev) for _ in range(2)]
     x = torch.empty(R, 1, D, dtype=torch.float32, device=dev)
     sess.beam_advance(beam_size, next_tok, None, wte, 0, tok[1], tok[0], x)     # step 0: tokens = next_tokens (base.py:94)
+    plain = G > 1 or guided                                                     # the update reads the logits, not the lm_head partials
     n = 1                                                                       # token columns written so far
     out = []
     for r in range(rounds):
@@ -136,18 +187,25 @@ def generate_beam_rounds(model, embeds: torch.Tensor, beam_size: int = 5, entry_
                 break
             if n >= total:
                 raise RuntimeError(f"generation reached n_positions = {g.dims['NPOS']} ({L0}-position prefix + {n} tokens; round {r + 1} of {rounds})")
-            if G == 1:
+            if not plain:
                 logits = sess.forward(x, partials=True, group=beam_size)        # x = wte[next_tokens] (base.py:117)
                 if bans is not None:                                            # a stopped beam's logits are ignored by the update: skipped
                     bans.apply(logits, n, tok[(n - 1) & 1], n, sess.lpart, has_stopped)
                 next_tok, src = beam_step(logits, S, beam_size, temperature, False, stop_token, scores, seq_lengths, has_stopped, bufs, sess.lpart)
-            else:                                                               # beam groups: the update reads the logits, not the partials
+            else:                                                               # beam groups, guidance: the update reads the logits, not the partials
                 logits = sess.forward(x, group=beam_size)
+                if guided:                                                      # the same tokens without the prefix; a stopped beam's logits are ignored
+                    engine.guide_logits(logits, usess.forward(x, group=beam_size), gs, skip_rows=has_stopped)
                 if bans is not None:
                     bans.apply(logits, n, tok[(n - 1) & 1], n, None, has_stopped)
-                next_tok, src = beam_group_step(logits, S, beam_size, G, temperature, diversity_penalty, False, stop_token, scores, seq_lengths,
-                                                has_stopped, bufs)
+                if G == 1:
+                    next_tok, src = beam_step(logits, S, beam_size, temperature, False, stop_token, scores, seq_lengths, has_stopped, bufs, None)
+                else:
+                    next_tok, src = beam_group_step(logits, S, beam_size, G, temperature, diversity_penalty, False, stop_token, scores, seq_lengths,
+                                                    has_stopped, bufs)
             sess.beam_advance(beam_size, next_tok, src, wte, n, tok[(n - 1) & 1], tok[n & 1], x)   # base.py:104-117
+            if guided:                                                          # the same ancestry for the second cache; rewrites the same tokens and x
+                usess.beam_advance(beam_size, next_tok, src, wte, n, tok[(n - 1) & 1], tok[n & 1], x)
             n += 1
         final = scores / seq_lengths                                            # base.py:123
         out.append((tok[(n - 1) & 1][:, :n].to(torch.int64).view(S, beam_size, -1), final.view(S, beam_size).clone(),
@@ -160,13 +218,13 @@ def generate_beam_rounds(model, embeds: torch.Tensor, beam_size: int = 5, entry_
 
 def generate_beam_tokens(model, embeds: torch.Tensor, beam_size: int = 5, entry_length: int = 67, temperature: float = 1.0,
                          stop_token: int = 50256, *, no_repeat_ngram_size: int = 0, min_length: int = 0,
-                         suppress_tokens=None, num_beam_groups: int = 1,
-                         diversity_penalty: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                         suppress_tokens=None, num_beam_groups: int = 1, diversity_penalty: float = 0.0, guidance_scale: float = 1.0,
+                         negative_embeds: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """One generation (the reference's number_to_generate = 1): (tokens int64 (S, beam, n), scores (S, beam) length-normalised,
     seq_lengths (S, beam))."""
     return generate_beam_rounds(model, embeds, beam_size, entry_length, temperature, stop_token, 1, no_repeat_ngram_size=no_repeat_ngram_size,
                                 min_length=min_length, suppress_tokens=suppress_tokens, num_beam_groups=num_beam_groups,
-                                diversity_penalty=diversity_penalty)[0]
+                                diversity_penalty=diversity_penalty, guidance_scale=guidance_scale, negative_embeds=negative_embeds)[0]
 
 
 def best_beams(scores: torch.Tensor, n: int = 1) -> torch.Tensor:
@@ -179,19 +237,23 @@ def best_beams(scores: torch.Tensor, n: int = 1) -> torch.Tensor:
 def generate_beam(model, tokenizer: Callable, embeds: torch.Tensor, number_to_generate: int = 1,
                   text_prefix_tokens: Optional[torch.Tensor] = None, beam_size: int = 5, entry_length: int = 67,
                   temperature: float = 1.0, *, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None,
-                  num_beam_groups: int = 1, diversity_penalty: float = 0.0, num_return_sequences: int = 1) -> List[str]:
+                  num_beam_groups: int = 1, diversity_penalty: float = 0.0, num_return_sequences: int = 1, guidance_scale: float = 1.0,
+                  negative_embeds: Optional[torch.Tensor] = None) -> List[str]:
     """Reference signature (base.py:55-64) plus the keyword-only constraints and diverse-beam-search options (module docstring).  For the reference's batch-1 input: ``number_to_generate`` texts, the best beam after each of
     the consecutive generations (base.py:79-130, see generate_beam_rounds).  A batch of prefixes (S > 1, an extension — the reference is
     batch-1) returns the best caption of every prefix row, round-major when number_to_generate > 1.
-    ``num_return_sequences`` = n > 1: for every prefix row (and round) its n best beams by final score, best first, next to each other."""
+    ``num_return_sequences`` = n > 1: for every prefix row (and round) its n best beams by final score, best first, next to each other.
+    ``guidance_scale`` != 1 (module docstring): ``negative_embeds`` None = the embedding of tokenizer.bos_token; the text prefix follows it."""
     stop = _stop_id(tokenizer)
+    negative_embeds = _negative_context(model, tokenizer, negative_embeds, text_prefix_tokens, guidance_scale)
     embeds = _with_text_prefix(model, embeds, text_prefix_tokens)
     validate_beam_groups(beam_size, num_beam_groups, diversity_penalty, num_return_sequences)
     out = []
     for tokens, scores, lengths in generate_beam_rounds(model, embeds, beam_size, entry_length, temperature, stop, number_to_generate,
                                                         no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length,
                                                         suppress_tokens=suppress_tokens, num_beam_groups=num_beam_groups,
-                                                        diversity_penalty=diversity_penalty):
+                                                        diversity_penalty=diversity_penalty, guidance_scale=guidance_scale,
+                                                        negative_embeds=negative_embeds):
         best = best_beams(scores, int(num_return_sequences)).cpu()
         for s in range(tokens.shape[0]):
             for b in best[s].tolist():
@@ -205,7 +267,8 @@ def sample_tokens(model, embeds: torch.Tensor, entry_length: int = 67, stop_toke
                   top_k: Optional[int] = None, temperature: float = 1.0, repetition_penalty: float = 1.0,
                   generator: Optional[torch.Generator] = None, head_tokens: Optional[torch.Tensor] = None,
                   desired_sentence_length: Optional[int] = None, sentence_length_factor: float = 1.0, no_repeat_ngram_size: int = 0,
-                  min_length: int = 0, suppress_tokens=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                  min_length: int = 0, suppress_tokens=None, guidance_scale: float = 1.0,
+                  negative_embeds: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """KV-cached sampling for a batch of prefixes, every step on the device (cc_decode_fwd + cc_sample_step, no host sync except
     an all-rows-stopped poll every 4th step).  embeds fp32 (R, L, D).  mode 0 = the nucleus rule of generate_nucleus_sampling
     (base.py:165-181), mode 1 = top_k_top_p_filtering + softmax (base.py:245-262).
@@ -216,14 +279,19 @@ def sample_tokens(model, embeds: torch.Tensor, entry_length: int = 67, stop_toke
     (utils.py:40-51) before the softmax, inside cc_sample_step_lp.
     The constraints (module docstring) are applied to the logits before all of that; their history is head_tokens ++ generated, the one
     the repetition penalty uses, and head tokens do not count towards ``min_length``.
+    ``guidance_scale`` != 1 with ``negative_embeds`` (R, Ln, D) or (1, Ln, D) (module docstring; needed here): a second session of R rows is
+    prefilled with the negative context and fed the same token embeddings; every step's logits are replaced by the guided scores
+    (cc_logits_guide) before the bans and the sampling step.
     Returns (tokens int64 (R, n), stop_pos int64 (R,)): stop_pos[r] = index of the first stop token of row r (n if none)."""
     lm = model.language_model
     g = lm.engine
     dev = g.arena.device
     embeds = embeds.to(dev, torch.float32)
     R, L0, D = embeds.shape
+    gs, neg = _negative_rows(negative_embeds, guidance_scale, R, D, dev, "sample_tokens")
     bans = _bans(g.dims["V"], stop_token, no_repeat_ngram_size, min_length, suppress_tokens, dev)
     sess = DecodeSession(g, R, L0 + entry_length)
+    usess = DecodeSession(g, R, neg.shape[1] + entry_length) if neg is not None else None
     H0 = 0 if head_tokens is None else int(head_tokens.shape[-1])
     hist = torch.zeros(R, H0 + entry_length, dtype=torch.int64, device=dev)          # [head | generated]: the penalty's history
     if H0:
@@ -234,6 +302,8 @@ def sample_tokens(model, embeds: torch.Tensor, entry_length: int = 67, stop_toke
     n = 0
     for step in range(entry_length):
         logits = sess.forward(x)                                                     # (R, V) fp32
+        if usess is not None:                                                        # the same tokens behind the negative context
+            engine.guide_logits(logits, usess.forward(neg if step == 0 else x), gs)
         if bans is not None:
             bans.apply(logits, step, hist, H0 + step)
         u = torch.rand(R, device=dev, generator=generator)
@@ -257,20 +327,30 @@ def _rows_for(embeds: torch.Tensor, number_to_generate: int) -> torch.Tensor:
     return embeds.repeat_interleave(max(1, number_to_generate), dim=0) if number_to_generate > 1 else embeds
 
 
+def _negative_rows_for(negative_embeds: Optional[torch.Tensor], number_to_generate: int) -> Optional[torch.Tensor]:
+    """_rows_for for the unconditional context: a context per prefix row is repeated like the prefix rows, a shared one (or None) stays."""
+    return negative_embeds if negative_embeds is None or negative_embeds.shape[0] == 1 else _rows_for(negative_embeds, number_to_generate)
+
+
 def generate_nucleus_sampling(model, tokenizer: Callable, embeds: torch.Tensor, number_to_generate: int = 1,
                               text_prefix_tokens: Optional[torch.Tensor] = None, entry_length: int = 67, top_p: float = 0.8, top_k=None,
                               temperature: float = 1.0, generator: Optional[torch.Generator] = None, rerank: bool = False, *,
-                              no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None) -> List[str]:
+                              no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None, guidance_scale: float = 1.0,
+                              negative_embeds: Optional[torch.Tensor] = None) -> List[str]:
     """base.py:135-201 with a KV cache and the sampling step on the device.  The reference is batch-1 and loops number_to_generate
     times; here every (prefix row, repetition) is one row of a single batched decode.  The returned text of a row includes its
     stop token, as the reference's does (it appends before breaking, base.py:186-195).
     ``rerank`` (not in the reference; off by default): the ``number_to_generate`` texts of every prefix row come back ordered by their
-    length-normalised likelihood under the model, best first (inference/score.py rerank_captions), instead of in sampling order."""
+    length-normalised likelihood under the model, best first (inference/score.py rerank_captions), instead of in sampling order.
+    ``guidance_scale`` != 1 (module docstring): ``negative_embeds`` None = the embedding of tokenizer.bos_token; the text prefix follows it.
+    Guidance shapes what is sampled; ``rerank`` keeps ranking by the UNGUIDED likelihood, the model's own p(caption | prefix)."""
     stop = _stop_id(tokenizer)
+    negative_embeds = _negative_context(model, tokenizer, negative_embeds, text_prefix_tokens, guidance_scale)
     embeds = _with_text_prefix(model, embeds, text_prefix_tokens)
     toks, stop_pos = sample_tokens(model, _rows_for(embeds, number_to_generate), entry_length, stop, mode=0, top_p=top_p, top_k=top_k,
                                    temperature=temperature, generator=generator, no_repeat_ngram_size=no_repeat_ngram_size,
-                                   min_length=min_length, suppress_tokens=suppress_tokens)
+                                   min_length=min_length, suppress_tokens=suppress_tokens, guidance_scale=guidance_scale,
+                                   negative_embeds=_negative_rows_for(negative_embeds, number_to_generate))
     rows = list(range(toks.shape[0]))
     if rerank and number_to_generate > 1:
         rows = _likelihood_order(model, embeds, toks, stop_pos, number_to_generate)
@@ -294,13 +374,15 @@ def generate_no_beam(model, tokenizer: Callable, embeds: torch.Tensor, text_pref
                      top_p: float = 0.9, top_k: float = 0.0, entry_length: int = 67, temperature: float = 1.0,
                      repetition_penalty: float = 1.2, desired_sentence_length: int = 50, sentence_length_factor: float = 1.0,
                      sweep: bool = True, generator: Optional[torch.Generator] = None, *, no_repeat_ngram_size: int = 0, min_length: int = 0,
-                     suppress_tokens=None) -> List[str]:
+                     suppress_tokens=None, guidance_scale: float = 1.0, negative_embeds: Optional[torch.Tensor] = None) -> List[str]:
     """base.py:204-279: the reference's debugging sweep over top_p x temperature (sweep=True reproduces it; sweep=False samples
     once with the given top_p / temperature).  Like the reference, ``repetition_penalty`` is accepted but not applied (its call is
     commented out, base.py:236-239).  The sentence-length penalty (base.py:248-254) is applied as the reference applies it: after the
     filter, history tokens whose VALUE equals the stop token id (utils.py:45 compares values, not ids) are scaled — on the device,
-    inside the sampling step.  The text of a row excludes its stop token (the reference breaks before appending, base.py:261-262)."""
+    inside the sampling step.  The text of a row excludes its stop token (the reference breaks before appending, base.py:261-262).
+    ``guidance_scale`` != 1 (module docstring): ``negative_embeds`` None = the embedding of tokenizer.bos_token; the text prefix follows it."""
     stop = _stop_id(tokenizer)
+    negative_embeds = _negative_context(model, tokenizer, negative_embeds, text_prefix_tokens, guidance_scale)
     embeds = _with_text_prefix(model, embeds, text_prefix_tokens)
     grid = [(p, t) for p in (0.5, 0.55, 0.6, 0.65, 0.7, 0.75, 0.8, 0.85, 0.9, 0.95, 1.0) for t in (0.9, 0.95, 1.0)] if sweep \
         else [(top_p, temperature)]
@@ -310,7 +392,8 @@ def generate_no_beam(model, tokenizer: Callable, embeds: torch.Tensor, text_pref
         toks, stop_pos = sample_tokens(model, embeds, entry_length, stop, mode=1, top_p=p, top_k=int(top_k), temperature=t, generator=generator,
                                        head_tokens=text_prefix_tokens, desired_sentence_length=desired_sentence_length,
                                        sentence_length_factor=sentence_length_factor, no_repeat_ngram_size=no_repeat_ngram_size,
-                                       min_length=min_length, suppress_tokens=suppress_tokens)
+                                       min_length=min_length, suppress_tokens=suppress_tokens, guidance_scale=guidance_scale,
+                                       negative_embeds=negative_embeds)
         toks, stop_pos = toks.cpu(), stop_pos.cpu()
         gens.extend(tokenizer.decode(head + toks[r, :int(stop_pos[r])].tolist()) for r in range(toks.shape[0]))
     return gens

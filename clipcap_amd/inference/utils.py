@@ -99,6 +99,21 @@ def validate_constraints(vocab_size: int, stop_token: int, no_repeat_ngram_size:
     return ids
 
 
+# ---- classifier-free guidance (not in the reference: guidance_scale / negative_embeds of the beam and sampling decoders) ---------------
+
+def validate_guidance(guidance_scale: float = 1.0) -> float:
+    """Checks the guidance scale of the decoders and returns it as a float.  ValueError unless it is a finite number >= 0 (1: no guidance,
+    the decoder as it is without the option; 0: the unconditional stream alone).  Pure: touches no device."""
+    import math
+    try:
+        g = float(guidance_scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"guidance_scale must be a finite number >= 0, got {guidance_scale!r}") from None
+    if isinstance(guidance_scale, bool) or not math.isfinite(g) or g < 0:
+        raise ValueError(f"guidance_scale must be finite and >= 0, got {guidance_scale!r}")
+    return g
+
+
 # ---- diverse beam search (not in the reference: num_beam_groups / diversity_penalty / num_return_sequences of the beam decoders) --------
 
 def validate_beam_groups(beam_size: int, num_beam_groups: int = 1, diversity_penalty: float = 0.0, num_return_sequences: int = 1) -> None:

@@ -69,7 +69,7 @@ extern "C" {
  * cc_grad_norm_scratch_floats, cc_grad_sqnorm, cc_grad_clip_coef, cc_adamw_step_clip, cc_logits_constrain, cc_beam_group_step,
  * cc_beam_group_ws_bytes, cc_decode_hidden_unit, cc_contrastive_topk, cc_contrastive_select, the decode-attention test hook
  * cc_decode_attention, and the label-smoothed loss cc_lmhead_smooth_scratch_floats, cc_lmhead_ce_fwd_smooth, cc_lmhead_ce_bwd_smooth,
- * and the weight-averaging optimizer step cc_adamw_step_ema. */
+ * the weight-averaging optimizer step cc_adamw_step_ema, and the decode-time guidance cc_logits_guide. */
 #define CC_ABI_VERSION 3
 int cc_abi_version(void);
 
@@ -320,6 +320,26 @@ int cc_beam_group_step(int32_t S, int32_t beam, int32_t groups, int32_t V, const
 int cc_logits_constrain(float* logits, int32_t R, int32_t V, int64_t ldl, float* lpart, int32_t npart, const void* history,
                         int32_t hist_elem_bytes, int64_t hist_stride, int32_t hist_len, int32_t no_repeat_ngram, int32_t ban_token,
                         const int32_t* suppress, int32_t n_suppress, const uint8_t* skip_rows, void* stream);
+/* Classifier-free guidance at decode time (since 3, added without a version bump; not in the reference: Kornblith et al., ICCV 2023,
+ * "Guiding image captioning models toward more specific captions"; Sanchez et al., 2023): one step's logits of the conditional stream
+ * cond [R][ld_c] (the language model behind the image prefix) and of the unconditional stream uncond [R][ld_u] (the same tokens without it)
+ * become the guided scores, BEFORE the token bans, the beam update or the sampling step.  Per row r, V real columns, fp32 throughout:
+ *     out[r][i] = scale * (cond[r][i] - lse_c) + (1 - scale) * (uncond[r][i] - lse_u)
+ *   with lse_* = the log-sum-exp of the row's V real columns of that stream (max-subtracted; -inf entries contribute nothing), i.e.
+ *   log_softmax(uncond) + scale * (log_softmax(cond) - log_softmax(uncond)).  scale 1 gives log_softmax(cond), scale 0
+ *   log_softmax(uncond); the step that follows renormalises.
+ *   - An entry that is -inf in cond OR in uncond is -inf in out (a token banned in either stream stays banned; no inf - inf is formed); a
+ *     row whose cond or uncond holds no finite entry is -inf everywhere.  NaN inputs are not supported.
+ *   - skip_rows (nullable, uint8 [R]): rows with a non-zero entry are not written (beam search passes has_stopped).
+ *   - out == cond, or out NULL (ld_o is then ignored), works in place.  Columns [V, ld) of all three buffers are neither read nor written.
+ * One launch, one workgroup per row: a sweep over both rows for the two running (max, sum) pairs, a second sweep (served by L2 / the
+ * Infinity Cache) that writes the combination.  16-byte accesses when cond, uncond and out are 16-byte aligned and the three leading
+ * dimensions are multiples of 4, scalar accesses otherwise; the arithmetic of an element does not depend on which.  Reductions in a fixed
+ * order, no atomics, no scratch: a row's result is bit-identical from run to run and does not depend on R, on the other rows or on their
+ * skip flags.  Leading dimensions in floats.  R == 0: CC_OK, nothing is launched.  CC_ERR_ARG: R < 0, V <= 0, a leading dimension < V,
+ * scale not finite or < 0, cond or uncond NULL with R > 0.  CC_ERR_SHAPE: V > 2^30. */
+int cc_logits_guide(const float* cond, int64_t ld_c, const float* uncond, int64_t ld_u, int32_t R, int32_t V, float scale, float* out,
+                    int64_t ld_o, const uint8_t* skip_rows, void* stream);
 /* Contrastive search (since 3, added without a version bump; not in the reference: Su et al., 2022, "A Contrastive Framework for Neural
  * Text Generation"): at every step the k most probable tokens of a caption are run through the model as k rows of one group, and the
  * token kept is the one with the largest  (1 - alpha) p(c) - alpha max_j cos(h_c, h_j),  h_c = the candidate's final hidden state, h_j =
