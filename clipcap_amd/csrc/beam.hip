@@ -1,6 +1,7 @@
 // Device-side beam-search update of the caption decoders (reference: clipcap/inference/base.py:84-119): from one step's logits to the next
 // tokens, source rows, scores, lengths and stop flags.  fp32 / integer work only, so this unit is built once (Makefile).
 #include "layout.h"
+#include "select.hip.h"
 
 using namespace CC_NS;
 
@@ -11,16 +12,32 @@ namespace {
 //   k_beam_partial  : grid (sample, chunk): top-`beam` of the length-normalised candidate scores inside one slice of the
 //                     flattened beam*V candidate space (thread-local insertion lists + block-wide selection)
 //   k_beam_final    : one block per sample merges the chunk winners, then gathers / updates scores, lengths, stopped flags
-// Ties resolve to the lowest flat index b*V + v.
+// Ties resolve to the lowest flat index b*V + v (cand_better, select.hip.h).
+//
+// Diverse beam search: beam groups with a Hamming penalty (Vijayakumar et al., 2016; not in the reference).  The `beam` rows of a sample
+// are split into G beam groups of W consecutive rows; one step advances the groups one after the other, and a candidate of beam group g
+// whose token v was picked c(v) times AT THIS STEP by the beam groups before it loses penalty * c(v) of its log-probability (before the
+// length normalisation; a stopped beam's token-0 continuation is neither penalised nor counted).  Apart from that a beam group's update
+// is the one above on its own W rows: the same two bodies (beam_partial_body, beam_final_body) with DIV = true.
+//   k_beam_rowstats      : once for all rows
+//   k_beam_group_partial : per beam group, grid (sample, chunk): top-W of a slice of the group's W * V candidates
+//   k_beam_group_final   : per beam group, one block per sample: merges the chunk winners, commits the group's W slots and leaves its
+//                          picks in the workspace for the groups after it
+// The launches are stream-ordered: beam group g + 1 starts after beam group g has written its picks.  The picks of the earlier groups
+// (at most beam - W ids) are loaded into LDS once per block, and a candidate is looked up in them only after the cheap key says it could
+// be kept: the penalty only lowers a value, so the unpenalised key stays an upper bound.
 constexpr int BEAM_MAX = 16;
 constexpr int BEAM_CHUNKS = 16;
-
-__device__ __forceinline__ bool cand_better(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
+constexpr int PICK_NONE = -1;      // a slot whose source beam had stopped: its token 0 is padding, not a pick
 
 template <bool VEC>   // VEC: rows are 16-B aligned (ldl % 4 == 0, aligned base) -> float4 loads
 __global__ __launch_bounds__(512) void k_beam_rowstats(const float* __restrict__ logits, size_t ldl, int V, float inv_temp, float* __restrict__ rs) {
     // one pass: every thread keeps a running (max, sum of exp(x - max)) pair, rescaling the sum when its max moves; pairs are merged
-    // the same way across lanes and waves (the logits matrix, 64 MB at 320 x 50257, is read once instead of twice)
+    // the same way across lanes and waves (the logits matrix, 64 MB at 320 x 50257, is read once instead of twice).
+    // This is SoftmaxPair (select.hip.h) written out, and it stays written out: through the struct, or through free functions on
+    // (m, sum) references, the kernel compiles to 73 / 80 more instructions with branches around expf where these lambdas give
+    // selects (profiles/r19_a_select_refactor.md), and it reads every logit of every three-kernel update.  A change to the -inf guards
+    // or the merge order is made in SoftmaxPair AND here.
     __shared__ float redm[8], reds[8];
     const int row = blockIdx.x, tid = threadIdx.x;
     const float* lg = logits + (size_t)row * ldl;
@@ -60,64 +77,6 @@ __global__ __launch_bounds__(512) void k_beam_rowstats(const float* __restrict__
     }
 }
 
-// ---- the pieces the selection kernels share ----------------------------------------------------------------------------------------
-// One round of block arg-max under cand_better, for blocks of NW full waves: wave arg-max by shuffles, the wave winners meet in LDS
-// (red / redi hold 2 NW entries, double-buffered on k, so a round costs one barrier), every thread merges them.  On return every thread
-// holds the block's best (bv, bi), and thread 0 has recorded it as pick k (no candidate left: -inf, 0x7fffffff).
-template <int NW>
-__device__ __forceinline__ void argmax_round(int k, float& bv, int& bi, float* red, int* redi, float* sel_v, int* sel_i) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (cand_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { red[(k & 1) * NW + wv] = bv; redi[(k & 1) * NW + wv] = bi; }
-    __syncthreads();
-    bv = red[(k & 1) * NW]; bi = redi[(k & 1) * NW];
-#pragma unroll
-    for (int w = 1; w < NW; w++) {
-        const float ov = red[(k & 1) * NW + w];
-        const int oi = redi[(k & 1) * NW + w];
-        if (cand_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    if (threadIdx.x == 0) { sel_v[k] = bi != 0x7fffffff ? bv : -INFINITY; sel_i[k] = bi; }
-}
-
-// The `beam` best of the n (value, flat index) candidates of an LDS list, best first, into sel_v / sel_i: one arg-max round per pick; the
-// winner is retired by its flat index (unique: one owner; visible after the round's closing barrier).  Blocks of NT threads.
-template <int NT>
-__device__ __forceinline__ void pick_from_list(const float* cv, int* ci, int n, int beam, float* red, int* redi, float* sel_v, int* sel_i) {
-    const int tid = threadIdx.x;
-    for (int k = 0; k < beam; k++) {
-        float bv = -INFINITY;
-        int bi = 0x7fffffff;
-        for (int c = tid; c < n; c += NT)
-            if (ci[c] != 0x7fffffff && cand_better(cv[c], ci[c], bv, bi)) { bv = cv[c]; bi = ci[c]; }
-        argmax_round<NT / 64>(k, bv, bi, red, redi, sel_v, sel_i);
-        for (int c = tid; c < n; c += NT)
-            if (ci[c] == bi) ci[c] = 0x7fffffff;
-        __syncthreads();
-    }
-}
-
-// The TB-th largest of the 256 threads' maxima: a lower bound of the block's TB-th best key (equal maxima leave together: the bound only
-// gets lower, which is still valid).  red: 8 floats.
-template <int TB>
-__device__ __forceinline__ float kth_bound(float tmax, float* red) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    float thr = -INFINITY;
-    for (int k = 0; k < TB; k++) {
-        float bv = wave_max(tmax);
-        if (lane == 0) red[(k & 1) * 4 + wv] = bv;
-        __syncthreads();
-        thr = fmaxf(fmaxf(red[(k & 1) * 4], red[(k & 1) * 4 + 1]), fmaxf(red[(k & 1) * 4 + 2], red[(k & 1) * 4 + 3]));
-        if (tmax == thr) tmax = -INFINITY;
-    }
-    return thr;
-}
-
 // What a candidate's value needs of its beam row: the stop flag, max and sum(exp) of the row's logits (over the temperature), log(sum),
 // the beam's score so far and the length the candidate would have (seq_len + 1; a stopped beam keeps its length).  First step: sc = 0,
 // len = 1, nothing stopped.
@@ -127,19 +86,27 @@ struct BeamRow {
 };
 // base.py:96-101: only token 0 continues a stopped beam, at the beam's own average
 __device__ __forceinline__ float beam_stopped(const BeamRow& g, int v, int first) { return v == 0 ? (first ? 0.f : (g.sc + 0.f) / g.len) : -INFINITY; }
+// DIV = true: the Hamming penalty of diverse beam search, c = picks of token v by the earlier beam groups.  c == 0 applies no operation at
+// all, so one beam group is bit-identical to the plain update; DIV = false compiles neither the count nor the penalty.
 // Cheap image of a candidate's value, monotone in the logit: exact for stopped beams, within ~1e-6 of beam_val otherwise
-// (x t - m - log(sum) instead of log(exp(x t - m) / sum)).  TEMP = false: temperature 1, no multiply.
-template <bool TEMP>
-__device__ __forceinline__ float beam_key(const BeamRow& g, int v, float xraw, float inv_temp, int first) {
+// (x t - m - log(sum) instead of log(exp(x t - m) / sum)).
+template <bool DIV>
+__device__ __forceinline__ float beam_key(const BeamRow& g, int v, float xraw, float inv_temp, int first, int c, float penalty) {
     if (g.st) return beam_stopped(g, v, first);
-    const float d = ((TEMP ? xraw * inv_temp : xraw) - g.m) - g.lsum;
+    float d = (xraw * inv_temp - g.m) - g.lsum;
+    if constexpr (DIV) {
+        if (c > 0) d -= penalty * (float)c;
+    }
     return first ? d : (g.sc + d) * (1.0f / g.len);
 }
 // The candidate's value in the reference's arithmetic: softmax().log(), then the length-normalised sum (base.py:99-101)
-template <bool TEMP>
-__device__ __forceinline__ float beam_val(const BeamRow& g, int v, float xraw, float inv_temp, int first) {
+template <bool DIV>
+__device__ __forceinline__ float beam_val(const BeamRow& g, int v, float xraw, float inv_temp, int first, int c, float penalty) {
     if (g.st) return beam_stopped(g, v, first);
-    const float lp = logf(expf((TEMP ? xraw * inv_temp : xraw) - g.m) / g.sum);
+    float lp = logf(expf(xraw * inv_temp - g.m) / g.sum);
+    if constexpr (DIV) {
+        if (c > 0) lp -= penalty * (float)c;
+    }
     return first ? lp : (g.sc + lp) / g.len;
 }
 
@@ -159,40 +126,56 @@ __device__ __forceinline__ void beam_commit(int o, float val, int b, int v, int 
     stopped[o] = (unsigned char)hs;
 }
 
-// TB = compile-time beam width (0: run-time width, lists in scratch memory — the slow fallback for beam > 8).
+__device__ __forceinline__ int picked_before(const int* picks, int n, int v) {
+    int c = 0;
+    for (int i = 0; i < n; i++) c += picks[i] == v ? 1 : 0;
+    return c;
+}
+
+// The slice selection of k_beam_partial (DIV = false) and k_beam_group_partial (DIV = true), for blocks of 256 threads.
+// TW = compile-time width (0: run-time width, dynamically indexed lists — the slow fallback for widths 6, 7 and > 8).  `beam`: rows per
+// sample; row0 = first of the `width` rows selected from (0 and width = beam: the whole sample); picks: int [S][beam], entries [0, row0) of a
+// sample are the earlier beam groups' picks of this step (DIV only: DIV = false has no pick list, no lookup and no penalty operand).
 // Each candidate's exact value needs expf + divide + logf (the reference's softmax().log() arithmetic); almost all of the 250 k
 // candidates lose against the thread's current worst kept value, so a cheap bound (x t - m - log(sum), equal up to ~1e-6) with a
 // 1e-3 margin decides whether the exact value is evaluated at all.
-template <int TB>
-__global__ __launch_bounds__(256) void k_beam_partial(const float* __restrict__ logits, size_t ldl, int beam_rt, int V, float inv_temp, int first,
-                                                      const float* __restrict__ rs, const float* __restrict__ scores,
-                                                      const float* __restrict__ seq_len, const unsigned char* __restrict__ stopped,
-                                                      float* __restrict__ pval, int* __restrict__ pidx) {
+template <int TW, bool DIV>
+__device__ __forceinline__ void beam_partial_body(const float* __restrict__ logits, size_t ldl, int beam, int row0, int width_rt, int V, float inv_temp,
+                                                  float penalty, int first, const float* __restrict__ rs, const float* __restrict__ scores,
+                                                  const float* __restrict__ seq_len, const unsigned char* __restrict__ stopped,
+                                                  const int* __restrict__ picks, float* __restrict__ pval, int* __restrict__ pidx) {
     __shared__ float red[8];
     __shared__ int redi[8];
-    __shared__ float cval[TB > 0 ? 1 : 256 * BEAM_MAX];          // candidate arrays: run-time-width fallback only
-    __shared__ int cidx[TB > 0 ? 1 : 256 * BEAM_MAX];
+    __shared__ float cval[TW > 0 ? 1 : 256 * BEAM_MAX];          // candidate arrays: run-time-width fallback only
+    __shared__ int cidx[TW > 0 ? 1 : 256 * BEAM_MAX];
     __shared__ float sel_v[BEAM_MAX];
     __shared__ int sel_i[BEAM_MAX];
-    constexpr int LB = TB > 0 ? TB : BEAM_MAX;
-    const int beam = TB > 0 ? TB : beam_rt;
+    __shared__ int s_pick[DIV ? BEAM_MAX : 1];                   // DIV only
+    const int width = TW > 0 ? TW : width_rt;
     const int s = blockIdx.x, ch = blockIdx.y, tid = threadIdx.x;
-    const int nrows = first ? 1 : beam;
+    const int nrows = first ? 1 : width;
     const int total = nrows * V;
     const int per = (total + BEAM_CHUNKS - 1) / BEAM_CHUNKS;
     const int lo = ch * per, hi = min(total, lo + per);
-    const float* lg = logits + (size_t)s * beam * ldl;
-    // a chunk (total / 16 candidates) spans at most two beam rows when V >= per; handled generally by walking row segments.
-    // scan(f): f(idx, v, row record, raw logit) for every candidate of the chunk, SU logits fetched per thread before any is looked at
+    const int r0 = s * beam + (first ? 0 : row0);                 // the first step reads row 0 of the sample in every beam group
+    const float* lg = logits + (size_t)r0 * ldl;
+    const int npick = row0;                                       // row0 < beam <= BEAM_MAX
+    if constexpr (DIV) {
+        if (tid < npick) s_pick[tid] = picks[s * beam + tid];
+        __syncthreads();
+    }
+    // a chunk (total / 16 candidates) spans at most two rows when V >= per; handled generally by walking row segments.
+    // scan(f): f(idx, v, row record, raw logit) for every candidate of the chunk (b: row inside the selection, idx = b * V + v), SU logits
+    // fetched per thread before any is looked at
     auto scan = [&](auto&& f) {
         for (int b = lo / V; b < nrows && b * V < hi; b++) {
             const int seg_lo = max(lo, b * V), seg_hi = min(hi, (b + 1) * V);
             BeamRow g;
-            g.st = !first && stopped[s * beam + b];
-            g.m = rs[2 * (s * beam + b)]; g.sum = rs[2 * (s * beam + b) + 1];
+            g.st = !first && stopped[r0 + b];
+            g.m = rs[2 * (r0 + b)]; g.sum = rs[2 * (r0 + b) + 1];
             g.lsum = logf(g.sum);
-            g.sc = first ? 0.f : scores[s * beam + b];
-            g.len = first ? 1.f : (seq_len[s * beam + b] + (g.st ? 0.f : 1.f));
+            g.sc = first ? 0.f : scores[r0 + b];
+            g.len = first ? 1.f : (seq_len[r0 + b] + (g.st ? 0.f : 1.f));
             const float* row = lg + (size_t)b * ldl - (size_t)b * V;      // row[idx] = lg[b * ldl + (idx - b V)]
             constexpr int SU = 8;
             for (int idx0 = seg_lo + tid; idx0 < seg_hi; idx0 += 256 * SU) {
@@ -207,93 +190,126 @@ __global__ __launch_bounds__(256) void k_beam_partial(const float* __restrict__ 
             }
         }
     };
+    auto count = [&](const BeamRow& g, int v) {
+        if constexpr (DIV) return (g.st || npick == 0) ? 0 : picked_before(s_pick, npick, v);
+        else return 0;
+    };
     bool done = false;
-    if constexpr (TB > 0) {
+    if constexpr (TW > 0) {
         // Two passes instead of a sorted list per thread (with per-thread lists some lane of a wave inserts in almost every iteration,
         // so every wave ran the ~100-instruction exact-value + insertion path for all of its candidates):
-        //   1. thread maxima of the cheap key; the TB-th largest thread maximum is a lower bound of the chunk's TB-th best value;
-        //   2. only candidates within 1e-3 of that bound get the exact value and go to a small LDS list (a handful per block);
-        //   3. TB picks from the list (ties -> lowest flat index).
+        //   1. thread maxima of the cheap key; the TW-th largest thread maximum is a lower bound of the chunk's TW-th best value.  DIV: the
+        //      maximum is of the PENALISED key (looked up only when the unpenalised key would raise the maximum), so the bound stays valid;
+        //   2. only candidates within 1e-3 of that bound get the exact value and go to a small LDS list (a handful per block).  DIV: the
+        //      filter is on the unpenalised key, an upper bound of the value;
+        //   3. TW picks from the list (ties -> lowest flat index).
         constexpr int FCAP = 1024;
         __shared__ float fcv[FCAP];
         __shared__ int fci[FCAP];
         __shared__ int fcount;
         float tmax = -INFINITY;
-        scan([&](int, int v, const BeamRow& g, float xraw) { tmax = fmaxf(tmax, beam_key<true>(g, v, xraw, inv_temp, first)); });
+        scan([&](int, int v, const BeamRow& g, float xraw) {
+            float key = beam_key<false>(g, v, xraw, inv_temp, first, 0, 0.f);
+            if constexpr (DIV) {
+                if (key > tmax) {
+                    const int c = count(g, v);
+                    if (c) key = beam_key<true>(g, v, xraw, inv_temp, first, c, penalty);
+                }
+            }
+            tmax = fmaxf(tmax, key);
+        });
         if (tid == 0) fcount = 0;
-        const float thr = kth_bound<TB>(tmax, red);
+        const float thr = kth_bound<TW>(tmax, red);
         scan([&](int idx, int v, const BeamRow& g, float xraw) {
-            const float key = beam_key<true>(g, v, xraw, inv_temp, first);
+            const float key = beam_key<false>(g, v, xraw, inv_temp, first, 0, 0.f);
             if (key > -INFINITY && key + 1e-3f >= thr) {
                 const int pos = atomicAdd(&fcount, 1);
-                if (pos < FCAP) { fcv[pos] = beam_val<true>(g, v, xraw, inv_temp, first); fci[pos] = idx; }
+                if (pos < FCAP) { fcv[pos] = beam_val<DIV>(g, v, xraw, inv_temp, first, count(g, v), penalty); fci[pos] = idx; }
             }
         });
         __syncthreads();
         if (fcount <= FCAP) {
-            pick_from_list<256>(fcv, fci, fcount, TB, red, redi, sel_v, sel_i);
+            pick_from_list<256>(fcv, fci, fcount, TW, red, redi, sel_v, sel_i);
             done = true;
         }
     }
     if (!done) {
-        // sorted insertion list per thread: any width (TB = 0: run-time width), and the overflow path of the list above (e.g. all logits equal)
-        float lv[LB];
-        int li[LB];
-#pragma unroll
-        for (int k = 0; k < LB; k++) { lv[k] = -INFINITY; li[k] = 0x7fffffff; }
-        scan([&](int idx, int v, const BeamRow& g, float xraw) {
-            if (!g.st) {
-                const float worst = TB > 0 ? lv[LB - 1] : lv[beam - 1];
-                if (beam_key<true>(g, v, xraw, inv_temp, first) + 1e-3f < worst) return;
-            }
-            const float val = beam_val<true>(g, v, xraw, inv_temp, first);
-            if constexpr (TB > 0) {
-                if (cand_better(val, idx, lv[LB - 1], li[LB - 1])) {
-                    lv[LB - 1] = val; li[LB - 1] = idx;
-#pragma unroll
-                    for (int k = LB - 1; k > 0; k--) {
-                        if (cand_better(lv[k], li[k], lv[k - 1], li[k - 1])) {
-                            const float tv = lv[k]; lv[k] = lv[k - 1]; lv[k - 1] = tv;
-                            const int ti = li[k]; li[k] = li[k - 1]; li[k - 1] = ti;
-                        }
-                    }
-                }
-            } else {
-                if (cand_better(val, idx, lv[beam - 1], li[beam - 1])) {
-                    int k = beam - 1;
-                    while (k > 0 && cand_better(val, idx, lv[k - 1], li[k - 1])) { lv[k] = lv[k - 1]; li[k] = li[k - 1]; k--; }
-                    lv[k] = val; li[k] = idx;
-                }
-            }
-        });
-        if constexpr (TB > 0) {
+        // sorted insertion list per thread: any width (TW = 0: run-time width), and the overflow path of the list above (e.g. all logits equal)
+        // the exact value of a candidate whose cheap key says it could still beat the list's worst entry (a list with room also takes
+        // candidates at -inf, banned tokens for instance: beam_final_body drops them)
+        auto exact = [&](const BeamRow& g, int v, float xraw, float worst, float& val) {
+            if (!g.st && beam_key<false>(g, v, xraw, inv_temp, first, 0, 0.f) + 1e-3f < worst) return false;
+            val = beam_val<DIV>(g, v, xraw, inv_temp, first, count(g, v), penalty);
+            return true;
+        };
+        if constexpr (TW > 0) {
+            SortedList<TW> l;
+            l.clear();
+            scan([&](int idx, int v, const BeamRow& g, float xraw) {
+                float val;
+                if (exact(g, v, xraw, l.v[TW - 1], val)) l.enter(val, idx);
+            });
             // every thread's list is sorted, so the block's next best is the best list HEAD; the owner pops its list
-            for (int k = 0; k < TB; k++) {
-                float bv = lv[0];
-                int bi = li[0];
-                argmax_round<4>(k, bv, bi, red, redi, sel_v, sel_i);
-                if (li[0] == bi && bi != 0x7fffffff) {              // flat indices are unique: exactly one owner
-#pragma unroll
-                    for (int q = 0; q + 1 < LB; q++) { lv[q] = lv[q + 1]; li[q] = li[q + 1]; }
-                    lv[LB - 1] = -INFINITY; li[LB - 1] = 0x7fffffff;
-                }
+            for (int k = 0; k < TW; k++) {
+                float bv = l.v[0];
+                int bi = l.i[0];
+                block_argmax<4>(k, bv, bi, red, redi);
+                record_pick(k, bv, bi, sel_v, sel_i);
+                l.retire(bi);
             }
             __syncthreads();
         } else {
-            for (int k = 0; k < beam; k++) { cval[tid * beam + k] = lv[k]; cidx[tid * beam + k] = li[k]; }
+            // run-time width: the list is indexed dynamically (two plain arrays, which the compiler keeps in indexed registers), then goes
+            // to LDS for the picks
+            float lv[BEAM_MAX];
+            int li[BEAM_MAX];
+#pragma unroll
+            for (int k = 0; k < BEAM_MAX; k++) { lv[k] = -INFINITY; li[k] = SEL_NONE; }
+            scan([&](int idx, int v, const BeamRow& g, float xraw) {
+                float val;
+                if (exact(g, v, xraw, lv[width - 1], val) && cand_better(val, idx, lv[width - 1], li[width - 1])) {
+                    int k = width - 1;
+                    while (k > 0 && cand_better(val, idx, lv[k - 1], li[k - 1])) { lv[k] = lv[k - 1]; li[k] = li[k - 1]; k--; }
+                    lv[k] = val; li[k] = idx;
+                }
+            });
+            for (int k = 0; k < width; k++) { cval[tid * width + k] = lv[k]; cidx[tid * width + k] = li[k]; }
             __syncthreads();
-            pick_from_list<256>(cval, cidx, 256 * beam, beam, red, redi, sel_v, sel_i);
+            pick_from_list<256>(cval, cidx, 256 * width, width, red, redi, sel_v, sel_i);
         }
     }
-    if (tid < beam) {
-        pval[((size_t)s * BEAM_CHUNKS + ch) * beam + tid] = sel_v[tid];
-        pidx[((size_t)s * BEAM_CHUNKS + ch) * beam + tid] = sel_i[tid];
+    if (tid < width) {
+        pval[((size_t)s * BEAM_CHUNKS + ch) * width + tid] = sel_v[tid];
+        pidx[((size_t)s * BEAM_CHUNKS + ch) * width + tid] = sel_i[tid];
     }
 }
 
-__global__ __launch_bounds__(64) void k_beam_final(int beam, int V, int first, int stop_token, const float* __restrict__ pval,
-                                                   const int* __restrict__ pidx, float* __restrict__ scores, float* __restrict__ seq_len,
-                                                   unsigned char* __restrict__ stopped, int* __restrict__ next_tok, int* __restrict__ src_row) {
+template <int TB>      // TB = compile-time beam width (0: run-time width beam_rt)
+__global__ __launch_bounds__(256) void k_beam_partial(const float* __restrict__ logits, size_t ldl, int beam_rt, int V, float inv_temp, int first,
+                                                      const float* __restrict__ rs, const float* __restrict__ scores,
+                                                      const float* __restrict__ seq_len, const unsigned char* __restrict__ stopped,
+                                                      float* __restrict__ pval, int* __restrict__ pidx) {
+    beam_partial_body<TB, false>(logits, ldl, TB > 0 ? TB : beam_rt, 0, beam_rt, V, inv_temp, 0.f, first, rs, scores, seq_len, stopped, nullptr, pval,
+                                 pidx);
+}
+
+template <int TW>      // TW = compile-time width of a beam group (0: run-time width width_rt)
+__global__ __launch_bounds__(256) void k_beam_group_partial(const float* __restrict__ logits, size_t ldl, int beam, int row0, int width_rt, int V,
+                                                            float inv_temp, float penalty, int first, const float* __restrict__ rs,
+                                                            const float* __restrict__ scores, const float* __restrict__ seq_len,
+                                                            const unsigned char* __restrict__ stopped, const int* __restrict__ picks,
+                                                            float* __restrict__ pval, int* __restrict__ pidx) {
+    beam_partial_body<TW, true>(logits, ldl, beam, row0, width_rt, V, inv_temp, penalty, first, rs, scores, seq_len, stopped, picks, pval, pidx);
+}
+
+// The merge of k_beam_final and k_beam_group_final, for blocks of 64 threads: the `width` best of the chunk winners, then the commit of slots
+// row0 .. row0 + width - 1 of the sample.  src_row = the source row's index inside the SAMPLE (what cc_beam_advance expects; 0 on the
+// first step, which reads row 0).  picks (null: none kept): picks[slot] = the token, or PICK_NONE when the source beam had stopped.
+// Fewer finite candidates than slots (extreme token bans): the empty slots continue row row0 with token 0 at -inf.
+__device__ __forceinline__ void beam_final_body(int beam, int row0, int width, int V, int first, int stop_token, const float* __restrict__ pval,
+                                                const int* __restrict__ pidx, float* __restrict__ scores, float* __restrict__ seq_len,
+                                                unsigned char* __restrict__ stopped, int* __restrict__ next_tok, int* __restrict__ src_row,
+                                                int* __restrict__ picks) {
     __shared__ float red[2];
     __shared__ int redi[2];
     __shared__ float cval[BEAM_CHUNKS * BEAM_MAX];
@@ -301,21 +317,47 @@ __global__ __launch_bounds__(64) void k_beam_final(int beam, int V, int first, i
     __shared__ float sel_v[BEAM_MAX];
     __shared__ int sel_i[BEAM_MAX];
     const int s = blockIdx.x, tid = threadIdx.x;
-    const int ncand = BEAM_CHUNKS * beam;
-    for (int c = tid; c < ncand; c += 64) { cval[c] = pval[(size_t)s * ncand + c]; cidx[c] = pidx[(size_t)s * ncand + c]; }
+    const int ncand = BEAM_CHUNKS * width;
+    // A chunk winner at -inf (a banned token, a stopped beam's tokens other than 0) is no candidate.  The compare is not redundant: the
+    // insertion lists of beam_partial_body (run-time width, list overflow) take -inf candidates with their real flat index while they have
+    // room, the two-pass path drops them in pass 2, and this is what makes all three agree when a sample has fewer finite candidates than
+    // slots.  Both loads come before the select, so the loop is two plain loads and a conditional move.
+    for (int c = tid; c < ncand; c += 64) {
+        const float val = pval[(size_t)s * ncand + c];
+        const int idx = pidx[(size_t)s * ncand + c];
+        cval[c] = val;
+        cidx[c] = val > -INFINITY ? idx : SEL_NONE;
+    }
     __syncthreads();
-    pick_from_list<64>(cval, cidx, ncand, beam, red, redi, sel_v, sel_i);
+    pick_from_list<64>(cval, cidx, ncand, width, red, redi, sel_v, sel_i);
     // the source beams' state goes to registers before the barrier, the slots are written after it
-    const int idx = tid < beam ? sel_i[tid] : 0;
-    const int b = idx / V, v = idx % V;
+    const int idx = (tid < width && sel_i[tid] != SEL_NONE) ? sel_i[tid] : 0;
+    const int b = first ? 0 : row0 + idx / V, v = idx % V;
     int st = 0;
     float len = 1.f;
-    if (tid < beam && !first) {
+    if (tid < width && !first) {
         st = stopped[s * beam + b];
         len = seq_len[s * beam + b] + (st ? 0.f : 1.f);
     }
     __syncthreads();
-    if (tid < beam) beam_commit(s * beam + tid, sel_v[tid], b, v, first, stop_token, len, st, scores, seq_len, stopped, next_tok, src_row);
+    if (tid < width) {
+        const int o = s * beam + row0 + tid;
+        beam_commit(o, sel_v[tid], b, v, first, stop_token, len, st, scores, seq_len, stopped, next_tok, src_row);
+        if (picks) picks[o] = st ? PICK_NONE : v;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_beam_final(int beam, int V, int first, int stop_token, const float* __restrict__ pval,
+                                                   const int* __restrict__ pidx, float* __restrict__ scores, float* __restrict__ seq_len,
+                                                   unsigned char* __restrict__ stopped, int* __restrict__ next_tok, int* __restrict__ src_row) {
+    beam_final_body(beam, 0, beam, V, first, stop_token, pval, pidx, scores, seq_len, stopped, next_tok, src_row, nullptr);
+}
+
+__global__ __launch_bounds__(64) void k_beam_group_final(int beam, int row0, int width, int V, int first, int stop_token, const float* __restrict__ pval,
+                                                         const int* __restrict__ pidx, float* __restrict__ scores, float* __restrict__ seq_len,
+                                                         unsigned char* __restrict__ stopped, int* __restrict__ next_tok, int* __restrict__ src_row,
+                                                         int* __restrict__ picks) {
+    beam_final_body(beam, row0, width, V, first, stop_token, pval, pidx, scores, seq_len, stopped, next_tok, src_row, picks);
 }
 
 // ---- beam step in ONE kernel, fed by the lm_head epilogue's partials (gemm.hip.h EpiLogits) ----------------------------------
@@ -325,7 +367,7 @@ __global__ __launch_bounds__(64) void k_beam_final(int beam, int V, int first, i
 // (softmax().log() as the reference writes it), same tie rule (lowest flat index) and same state update as the three-kernel path,
 // which stays as the fallback for temperature != 1, run-time beam widths and candidate-list overflow (e.g. all logits equal).
 // This is the product's kernel (all but the first steps of a decode batch), and its compiled code is held fixed: routed through the
-// shared pieces above (argmax_round, pick_from_list, kth_bound, BeamRow / beam_key / beam_val, beam_commit), each tried alone, every
+// shared pieces (select.hip.h block_argmax + record_pick, pick_from_list, kth_bound; BeamRow / beam_key / beam_val, beam_commit), each tried alone, every
 // instantiation compiles differently (profiles/r12_a_beam_refactor.md), so it keeps these five idioms written out.  A change to the tie
 // rule, the stopped-beam rule or the length normalisation is made in the shared pieces AND here.
 template <int TB, int PER>      // PER: (row, block) partials per thread = ceil(TB * ceil(V / 64) / 256) at most (checked by the host)
@@ -549,217 +591,61 @@ __global__ __launch_bounds__(256) void k_beam_fused(const float* __restrict__ lo
     }
 }
 
-// ---- diverse beam search: beam groups with a Hamming penalty (Vijayakumar et al., 2016; not in the reference) -------------------------
-// The `beam` rows of a sample are split into G beam groups of W consecutive rows; one step advances the groups one after the other, and a
-// candidate of beam group g whose token v was picked c(v) times AT THIS STEP by the beam groups before it loses penalty * c(v) of its
-// log-probability (before the length normalisation; a stopped beam's token-0 continuation is neither penalised nor counted).  Apart from
-// that a beam group's update is the one above on its own W rows: same arithmetic, tie rule and commit.
-//   k_beam_rowstats      : once for all rows, as above
-//   k_beam_group_partial : per beam group, grid (sample, chunk): top-W of a slice of the group's W * V candidates (k_beam_partial's two
-//                          passes and its insertion-list overflow path, with the row offset and the picks of the earlier groups)
-//   k_beam_group_final   : per beam group, one block per sample: merges the chunk winners, commits the group's W slots and leaves its
-//                          picks in the workspace for the groups after it
-// The launches are stream-ordered: beam group g + 1 starts after beam group g has written its picks.  The picks of the earlier groups
-// (at most beam - W ids) are loaded into LDS once per block, and a candidate is looked up in them only after the cheap key says it could
-// be kept: the penalty only lowers a value, so the unpenalised key stays an upper bound.
-constexpr int PICK_NONE = -1;      // a slot whose source beam had stopped: its token 0 is padding, not a pick
-
-__device__ __forceinline__ int picked_before(const int* picks, int n, int v) {
-    int c = 0;
-    for (int i = 0; i < n; i++) c += picks[i] == v ? 1 : 0;
-    return c;
+// ---- host side of the three-kernel path ----------------------------------------------------------------------------------------------
+// Workspace: row statistics [S * beam][2] | chunk winners of ONE selection of `width` rows (values, then flat indices) | beam groups only:
+// this step's picks [S * beam].  The plain update selects from all `beam` rows at once and keeps no picks (picks = null).
+struct BeamWs {
+    float *rs, *pval;
+    int *pidx, *picks;
+};
+BeamWs beam_ws(void* ws, int S, int beam, int width, bool picks) {
+    BeamWs w;
+    w.rs = static_cast<float*>(ws);
+    w.pval = w.rs + (size_t)S * beam * 2;
+    w.pidx = reinterpret_cast<int*>(w.pval + (size_t)S * BEAM_CHUNKS * width);
+    w.picks = picks ? w.pidx + (size_t)S * BEAM_CHUNKS * width : nullptr;
+    return w;
 }
-// beam_val with the Hamming penalty: c = picks of token v by the earlier beam groups.  c == 0 applies no operation at all: one beam group
-// is bit-identical to beam_val.
-template <bool TEMP>
-__device__ __forceinline__ float beam_val_div(const BeamRow& g, int v, float xraw, float inv_temp, int first, int c, float penalty) {
-    if (g.st) return beam_stopped(g, v, first);
-    float lp = logf(expf((TEMP ? xraw * inv_temp : xraw) - g.m) / g.sum);
-    if (c > 0) lp -= penalty * (float)c;
-    return first ? lp : (g.sc + lp) / g.len;
-}
-// the same for the cheap key (an image of beam_val_div within ~1e-6, as beam_key is of beam_val)
-template <bool TEMP>
-__device__ __forceinline__ float beam_key_div(const BeamRow& g, int v, float xraw, float inv_temp, int first, int c, float penalty) {
-    if (g.st) return beam_stopped(g, v, first);
-    float d = ((TEMP ? xraw * inv_temp : xraw) - g.m) - g.lsum;
-    if (c > 0) d -= penalty * (float)c;
-    return first ? d : (g.sc + d) * (1.0f / g.len);
+int64_t beam_ws_bytes(int S, int beam, int width, bool picks) {
+    return (int64_t)S * beam * 2 * sizeof(float) + (int64_t)S * BEAM_CHUNKS * width * (sizeof(float) + sizeof(int)) +
+           (picks ? (int64_t)S * beam * sizeof(int) : 0) + 512;
 }
 
-// TW = compile-time width of a beam group (0: run-time width).  `beam`: rows per sample; row0 = first row of this beam group inside the
-// sample; picks: int [S][beam], entries [0, row0) of a sample are the earlier groups' picks of this step.
-template <int TW>
-__global__ __launch_bounds__(256) void k_beam_group_partial(const float* __restrict__ logits, size_t ldl, int beam, int row0, int width_rt, int V,
-                                                            float inv_temp, float penalty, int first, const float* __restrict__ rs,
-                                                            const float* __restrict__ scores, const float* __restrict__ seq_len,
-                                                            const unsigned char* __restrict__ stopped, const int* __restrict__ picks,
-                                                            float* __restrict__ pval, int* __restrict__ pidx) {
-    __shared__ float red[8];
-    __shared__ int redi[8];
-    __shared__ float cval[TW > 0 ? 1 : 256 * BEAM_MAX];          // candidate arrays: run-time-width fallback only
-    __shared__ int cidx[TW > 0 ? 1 : 256 * BEAM_MAX];
-    __shared__ float sel_v[BEAM_MAX];
-    __shared__ int sel_i[BEAM_MAX];
-    __shared__ int s_pick[BEAM_MAX];
-    constexpr int LB = TW > 0 ? TW : BEAM_MAX;
-    const int width = TW > 0 ? TW : width_rt;
-    const int s = blockIdx.x, ch = blockIdx.y, tid = threadIdx.x;
-    const int nrows = first ? 1 : width;
-    const int total = nrows * V;
-    const int per = (total + BEAM_CHUNKS - 1) / BEAM_CHUNKS;
-    const int lo = ch * per, hi = min(total, lo + per);
-    const int r0 = s * beam + (first ? 0 : row0);                 // the first step reads row 0 of the sample in every beam group
-    const float* lg = logits + (size_t)r0 * ldl;
-    const int npick = row0;                                       // row0 < beam <= BEAM_MAX
-    if (tid < npick) s_pick[tid] = picks[s * beam + tid];
-    __syncthreads();
-    // scan(f): as in k_beam_partial, over the beam group's rows (b: row inside the group, idx = b * V + v)
-    auto scan = [&](auto&& f) {
-        for (int b = lo / V; b < nrows && b * V < hi; b++) {
-            const int seg_lo = max(lo, b * V), seg_hi = min(hi, (b + 1) * V);
-            BeamRow g;
-            g.st = !first && stopped[r0 + b];
-            g.m = rs[2 * (r0 + b)]; g.sum = rs[2 * (r0 + b) + 1];
-            g.lsum = logf(g.sum);
-            g.sc = first ? 0.f : scores[r0 + b];
-            g.len = first ? 1.f : (seq_len[r0 + b] + (g.st ? 0.f : 1.f));
-            const float* row = lg + (size_t)b * ldl - (size_t)b * V;      // row[idx] = lg[b * ldl + (idx - b V)]
-            constexpr int SU = 8;
-            for (int idx0 = seg_lo + tid; idx0 < seg_hi; idx0 += 256 * SU) {
-                float xs[SU];
-#pragma unroll
-                for (int u = 0; u < SU; u++) xs[u] = g.st ? 0.f : row[min(idx0 + u * 256, seg_hi - 1)];
-#pragma unroll
-                for (int u = 0; u < SU; u++) {
-                    const int idx = idx0 + u * 256;
-                    if (idx < seg_hi) f(idx, idx - b * V, g, xs[u]);
-                }
-            }
-        }
-    };
-    auto count = [&](const BeamRow& g, int v) { return (g.st || npick == 0) ? 0 : picked_before(s_pick, npick, v); };
-    bool done = false;
-    if constexpr (TW > 0) {
-        // k_beam_partial's two passes.  Pass 1 keeps the thread maximum of the PENALISED key (looked up only when the unpenalised key would
-        // raise the maximum), so its TW-th largest stays a lower bound of the chunk's TW-th best value; pass 2 filters on the unpenalised key,
-        // an upper bound of the value.
-        constexpr int FCAP = 1024;
-        __shared__ float fcv[FCAP];
-        __shared__ int fci[FCAP];
-        __shared__ int fcount;
-        float tmax = -INFINITY;
-        scan([&](int, int v, const BeamRow& g, float xraw) {
-            const float key = beam_key<true>(g, v, xraw, inv_temp, first);
-            if (key > tmax) {
-                const int c = count(g, v);
-                tmax = fmaxf(tmax, c ? beam_key_div<true>(g, v, xraw, inv_temp, first, c, penalty) : key);
-            }
-        });
-        if (tid == 0) fcount = 0;
-        const float thr = kth_bound<TW>(tmax, red);
-        scan([&](int idx, int v, const BeamRow& g, float xraw) {
-            const float key = beam_key<true>(g, v, xraw, inv_temp, first);
-            if (key > -INFINITY && key + 1e-3f >= thr) {
-                const int pos = atomicAdd(&fcount, 1);
-                if (pos < FCAP) { fcv[pos] = beam_val_div<true>(g, v, xraw, inv_temp, first, count(g, v), penalty); fci[pos] = idx; }
-            }
-        });
-        __syncthreads();
-        if (fcount <= FCAP) {
-            pick_from_list<256>(fcv, fci, fcount, TW, red, redi, sel_v, sel_i);
-            done = true;
-        }
-    }
-    if (!done) {
-        // sorted insertion list per thread: any width (TW = 0: run-time width), and the overflow path of the list above (e.g. all logits equal)
-        float lv[LB];
-        int li[LB];
-#pragma unroll
-        for (int k = 0; k < LB; k++) { lv[k] = -INFINITY; li[k] = 0x7fffffff; }
-        scan([&](int idx, int v, const BeamRow& g, float xraw) {
-            if (!g.st) {
-                const float worst = TW > 0 ? lv[LB - 1] : lv[width - 1];
-                if (beam_key<true>(g, v, xraw, inv_temp, first) + 1e-3f < worst) return;
-            }
-            const float val = beam_val_div<true>(g, v, xraw, inv_temp, first, count(g, v), penalty);
-            if constexpr (TW > 0) {
-                if (cand_better(val, idx, lv[LB - 1], li[LB - 1])) {
-                    lv[LB - 1] = val; li[LB - 1] = idx;
-#pragma unroll
-                    for (int k = LB - 1; k > 0; k--) {
-                        if (cand_better(lv[k], li[k], lv[k - 1], li[k - 1])) {
-                            const float tv = lv[k]; lv[k] = lv[k - 1]; lv[k - 1] = tv;
-                            const int ti = li[k]; li[k] = li[k - 1]; li[k - 1] = ti;
-                        }
-                    }
-                }
-            } else {
-                if (cand_better(val, idx, lv[width - 1], li[width - 1])) {
-                    int k = width - 1;
-                    while (k > 0 && cand_better(val, idx, lv[k - 1], li[k - 1])) { lv[k] = lv[k - 1]; li[k] = li[k - 1]; k--; }
-                    lv[k] = val; li[k] = idx;
-                }
-            }
-        });
-        if constexpr (TW > 0) {
-            // every thread's list is sorted, so the block's next best is the best list HEAD; the owner pops its list
-            for (int k = 0; k < TW; k++) {
-                float bv = lv[0];
-                int bi = li[0];
-                argmax_round<4>(k, bv, bi, red, redi, sel_v, sel_i);
-                if (li[0] == bi && bi != 0x7fffffff) {              // flat indices are unique: exactly one owner
-#pragma unroll
-                    for (int q = 0; q + 1 < LB; q++) { lv[q] = lv[q + 1]; li[q] = li[q + 1]; }
-                    lv[LB - 1] = -INFINITY; li[LB - 1] = 0x7fffffff;
-                }
-            }
-            __syncthreads();
-        } else {
-            for (int k = 0; k < width; k++) { cval[tid * width + k] = lv[k]; cidx[tid * width + k] = li[k]; }
-            __syncthreads();
-            pick_from_list<256>(cval, cidx, 256 * width, width, red, redi, sel_v, sel_i);
-        }
-    }
-    if (tid < width) {
-        pval[((size_t)s * BEAM_CHUNKS + ch) * width + tid] = sel_v[tid];
-        pidx[((size_t)s * BEAM_CHUNKS + ch) * width + tid] = sel_i[tid];
-    }
+void launch_rowstats(hipStream_t st, const float* logits, int64_t ldl, int rows, int V, float inv_temp, float* rs) {
+    if ((ldl & 3) || ((uintptr_t)logits & 15))
+        hipLaunchKernelGGL(k_beam_rowstats<false>, dim3(rows), dim3(512), 0, st, logits, (size_t)ldl, V, inv_temp, rs);
+    else
+        hipLaunchKernelGGL(k_beam_rowstats<true>, dim3(rows), dim3(512), 0, st, logits, (size_t)ldl, V, inv_temp, rs);
 }
 
-// k_beam_final for one beam group: slots and source rows are row0 .. row0 + width - 1 of the sample; src_row = the source row's index
-// inside the SAMPLE (what cc_beam_advance expects; 0 on the first step, which reads row 0), picks[slot] = the token, or PICK_NONE when
-// the source beam had stopped.
-__global__ __launch_bounds__(64) void k_beam_group_final(int beam, int row0, int width, int V, int first, int stop_token, const float* __restrict__ pval,
-                                                         const int* __restrict__ pidx, float* __restrict__ scores, float* __restrict__ seq_len,
-                                                         unsigned char* __restrict__ stopped, int* __restrict__ next_tok, int* __restrict__ src_row,
-                                                         int* __restrict__ picks) {
-    __shared__ float red[2];
-    __shared__ int redi[2];
-    __shared__ float cval[BEAM_CHUNKS * BEAM_MAX];
-    __shared__ int cidx[BEAM_CHUNKS * BEAM_MAX];
-    __shared__ float sel_v[BEAM_MAX];
-    __shared__ int sel_i[BEAM_MAX];
-    const int s = blockIdx.x, tid = threadIdx.x;
-    const int ncand = BEAM_CHUNKS * width;
-    for (int c = tid; c < ncand; c += 64) { cval[c] = pval[(size_t)s * ncand + c]; cidx[c] = pidx[(size_t)s * ncand + c]; }
-    __syncthreads();
-    pick_from_list<64>(cval, cidx, ncand, width, red, redi, sel_v, sel_i);
-    // the source beams' state goes to registers before the barrier, the slots are written after it
-    const int idx = (tid < width && sel_i[tid] != 0x7fffffff) ? sel_i[tid] : 0;      // fewer than `width` candidates: row 0, token 0 at -inf
-    const int b = first ? 0 : row0 + idx / V, v = idx % V;
-    int st = 0;
-    float len = 1.f;
-    if (tid < width && !first) {
-        st = stopped[s * beam + b];
-        len = seq_len[s * beam + b] + (st ? 0.f : 1.f);
+// partial + final for rows [row0, row0 + width) of every sample.  w.picks null: the plain kernels (row0 = 0, width = beam); else a beam group.
+void launch_select(hipStream_t st, int S, int beam, int row0, int width, int V, const float* logits, int64_t ldl, float inv_temp, float penalty, int first,
+                   int stop_token, const BeamWs& w, float* scores, float* seq_lengths, uint8_t* has_stopped, int32_t* next_tokens, int32_t* src_rows) {
+#define BEAM_PARTIAL(TW)                                                                                                                              \
+    do {                                                                                                                                              \
+        if (w.picks)                                                                                                                                  \
+            hipLaunchKernelGGL(k_beam_group_partial<TW>, dim3(S, BEAM_CHUNKS), dim3(256), 0, st, logits, (size_t)ldl, beam, row0, width, V, inv_temp, \
+                               penalty, first, w.rs, scores, seq_lengths, has_stopped, w.picks, w.pval, w.pidx);                                     \
+        else                                                                                                                                          \
+            hipLaunchKernelGGL(k_beam_partial<TW>, dim3(S, BEAM_CHUNKS), dim3(256), 0, st, logits, (size_t)ldl, beam, V, inv_temp, first, w.rs,      \
+                               scores, seq_lengths, has_stopped, w.pval, w.pidx);                                                                    \
+    } while (0)
+    switch (width) {
+        case 1: BEAM_PARTIAL(1); break;
+        case 2: BEAM_PARTIAL(2); break;
+        case 3: BEAM_PARTIAL(3); break;
+        case 4: BEAM_PARTIAL(4); break;
+        case 5: BEAM_PARTIAL(5); break;
+        case 8: BEAM_PARTIAL(8); break;
+        default: BEAM_PARTIAL(0); break;
     }
-    __syncthreads();
-    if (tid < width) {
-        const int o = s * beam + row0 + tid;
-        beam_commit(o, sel_v[tid], b, v, first, stop_token, len, st, scores, seq_len, stopped, next_tok, src_row);
-        picks[o] = st ? PICK_NONE : v;
-    }
+#undef BEAM_PARTIAL
+    if (w.picks)
+        hipLaunchKernelGGL(k_beam_group_final, dim3(S), dim3(64), 0, st, beam, row0, width, V, first, stop_token, w.pval, w.pidx, scores, seq_lengths,
+                           has_stopped, next_tokens, src_rows, w.picks);
+    else
+        hipLaunchKernelGGL(k_beam_final, dim3(S), dim3(64), 0, st, beam, V, first, stop_token, w.pval, w.pidx, scores, seq_lengths, has_stopped,
+                           next_tokens, src_rows);
 }
 
 }  // namespace
@@ -769,7 +655,7 @@ extern "C" {
 int64_t CC_API(cc_beam_ws_bytes)(int32_t S, int32_t beam, int32_t V) {
     (void)V;
     if (S <= 0 || beam <= 0 || beam > BEAM_MAX) return CC_ERR_SHAPE;
-    return (int64_t)S * beam * 2 * sizeof(float) + (int64_t)S * BEAM_CHUNKS * beam * (sizeof(float) + sizeof(int)) + 512;
+    return beam_ws_bytes(S, beam, beam, false);
 }
 
 int CC_API(cc_beam_step_p)(int32_t S, int32_t beam, int32_t V, const float* logits, int64_t ldl, const float* lpart, int32_t npart, float temperature,
@@ -807,36 +693,17 @@ int CC_API(cc_beam_step_p)(int32_t S, int32_t beam, int32_t V, const float* logi
         return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
     }
     const float inv_temp = 1.0f / (temperature > 0.f ? temperature : 1.0f);   // base.py:83
-    float* rs = static_cast<float*>(ws);
-    float* pval = rs + (size_t)S * beam * 2;
-    int* pidx = reinterpret_cast<int*>(pval + (size_t)S * BEAM_CHUNKS * beam);
+    const BeamWs w = beam_ws(ws, S, beam, beam, false);
     // step 0 reads only row 0 of every sample's block of `beam` rows, but computing all rows' statistics is harmless and uniform
-    if ((ldl & 3) || ((uintptr_t)logits & 15))
-        hipLaunchKernelGGL(k_beam_rowstats<false>, dim3(S * beam), dim3(512), 0, st, logits, (size_t)ldl, V, inv_temp, rs);
-    else
-        hipLaunchKernelGGL(k_beam_rowstats<true>, dim3(S * beam), dim3(512), 0, st, logits, (size_t)ldl, V, inv_temp, rs);
-#define BEAM_PARTIAL(TB) hipLaunchKernelGGL(k_beam_partial<TB>, dim3(S, BEAM_CHUNKS), dim3(256), 0, st, logits, (size_t)ldl, beam, V, inv_temp, first, rs, scores, seq_lengths, has_stopped, pval, pidx)
-    switch (beam) {
-        case 1: BEAM_PARTIAL(1); break;
-        case 2: BEAM_PARTIAL(2); break;
-        case 3: BEAM_PARTIAL(3); break;
-        case 4: BEAM_PARTIAL(4); break;
-        case 5: BEAM_PARTIAL(5); break;
-        case 8: BEAM_PARTIAL(8); break;
-        default: BEAM_PARTIAL(0); break;
-    }
-#undef BEAM_PARTIAL
-    hipLaunchKernelGGL(k_beam_final, dim3(S), dim3(64), 0, st, beam, V, first, stop_token, pval, pidx, scores, seq_lengths, has_stopped, next_tokens,
-                       src_rows);
+    launch_rowstats(st, logits, ldl, S * beam, V, inv_temp, w.rs);
+    launch_select(st, S, beam, 0, beam, V, logits, ldl, inv_temp, 0.f, first, stop_token, w, scores, seq_lengths, has_stopped, next_tokens, src_rows);
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 
-// workspace of cc_beam_group_step: row statistics | chunk winners of ONE beam group (values, flat indices) | this step's picks
 int64_t CC_API(cc_beam_group_ws_bytes)(int32_t S, int32_t beam, int32_t groups, int32_t V) {
     (void)V;
     if (S <= 0 || beam <= 0 || beam > BEAM_MAX || groups < 1 || beam % groups) return CC_ERR_SHAPE;
-    const int width = beam / groups;
-    return (int64_t)S * beam * 2 * sizeof(float) + (int64_t)S * BEAM_CHUNKS * width * (sizeof(float) + sizeof(int)) + (int64_t)S * beam * sizeof(int) + 512;
+    return beam_ws_bytes(S, beam, beam / groups, true);
 }
 
 int CC_API(cc_beam_group_step)(int32_t S, int32_t beam, int32_t groups, int32_t V, const float* logits, int64_t ldl, float temperature,
@@ -849,30 +716,11 @@ int CC_API(cc_beam_group_step)(int32_t S, int32_t beam, int32_t groups, int32_t 
     hipStream_t st = S_(stream);
     const int width = beam / groups;
     const float inv_temp = 1.0f / (temperature > 0.f ? temperature : 1.0f);   // base.py:83
-    float* rs = static_cast<float*>(ws);
-    float* pval = rs + (size_t)S * beam * 2;
-    int* pidx = reinterpret_cast<int*>(pval + (size_t)S * BEAM_CHUNKS * width);
-    int* picks = pidx + (size_t)S * BEAM_CHUNKS * width;
-    if ((ldl & 3) || ((uintptr_t)logits & 15))
-        hipLaunchKernelGGL(k_beam_rowstats<false>, dim3(S * beam), dim3(512), 0, st, logits, (size_t)ldl, V, inv_temp, rs);
-    else
-        hipLaunchKernelGGL(k_beam_rowstats<true>, dim3(S * beam), dim3(512), 0, st, logits, (size_t)ldl, V, inv_temp, rs);
-    for (int g = 0; g < groups; g++) {
-        const int row0 = g * width;
-#define BEAM_GROUP_PARTIAL(TW) hipLaunchKernelGGL(k_beam_group_partial<TW>, dim3(S, BEAM_CHUNKS), dim3(256), 0, st, logits, (size_t)ldl, beam, row0, width, V, inv_temp, diversity_penalty, first, rs, scores, seq_lengths, has_stopped, picks, pval, pidx)
-        switch (width) {
-            case 1: BEAM_GROUP_PARTIAL(1); break;
-            case 2: BEAM_GROUP_PARTIAL(2); break;
-            case 3: BEAM_GROUP_PARTIAL(3); break;
-            case 4: BEAM_GROUP_PARTIAL(4); break;
-            case 5: BEAM_GROUP_PARTIAL(5); break;
-            case 8: BEAM_GROUP_PARTIAL(8); break;
-            default: BEAM_GROUP_PARTIAL(0); break;
-        }
-#undef BEAM_GROUP_PARTIAL
-        hipLaunchKernelGGL(k_beam_group_final, dim3(S), dim3(64), 0, st, beam, row0, width, V, first, stop_token, pval, pidx, scores, seq_lengths,
-                           has_stopped, next_tokens, src_rows, picks);
-    }
+    const BeamWs w = beam_ws(ws, S, beam, width, true);
+    launch_rowstats(st, logits, ldl, S * beam, V, inv_temp, w.rs);
+    for (int g = 0; g < groups; g++)
+        launch_select(st, S, beam, g * width, width, V, logits, ldl, inv_temp, diversity_penalty, first, stop_token, w, scores, seq_lengths,
+                      has_stopped, next_tokens, src_rows);
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 

@@ -5,6 +5,7 @@
 // cc_logits_constrain need).  The unit vectors come from cc_decode_hidden_unit (decode.hip).  fp32 / integer work only, so this unit is
 // built once (Makefile).  Plain C++: no inline assembly.
 #include "layout.h"
+#include "select.hip.h"
 
 using namespace CC_NS;
 
@@ -15,16 +16,12 @@ constexpr int CS_VMAX = 2097152;
 constexpr int CS_DMAX = 2048;
 constexpr int TK_T = 512;                 // threads per caption in the top-k kernel (8 waves)
 constexpr int SL_T = 256;                 // threads per caption in the select kernel (4 waves)
-constexpr int CS_NONE = 0x7fffffff;
-
-__device__ __forceinline__ bool cs_better(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
 
 // ---- top-k with probabilities ------------------------------------------------------------------------------------------------------------
-// One workgroup per caption, the row read once.  Every thread keeps, over its share of the row, a running (max, sum of exp(x - max)) pair
-// (k_beam_rowstats' form: the sum is rescaled when the max moves) and its own K best (value, id) in registers, best first: an element
-// enters by one compare against the list's last entry and sinks in with statically indexed swaps.  The block then takes K rounds of
-// arg-max over the threads' list heads (shuffles inside a wave, LDS between waves); the winner's owner shifts its list up by one.  The
-// block's K best are among the threads' K best, so nothing is missed.  -inf never enters a list: an empty head is (-inf, CS_NONE).
+// One workgroup per caption, the row read once.  Every thread keeps, over its share of the row, a running softmax pair and its own K best
+// (value, id) in a sorted register list (select.hip.h, as k_beam_rowstats and the beam kernels' overflow path do).  The block then takes K
+// rounds of arg-max over the threads' list heads; the winner's owner pops its list.  The block's K best are among the threads' K best, so
+// nothing is missed.  -inf never enters a list: an empty head is (-inf, SEL_NONE).
 template <int K, bool VEC>   // VEC: rows are 16-B aligned (ldl % 4 == 0, aligned base) -> float4 loads
 __global__ __launch_bounds__(TK_T) void k_contrastive_topk(const float* __restrict__ logits, size_t ldl, int rows_per, const int* __restrict__ sel,
                                                            int V, const unsigned char* __restrict__ stopped, int* __restrict__ cand_tok,
@@ -38,81 +35,40 @@ __global__ __launch_bounds__(TK_T) void k_contrastive_topk(const float* __restri
         return;
     }
     const float* lg = logits + ((size_t)s * rows_per + (sel ? min(max(sel[s], 0), rows_per - 1) : 0)) * ldl;   // never outside the caption's rows
-    float tv[K];
-    int ti[K];
-#pragma unroll
-    for (int j = 0; j < K; j++) { tv[j] = -INFINITY; ti[j] = CS_NONE; }
-    float m = -INFINITY, sum = 0.f;
+    SortedList<K> top;
+    top.clear();
+    SoftmaxPair p;
     auto take = [&](float x, int v) {
-        if (x > -INFINITY && cs_better(x, v, tv[K - 1], ti[K - 1])) {
-            tv[K - 1] = x; ti[K - 1] = v;
-#pragma unroll
-            for (int j = K - 1; j > 0; j--) {
-                if (cs_better(tv[j], ti[j], tv[j - 1], ti[j - 1])) {
-                    const float fv = tv[j]; tv[j] = tv[j - 1]; tv[j - 1] = fv;
-                    const int fi = ti[j]; ti[j] = ti[j - 1]; ti[j - 1] = fi;
-                }
-            }
-        }
+        if (x > -INFINITY) top.enter(x, v);
     };
     const int V4 = VEC ? (V >> 2) : 0;
     for (int v = tid; v < V4; v += TK_T) {
         const float4 x = reinterpret_cast<const float4*>(lg)[v];
-        const float mx = fmaxf(fmaxf(x.x, x.y), fmaxf(x.z, x.w));
-        if (mx > m) { sum *= expf(m - mx); m = mx; }                    // expf(-inf) = 0 on the first group
-        if (m > -INFINITY) sum += expf(x.x - m) + expf(x.y - m) + expf(x.z - m) + expf(x.w - m);   // banned tokens (-inf) first: no -inf - -inf
+        p.add4(x.x, x.y, x.z, x.w);
         take(x.x, 4 * v); take(x.y, 4 * v + 1); take(x.z, 4 * v + 2); take(x.w, 4 * v + 3);
     }
     for (int v = V4 * 4 + tid; v < V; v += TK_T) {
         const float x = lg[v];
-        if (x > m) { sum *= expf(m - x); m = x; }
-        if (m > -INFINITY) sum += expf(x - m);
+        p.add(x);
         take(x, v);
     }
     // the row's (max, sum): pairs merged across lanes and waves in a fixed order
-    auto merge = [&](float om, float os) {
-        const float mx = fmaxf(m, om);
-        if (mx == -INFINITY) return;                                    // both empty
-        sum = sum * expf(m - mx) + os * expf(om - mx);
-        m = mx;
-    };
-    for (int o = 32; o > 0; o >>= 1) {
-        const float om = __shfl_xor(m, o, 64), os = __shfl_xor(sum, o, 64);
-        merge(om, os);
-    }
-    if (lane == 0) { redm[wv] = m; reds[wv] = sum; }
+    p.wave_merge();
+    if (lane == 0) { redm[wv] = p.m; reds[wv] = p.sum; }
     __syncthreads();
-    m = redm[0]; sum = reds[0];
-    for (int i = 1; i < NW; i++) merge(redm[i], reds[i]);               // every thread, the same order: block-uniform (m, sum)
-    // K rounds of block arg-max over the list heads (red buffers double-buffered on the round: one barrier per round)
+    p.m = redm[0]; p.sum = reds[0];
+    for (int i = 1; i < NW; i++) p.merge(redm[i], reds[i]);             // every thread, the same order: block-uniform (m, sum)
+    // K rounds of block arg-max over the list heads
 #pragma unroll
     for (int r = 0; r < K; r++) {
-        float bv = tv[0];
-        int bi = ti[0];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (cs_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-        }
-        if (lane == 0) { redv[(r & 1) * NW + wv] = bv; redi[(r & 1) * NW + wv] = bi; }
-        __syncthreads();
-        bv = redv[(r & 1) * NW]; bi = redi[(r & 1) * NW];
-#pragma unroll
-        for (int w = 1; w < NW; w++) {
-            const float ov = redv[(r & 1) * NW + w];
-            const int oi = redi[(r & 1) * NW + w];
-            if (cs_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-        }
-        if (bi != CS_NONE && bi == ti[0]) {                             // ids are unique: exactly one owner retires its head
-#pragma unroll
-            for (int j = 0; j + 1 < K; j++) { tv[j] = tv[j + 1]; ti[j] = ti[j + 1]; }
-            tv[K - 1] = -INFINITY; ti[K - 1] = CS_NONE;
-        }
+        float bv = top.v[0];
+        int bi = top.i[0];
+        block_argmax<NW>(r, bv, bi, redv, redi);
+        top.retire(bi);
         if (tid == 0) {
-            const bool ok = bi != CS_NONE;
+            const bool ok = bi != SEL_NONE;
             cand_tok[s * K + r] = ok ? bi : 0;
-            cand_prob[s * K + r] = ok ? expf(bv - m) / sum : -1.0f;
+            cand_prob[s * K + r] = ok ? expf(bv - p.m) / p.sum : -1.0f;
         }
     }
 }

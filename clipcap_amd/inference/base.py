@@ -162,12 +162,15 @@ def generate_beam_rounds(model, embeds: torch.Tensor, beam_size: int = 5, entry_
     else:
         lg[::beam_size] = logits0                                               # row 0 of every beam set
     bufs = beam_buffers(dev, S, beam_size, V) if G == 1 else beam_group_buffers(dev, S, beam_size, G, V)   # this decode's own step outputs + scratch
+
+    def update(logits, first, lpart=None):                                      # the step's update -> (next tokens, source rows); state in place
+        if G == 1:
+            return beam_step(logits, S, beam_size, temperature, first, stop_token, scores, seq_lengths, has_stopped, bufs, lpart)
+        return beam_group_step(logits, S, beam_size, G, temperature, diversity_penalty, first, stop_token, scores, seq_lengths, has_stopped, bufs)
+
     if bans is not None:
         bans.apply(lg[::beam_size], 0)                                          # the rows the first update reads; no history yet
-    if G == 1:
-        next_tok, src = beam_step(lg, S, beam_size, temperature, True, stop_token, scores, seq_lengths, has_stopped, bufs)
-    else:
-        next_tok, src = beam_group_step(lg, S, beam_size, G, temperature, diversity_penalty, True, stop_token, scores, seq_lengths, has_stopped, bufs)
+    next_tok, src = update(lg, True)
     sess = sess.expand((base // beam_size).to(torch.int32), R)
     if guided:
         usess = usess.expand((base // beam_size).to(torch.int32), R)
@@ -191,18 +194,14 @@ def generate_beam_rounds(model, embeds: torch.Tensor, beam_size: int = 5, entry_
                 logits = sess.forward(x, partials=True, group=beam_size)        # x = wte[next_tokens] (base.py:117)
                 if bans is not None:                                            # a stopped beam's logits are ignored by the update: skipped
                     bans.apply(logits, n, tok[(n - 1) & 1], n, sess.lpart, has_stopped)
-                next_tok, src = beam_step(logits, S, beam_size, temperature, False, stop_token, scores, seq_lengths, has_stopped, bufs, sess.lpart)
+                next_tok, src = update(logits, False, sess.lpart)
             else:                                                               # beam groups, guidance: the update reads the logits, not the partials
                 logits = sess.forward(x, group=beam_size)
                 if guided:                                                      # the same tokens without the prefix; a stopped beam's logits are ignored
                     engine.guide_logits(logits, usess.forward(x, group=beam_size), gs, skip_rows=has_stopped)
                 if bans is not None:
                     bans.apply(logits, n, tok[(n - 1) & 1], n, None, has_stopped)
-                if G == 1:
-                    next_tok, src = beam_step(logits, S, beam_size, temperature, False, stop_token, scores, seq_lengths, has_stopped, bufs, None)
-                else:
-                    next_tok, src = beam_group_step(logits, S, beam_size, G, temperature, diversity_penalty, False, stop_token, scores, seq_lengths,
-                                                    has_stopped, bufs)
+                next_tok, src = update(logits, False)
             sess.beam_advance(beam_size, next_tok, src, wte, n, tok[(n - 1) & 1], tok[n & 1], x)   # base.py:104-117
             if guided:                                                          # the same ancestry for the second cache; rewrites the same tokens and x
                 usess.beam_advance(beam_size, next_tok, src, wte, n, tok[(n - 1) & 1], tok[n & 1], x)

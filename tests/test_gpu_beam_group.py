@@ -111,9 +111,10 @@ def test_group_step_matches_the_float64_statement(shape):
         assert err <= SCORE_TOL, (i, err)
 
 
-@pytest.mark.parametrize("beam", [5, 6, 8, 1])
+@pytest.mark.parametrize("beam", [1, 2, 3, 4, 5, 6, 8])
 def test_one_beam_group_is_bit_identical_to_beam_step(beam):
-    """G = 1 with a penalty: torch.equal outputs and state to cc_beam_step's three-kernel path, through stopped beams."""
+    """G = 1 with a penalty: torch.equal outputs and state to cc_beam_step's three-kernel path, through stopped beams; every compile-time
+    width and one run-time width (the two entry points' kernels are wrappers over one body: a wrong row offset or width shows here)."""
     V, ld = 4099, 4104
     bufs = _inputs(beam, 1, V, ld, steps=4)
     a, b = _state(S * beam), _state(S * beam)
@@ -195,6 +196,69 @@ def test_banned_logits_are_never_picked():
         assert (nt.cpu()[~live] == 0).all()                                         # a stopped beam continues with its padding token
         assert torch.isfinite(scores).all(), i
     assert stopped.any()
+
+
+@pytest.mark.parametrize("beam", [5, 6], ids=["compile-time-width", "run-time-width"])
+def test_a_missing_pick_is_defined_and_in_bounds(beam):
+    """Fewer finite candidates than slots (three per sample, the rest -inf, as extreme token bans leave them), on the first step and on a
+    later step with no beam stopped: cc_beam_step's three-kernel path and cc_beam_group_step with one beam group give torch.equal outputs;
+    the three candidates come first in value order, and the empty slots hold token 0, source row 0 and score -inf, with the length and
+    stop flag the commit gives a continuation of row 0.  Finite scores against float64 within SCORE_TOL."""
+    samples, V, ld, inv_t = 2, 130, 136, 1.0 / TEMP
+    R, ninf = samples * beam, float("-inf")
+    # first step (reads row 0 of every sample): (token, logit), best first
+    cand0 = [(41, 2.0), (7, 1.0), (99, -0.5)]
+    lg0 = torch.full((R, ld), ninf)
+    for s in range(samples):
+        for v, x in cand0:
+            lg0[s * beam, v] = x
+    lp0 = torch.log_softmax(torch.tensor([x for _, x in cand0], dtype=torch.float64) * inv_t, 0)
+    # later step: (row inside the sample, token, logit); rows 0, 2 and 4 (and 5) have no finite logit at all
+    cand1 = [(1, 40, 1.0), (3, 7, 2.0), (3, 99, 0.0)]
+    lg1 = torch.full((R, ld), ninf)
+    for s in range(samples):
+        for b, v, x in cand1:
+            lg1[s * beam + b, v] = x
+    sc_in = -0.4 * torch.arange(1, R + 1, dtype=torch.float32)
+    len_in = 1.0 + (torch.arange(R) % beam).float()                                 # 1 .. beam: a slot's length names its source row
+    outs = []
+    for entry in ("plain", "group"):
+        scores, seql, stopped = _state(R)
+        res = []
+        for first, lg in ((True, lg0), (False, lg1)):
+            if not first:
+                scores.copy_(sc_in)
+                seql.copy_(len_in)
+                stopped.zero_()
+            dev = lg.cuda()[:, :V]
+            if entry == "plain":
+                nt, sr = beam_step(dev, samples, beam, TEMP, first, STOP, scores, seql, stopped)
+            else:
+                nt, sr = beam_group_step(dev, samples, beam, 1, TEMP, PENALTY, first, STOP, scores, seql, stopped)
+            res.append([t.cpu().clone() for t in (nt, sr, scores, seql, stopped)])
+        outs.append(res)
+    for a, b in zip(outs[0], outs[1]):
+        assert all(torch.equal(x.view(torch.int32) if x.dtype == torch.float32 else x, y.view(torch.int32) if y.dtype == torch.float32 else y)
+                   for x, y in zip(a, b))
+    for s in range(samples):
+        sl = slice(s * beam, (s + 1) * beam)
+        nt, sr, sc, ln, st = (t[sl] for t in outs[0][0])
+        assert nt.tolist() == [v for v, _ in cand0] + [0] * (beam - 3) and sr.tolist() == [0] * beam
+        assert (sc[:3].double() - lp0).abs().max().item() <= SCORE_TOL and (sc[3:] == ninf).all()
+        assert ln.tolist() == [1.0] * beam and st.tolist() == [0] * beam
+        # later step, float64: value = (score + log-probability) / (length + 1), score = value * (length + 1)
+        sc64, ln64 = sc_in[sl].double(), len_in[sl].double() + 1.0
+        lp3 = torch.log_softmax(torch.tensor([2.0, 0.0], dtype=torch.float64) * inv_t, 0)
+        vals = [(sc64[1] / ln64[1]).item(), ((sc64[3] + lp3[0]) / ln64[3]).item(), ((sc64[3] + lp3[1]) / ln64[3]).item()]
+        order = sorted(range(3), key=lambda k: -vals[k])
+        assert min(vals[order[k]] - vals[order[k + 1]] for k in range(2)) >= 1e-3      # a condition on the inputs: the order is not a near-tie
+        nt, sr, sc, ln, st = (t[sl] for t in outs[0][1])
+        assert nt.tolist() == [cand1[k][1] for k in order] + [0] * (beam - 3)
+        assert sr.tolist() == [cand1[k][0] for k in order] + [0] * (beam - 3)
+        want = torch.tensor([vals[k] * ln64[cand1[k][0]].item() for k in order], dtype=torch.float64)
+        assert (sc[:3].double() - want).abs().max().item() <= SCORE_TOL and (sc[3:] == ninf).all()
+        assert ln.tolist() == [ln64[cand1[k][0]].item() for k in order] + [ln64[0].item()] * (beam - 3)
+        assert st.tolist() == [0] * beam                                            # neither a picked token nor token 0 is the stop token
 
 
 def _seeded_run():

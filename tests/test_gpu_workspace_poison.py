@@ -23,8 +23,9 @@ anything reads it (so the -1 of the poison never becomes an address):
     those and writes skeys / info at a permutation of [0, R) (keys are unique); k_sc_compact reads [0, R) and writes heads[0, cnt[0]),
     mstarts[0, cnt[1]) and cnt[0..1]; k_sc_sum / k_sc_fold read exactly those ranges; part is written by k_sc_sum before k_sc_fold.
     Token ids are clamped to [0, Vp) in k_sc_sort_tile.
-  * beam scratch (beam.hip): pidx — every (sample, chunk, slot < beam) written by k_beam_partial / k_beam_group_partial before
-    k_beam_final / k_beam_group_final read them; picks — beam group g reads slots [0, row0) that the finals of groups < g wrote this step.
+  * beam scratch (beam.hip): pidx — every (sample, chunk, slot < width) written by beam_partial_body (k_beam_partial /
+    k_beam_group_partial) before beam_final_body (k_beam_final / k_beam_group_final) reads them; picks — beam group g reads slots
+    [0, row0) that the finals of groups < g wrote this step; the plain kernels have no picks.
   * MapperWS has no integer buffer.  DecodeSession.row_map is not scratch: it is built by arange at construction and never poisoned here.
 The token inputs themselves (int64, -1 pads) are the caller's, not workspace; embed_concat and ce_targets clamp id < 0.
 
