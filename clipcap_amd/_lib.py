@@ -96,6 +96,8 @@ SIGNATURES = {
     "cc_lmhead_smooth_scratch_floats": (_L, [_GC, _GS]),
     "cc_lmhead_ce_fwd_smooth": (_I, [_GC, _GS, _P, _P, _P, _P, _F, _P, _P, _P]),
     "cc_lmhead_ce_bwd_smooth": (_I, [_GC, _GS, _P, _P, _P, _P, _P, _F, _P, _P, _P]),
+    "cc_lmhead_ce_fwd_w": (_I, [_GC, _GS, _P, _P, _P, _P, _P, _F, _P, _P, _P]),
+    "cc_lmhead_ce_bwd_w": (_I, [_GC, _GS, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P]),
     "cc_lmhead_put_x": (_I, [_GC, _GS, _P, _P, _P]),
     "cc_lmhead_get": (_I, [_GC, _GS, _P, _I, _P, _L, _P]),
     "cc_gpt2_bwd": (_I, [_GC, _GS, _P, _P, _P, _P, _P, _P, _P]),

@@ -719,11 +719,17 @@ struct SmoothScratch {
 // eps in [0, 1) and a usable scratch; written so that a NaN fails
 inline bool smooth_ok(float eps, const float* scratch) { return eps >= 0.f && eps < 1.f && scratch && !((uintptr_t)scratch & 15); }
 
-// cc_lmhead_ce_fwd (scratch == nullptr: stats of 2 floats) and cc_lmhead_ce_fwd_smooth (stats of 3) share this body
+// the weighted pair: a row_weight, and a scratch unless eps == 0 (then no smoothing launch reads one)
+inline bool weighted_ok(const float* row_weight, float eps, const float* scratch) {
+    return row_weight && eps >= 0.f && eps < 1.f && (eps == 0.f || scratch) && !((uintptr_t)scratch & 15);
+}
+
+// cc_lmhead_ce_fwd (scratch == nullptr: stats of 2 floats), cc_lmhead_ce_fwd_smooth (stats of 3) and cc_lmhead_ce_fwd_w (row_weight set:
+// stats of 3, scratch only where eps != 0) share this body
 static int lmhead_ce_fwd_body(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const int64_t* tokens,
-                       float eps, float* scratch, float* stats, void* stream);
+                       float eps, float* scratch, float* stats, void* stream, const float* row_weight = nullptr);
 static int lmhead_ce_bwd_body(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const float* denom,
-                       const float* loss_scale, float eps, float* scratch, float* g32, void* stream);
+                       const float* loss_scale, float eps, float* scratch, float* g32, void* stream, const float* row_weight = nullptr);
 }  // namespace
 
 int CC_API(cc_lmhead_ce_fwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const int64_t* tokens,
@@ -748,6 +754,18 @@ int CC_API(cc_lmhead_ce_bwd_smooth)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s
     return lmhead_ce_bwd_body(c, s, w32, w16, ws, denom, loss_scale, eps, scratch, g32, stream);
 }
 
+int CC_API(cc_lmhead_ce_fwd_w)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const int64_t* tokens,
+                       const float* row_weight, float eps, float* scratch, float* stats3, void* stream) {
+    if (!weighted_ok(row_weight, eps, scratch)) return CC_ERR_ARG;
+    return lmhead_ce_fwd_body(c, s, w32, w16, ws, tokens, eps, scratch, stats3, stream, row_weight);
+}
+
+int CC_API(cc_lmhead_ce_bwd_w)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const float* denom,
+                       const float* loss_scale, const float* row_weight, float eps, float* scratch, float* g32, void* stream) {
+    if (!weighted_ok(row_weight, eps, scratch)) return CC_ERR_ARG;
+    return lmhead_ce_bwd_body(c, s, w32, w16, ws, denom, loss_scale, eps, scratch, g32, stream, row_weight);
+}
+
 int CC_API(cc_lmhead_ce_bwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const float* denom,
                      const float* loss_scale, float* g32, void* stream) {
     return lmhead_ce_bwd_body(c, s, w32, w16, ws, denom, loss_scale, 0.f, nullptr, g32, stream);
@@ -755,14 +773,14 @@ int CC_API(cc_lmhead_ce_bwd)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const
 
 namespace {
 static int lmhead_ce_fwd_body(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const int64_t* tokens,
-                       float eps, float* scratch, float* stats, void* stream) {
+                       float eps, float* scratch, float* stats, void* stream, const float* rw) {
     if (!gpt2_cfg_ok(c) || !shape_ok(c, s) || s->mode < 1 || s->L < 1 || !w32 || !w16 || !ws || !tokens || !stats) return CC_ERR_ARG;
     const int cap = s->T - s->L;
     if (cap != s->cap) return CC_ERR_SHAPE;  // the loss consumes every token column (model.py:108-109)
     Gpt2Pass ps(c, s, cap, ws, stream);
     auto& [st, o, w, cx, D, M, H, hd] = ps;
     const int Mc = s->B * cap, npart = c->Vp / 64;
-    if (hipMemsetAsync(stats, 0, 2 * sizeof(float), st) != hipSuccess) return CC_ERR_LAUNCH;
+    if (hipMemsetAsync(stats, 0, (rw ? 3 : 2) * sizeof(float), st) != hipSuccess) return CC_ERR_LAUNCH;
     CC_TRY(ce_targets(reinterpret_cast<const long long*>(tokens), w.target, w.row_map, s->B, cap, s->L, s->T, st));
     // ln_f only on the rows the loss reads: L-1 .. T-2 of every sample (model.py:108)
     CC_TRY(ln_fwd(w.x[c->NL], D, w.row_map, w32 + o.lnf_w, w32 + o.lnf_b, w.hf16, nullptr, w.meanf, w.rstdf, Mc, D, st));
@@ -771,14 +789,14 @@ static int lmhead_ce_fwd_body(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, cons
     if (ef) CC_TRY(lm_tgt_ref(w.hf16, wte_rows, D, w.target, w.cref, Mc, st));
     CC_TIMED(CC_SITE_LMHEAD_FWD, st, gemm_lmhead(w.hf16, D, W16(w16, o.wte), D, Mc, c->Vp, c->V, D, lm_logits(c, s, w.logits16), c->Vp, w.pmax, w.psum, npart, w.target, w.tgt_logit, cx,
                                                  ef ? w.cref : nullptr));
-    CC_TRY(ce_rows(w.pmax, w.psum, npart, w.target, ef ? w.cref : w.tgt_logit, w.lse_row, w.row_loss, stats, Mc, st));   // cref IS the target logit
-    if (!scratch) return CC_OK;
+    CC_TRY(ce_rows(w.pmax, w.psum, npart, w.target, ef ? w.cref : w.tgt_logit, w.lse_row, w.row_loss, stats, Mc, st, rw));   // cref IS the target logit
+    if (!scratch || (rw && eps == 0.f)) return CC_OK;      // with weights ce_rows has written the third float too
     if (eps == 0.f)      // the plain chain, and the third float
         return hipMemcpyAsync(stats + 2, stats, sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
     // + eps (z_t - zbar) per kept row: wbar from the rows the lm_head GEMM read, zbar a GEMV over the stored hf — no pass over V
     const SmoothScratch sm(c, s, scratch);
     CC_TRY(smooth_wbar(reinterpret_cast<const act_t*>(wte_rows), c->V, D, sm.part, sm.wbar, st));
-    return smooth_rows(w.hf16, sm.wbar, D, w.target, ef ? w.cref : w.tgt_logit, eps, sm.zbar, sm.term, stats, Mc, st);
+    return smooth_rows(w.hf16, sm.wbar, D, w.target, ef ? w.cref : w.tgt_logit, eps, sm.zbar, sm.term, stats, Mc, st, rw);
 }
 }  // namespace
 
@@ -801,7 +819,7 @@ int CC_API(cc_lmhead_score)(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const 
 
 namespace {
 static int lmhead_ce_bwd_body(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, const float* w32, const uint16_t* w16, void* ws, const float* denom,
-                       const float* loss_scale, float eps, float* scratch, float* g32, void* stream) {
+                       const float* loss_scale, float eps, float* scratch, float* g32, void* stream, const float* rw) {
     if (!gpt2_cfg_ok(c) || !shape_ok(c, s) || s->mode < 1 || !w32 || !w16 || !ws || !denom || (s->mode == 2 && !g32)) return CC_ERR_ARG;
     const int cap = s->T - s->L;
     Gpt2Pass ps(c, s, cap, ws, stream);
@@ -812,14 +830,17 @@ static int lmhead_ce_bwd_body(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, cons
     // GEMMs' finishing passes (EpiLMHead comment).  Otherwise: the in-place softmax-gradient pass over the stored logits.
     const bool ef = lm_exp_form(s);
     const LmFix fix{w.lmfac, w.target, kX3 ? reinterpret_cast<const op16_t*>(w32 + o.wte) : W16(w16, o.wte)};
-    if (ef) CC_TRY(lm_rowfac(w.cref, w.lse_row, w.target, denom, loss_scale, w.lmfac, Mc, st));
+    if (ef) CC_TRY(lm_rowfac(w.cref, w.lse_row, w.target, denom, loss_scale, w.lmfac, Mc, st, rw));
     const Act lg = lm_logits(c, s, w.logits16);
     ActIn dlog = lg;                    // the A operand of the input-gradient GEMM (bf16x3 exponential form: E, written as its operand image)
     // bf16x3, frozen LM: nothing but that GEMM reads d logits -> the softmax-gradient pass writes its [hi | hi | lo] operand image straight
     // into the call's operand scratch (sized for exactly this image, gpt2_carve) instead of fp32 values a split pass would re-read
     op16_t* dimg = (kX3 && !ef && !full && x3_img_on()) ? x3_scratch_block(cx, x3_img(Mc, c->Vp)) : nullptr;
     if (dimg) dlog = ActIn(reinterpret_cast<const act_t*>(dimg), c->Vp);
-    if (!ef) CC_TRY(ce_dlogits(w.logits16, c->Vp, c->V, w.target, w.lse_row, denom, loss_scale, Mc, st, dimg));
+    if (!ef) CC_TRY(ce_dlogits(w.logits16, c->Vp, c->V, w.target, w.lse_row, denom, loss_scale, Mc, st, dimg, rw));
+    // logit form with weights: d logits carries |factor|; the factor's sign is applied to the rows of d hf and of the weight-gradient operand
+    const bool sgn = rw && !ef;
+    if (sgn) CC_TRY(lm_rowsign(w.target, denom, loss_scale, rw, w.lmfac, Mc, st));
     // d hf = dlogits · wte   ([Mc,Vp] x [Vp(k), D(n)])
     // K = Vp is deep and the output narrow: K slices over the idle CUs, slabs parked in du16 (free until the first layer's backward)
     const auto lm_dgrad = [&]() {
@@ -831,6 +852,7 @@ static int lmhead_ce_bwd_body(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, cons
         return (rc2 != CC_OK || !ef) ? rc2 : lm_dgrad_fix(w.dhf16, w.lmfac, w.target, fix.wte, D, Mc, st);
     };
     CC_TIMED(CC_SITE_LMHEAD_DGRAD, st, lm_dgrad());
+    if (sgn) CC_TRY(lm_scale_rows_inplace(w.dhf16, w.lmfac, D, Mc, st));
     if (full) {      // tied lm_head: d wte += dlogits^T hf  (= E^T (r hf) - onehot^T (w hf) in the exponential form)
         if (ef) {
             CC_TRY(lm_scale_rows(w.hf16, w.lmfac, w.hfs16, D, Mc, st));
@@ -839,14 +861,15 @@ static int lmhead_ce_bwd_body(const cc_gpt2_cfg* c, const cc_gpt2_shape* s, cons
             oh.ids32 = w.target; oh.act = w.hf16; oh.fac = w.lmfac;
             CC_TRY(scatter_rows(oh, Mc, D, c->Vp, g32 + o.wte, w.scat, st));
         } else {
-            CC_TRY(gemm_wgrad(lg, c->Vp, w.hf16, D, c->Vp, D, Mc, g32 + o.wte, D, w.wg_scratch, cx));
+            if (sgn) CC_TRY(lm_scale_rows(w.hf16, w.lmfac, w.hfs16, D, Mc, st));
+            CC_TRY(gemm_wgrad(lg, c->Vp, sgn ? w.hfs16 : w.hf16, D, c->Vp, D, Mc, g32 + o.wte, D, w.wg_scratch, cx));
         }
     }
     if (scratch && eps != 0.f) {
         // label smoothing, a pass of its own after the input-gradient GEMM and its fix: d hf += c (wte[t] - wbar) with the forward's wbar;
         // tied lm_head: d wte[t] += c hf (a row scatter, as the one-hot term above) and d wte[v < V] -= (sum of c hf) / V (one vector)
         const SmoothScratch sm(c, s, scratch);
-        CC_TRY(smooth_dhf(w.dhf16, w.target, denom, loss_scale, eps, reinterpret_cast<const act_t*>(fix.wte), sm.wbar, sm.coef, D, Mc, st));
+        CC_TRY(smooth_dhf(w.dhf16, w.target, denom, loss_scale, eps, reinterpret_cast<const act_t*>(fix.wte), sm.wbar, sm.coef, D, Mc, st, rw));
         if (full) {
             ScatterSrc sc;
             sc.ids32 = w.target; sc.act = w.hf16; sc.fac = sm.coef;

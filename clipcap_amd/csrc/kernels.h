@@ -91,25 +91,44 @@ struct ScatterSrc {
 size_t scatter_ws_bytes(int R, int D);
 int scatter_rows(const ScatterSrc& s, int R, int D, int Vp, float* dst, void* ws, hipStream_t st);
 
+// Per-row loss weights (cc_lmhead_ce_fwd_w / _bwd_w): the one place that turns "kept" into a factor.  A row that is not kept (target 0)
+// gets 0 by selection, so neither x nor the bits of its weight (NaN, inf) reach anything; a kept row gets x * rw[row] (WT) or x.
+// rw == 1.0 gives the bits of the form without weights.  The row_weight arguments below: nullptr launches the <false> forms, what the entry points
+// without weights launch.
+#ifdef __HIPCC__
+template <bool WT>
+__device__ __forceinline__ float row_factor(int target, float x, const float* __restrict__ rw, int row) {
+    if (target == 0) return 0.f;
+    return WT ? x * rw[row] : x;
+}
+#endif
+// row_weight: stats has 3 floats, [sum of rw * row_loss over the kept rows, kept rows, the plain sum]; row_loss stays the plain row loss
 int ce_rows(const float* pmax, const float* psum, int npart, const int* target, const float* tgt_logit, float* lse, float* row_loss,
-            float* stats, int M, hipStream_t st);
+            float* stats, int M, hipStream_t st, const float* row_weight = nullptr);
 // scoring: token_logprob[row] = keep[row] ? tgt_logit[row] - lse[row] : 0 (lse folded exactly as ce_rows does), then per sample
 // sample_stats[b] = {sum over its cap rows, kept count} in a fixed order (bit-identical from run to run)
 int score_rows(const float* pmax, const float* psum, int npart, const int* keep, const float* tgt_logit, float* lse, float* token_logprob,
                float* sample_stats, int B, int cap, hipStream_t st);
 int ce_dlogits(act_t* logits, int ld, int V, const int* target, const float* lse, const float* denom, const float* loss_scale, int M,
-               hipStream_t st, op16_t* img = nullptr);   // img (bf16x3): write the gradient as the dgrad GEMM's operand image there instead of in place
+               hipStream_t st, op16_t* img = nullptr,    // img (bf16x3): write the gradient as the dgrad GEMM's operand image there instead of in place
+               const float* row_weight = nullptr);       // row_weight: the factor's MAGNITUDE goes into the gradient; its sign: lm_rowsign
 int ce_targets(const long long* tokens, int* target, int* row_map, int B, int cap, int L, int T, hipStream_t st);
 int score_keep(const long long* tokens, int* keep, int n, int ignore_zero, hipStream_t st);   // keep[i] = tokens[i] >= 0 (&& != 0 with ignore_zero)
 // Exponential form of the lm_head outputs (gemm.hip.h EpiLMHead, bf16 build):
 //   lm_tgt_ref   cref[m] = hf[m] . wte[target[m]]  (16-bit operands, fp32 accumulate): the reference shift of row m
-//   lm_rowfac    fac[m] = {r, w}: w = (target[m] != 0) * loss_scale / max(denom, 1), r = exp(cref[m] - lse[m]) * w
+//   lm_rowfac    fac[m] = {r, w}: w = (target[m] != 0) * loss_scale / max(denom, 1) (* row_weight[m]), r = exp(cref[m] - lse[m]) * w
 //   lm_dgrad_fix dhf[m][:] = r dhf[m][:] - w wte[target[m]][:]  (the path whose GEMM has no finishing pass of its own)
 //   lm_scale_rows out[m][:] = r hf[m][:] (weight-gradient operand);  the one-hot term dwte[target[m]][:] -= w hf[m][:] is scatter_rows' act form
 int lm_tgt_ref(const act_t* hf, const op16_t* wte, int D, const int* target, float* cref, int M, hipStream_t st);
-int lm_rowfac(const float* cref, const float* lse, const int* target, const float* denom, const float* loss_scale, float* fac, int M, hipStream_t st);
+int lm_rowfac(const float* cref, const float* lse, const int* target, const float* denom, const float* loss_scale, float* fac, int M, hipStream_t st,
+              const float* row_weight = nullptr);
+//   lm_rowsign   logit form with row weights: fac[m] = {s, 0}, s = the sign of row m's factor (+1 for 0 and for rows that are not kept): ce_dlogits
+//                then writes d logits with the factor's magnitude, and lm_scale_rows(_inplace) puts s onto d hf and onto the hf rows
+//                of the weight-gradient GEMM, so that a negated weight gives the negated row bit for bit
+int lm_rowsign(const int* target, const float* denom, const float* loss_scale, const float* row_weight, float* fac, int M, hipStream_t st);
 int lm_dgrad_fix(act_t* dhf, const float* fac, const int* target, const op16_t* wte, int D, int M, hipStream_t st);
 int lm_scale_rows(const act_t* hf, const float* fac, act_t* out, int D, int M, hipStream_t st);
+int lm_scale_rows_inplace(act_t* x, const float* fac, int D, int M, hipStream_t st);      // x[m][:] = r x[m][:]
 
 // Label smoothing around the chain above (smooth.hip; include/clipcap_hip.h cc_lmhead_ce_fwd_smooth for the algebra).  wte: the rows as
 // they are read elementwise ([V][D] of the operand image; bf16x3: of the fp32 master).  All sums in a fixed order, no atomics.
@@ -118,12 +137,13 @@ int lm_scale_rows(const act_t* hf, const float* fac, act_t* out, int D, int M, h
 //   smooth_dhf        coef[m] = {0, -c_m}, c_m = (target[m] != 0) eps loss_scale / max(denom, 1); dhf[m][:] += c_m (wte[target[m]][:] - wbar[:])
 //   smooth_dwte_bcast hsum[:] = sum of c_m hf[m][:] (partials in the call's reduction scratch, fold_partials); dwte[v][:] -= hsum[:] / V, v < V
 //                     (the other half, dwte[target[m]][:] += c_m hf[m][:], is scatter_rows' act form fed coef)
+// row_weight (smooth_rows, smooth_dhf): term[m] and c_m times row_weight[m] on kept rows; smooth_rows then leaves stats3[2] as ce_rows wrote it
 inline int smooth_wbar_slices(int V) { return std::max(1, std::min((V + 127) / 128, 256)); }
 int smooth_wbar(const act_t* wte, int V, int D, float* part, float* wbar, hipStream_t st);
 int smooth_rows(const act_t* hf, const float* wbar, int D, const int* target, const float* tgt, float eps, float* zbar, float* term,
-                float* stats3, int M, hipStream_t st);
+                float* stats3, int M, hipStream_t st, const float* row_weight = nullptr);
 int smooth_dhf(act_t* dhf, const int* target, const float* denom, const float* loss_scale, float eps, const act_t* wte, const float* wbar,
-               float* coef, int D, int M, hipStream_t st);
+               float* coef, int D, int M, hipStream_t st, const float* row_weight = nullptr);
 int smooth_dwte_bcast(const act_t* hf, const float* coef, int D, int M, int V, float* hsum, float* dwte, Call& cx);
 
 int adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, float wd, int step, float gscale,

@@ -61,31 +61,48 @@ __global__ __launch_bounds__(256) void k_ce_rows(const float* __restrict__ pmax,
         row_loss[row] = (target[row] != 0) ? l - tgt_logit[row] : 0.f;
     }
 }
-// stats[0] = sum of kept-row losses, stats[1] = kept rows — one block, fixed summation order (deterministic, no atomics)
-__global__ __launch_bounds__(1024) void k_ce_stats(const float* __restrict__ row_loss, const int* __restrict__ target, float* __restrict__ stats,
-                                                   int M) {
-    __shared__ float sl[16], sc[16];
-    float a = 0.f, c = 0.f;
+// stats[0] = sum of kept-row losses, stats[1] = kept rows — one block, fixed summation order (deterministic, no atomics).
+// WT (per-row loss weights, row_factor): stats[0] = the sum of rw[i] * row_loss[i] over the kept rows, stats[2] = the plain sum in the
+// order stats[0] has without weights; a kept row of weight 0 still counts in stats[1].  row_loss itself stays the plain row loss.
+template <bool WT>
+__global__ __launch_bounds__(1024) void k_ce_stats(const float* __restrict__ row_loss, const int* __restrict__ target,
+                                                   const float* __restrict__ rw, float* __restrict__ stats, int M) {
+    __shared__ float sl[16], sc[16], sp[WT ? 16 : 1];
+    float a = 0.f, c = 0.f, p = 0.f;
     for (int i = threadIdx.x; i < M; i += 1024) {
-        a += row_loss[i];
-        c += (target[i] != 0) ? 1.f : 0.f;
+        const int t = target[i];
+        const float l = row_loss[i];
+        a += WT ? row_factor<true>(t, l, rw, i) : l;
+        c += (t != 0) ? 1.f : 0.f;
+        if (WT) p += l;
     }
     a = wave_sum(a);
     c = wave_sum(c);
-    if ((threadIdx.x & 63) == 0) { sl[threadIdx.x >> 6] = a; sc[threadIdx.x >> 6] = c; }
+    if (WT) p = wave_sum(p);
+    if ((threadIdx.x & 63) == 0) {
+        sl[threadIdx.x >> 6] = a;
+        sc[threadIdx.x >> 6] = c;
+        if (WT) sp[threadIdx.x >> 6] = p;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        float ta = 0.f, tc = 0.f;
-        for (int w = 0; w < 16; w++) { ta += sl[w]; tc += sc[w]; }
+        float ta = 0.f, tc = 0.f, tp = 0.f;
+        for (int w = 0; w < 16; w++) {
+            ta += sl[w];
+            tc += sc[w];
+            if (WT) tp += sp[w];
+        }
         stats[0] = ta;
         stats[1] = tc;
+        if (WT) stats[2] = tp;
     }
 }
 int ce_rows(const float* pmax, const float* psum, int npart, const int* target, const float* tgt_logit, float* lse, float* row_loss,
-            float* stats, int M, hipStream_t st) {
+            float* stats, int M, hipStream_t st, const float* row_weight) {
     if (M <= 0) return CC_OK;
     hipLaunchKernelGGL(k_ce_rows, dim3((M + 3) / 4), dim3(256), 0, st, pmax, psum, npart, target, tgt_logit, lse, row_loss, M);
-    hipLaunchKernelGGL(k_ce_stats, dim3(1), dim3(1024), 0, st, row_loss, target, stats, M);
+    if (row_weight) hipLaunchKernelGGL(k_ce_stats<true>, dim3(1), dim3(1024), 0, st, row_loss, target, row_weight, stats, M);
+    else hipLaunchKernelGGL(k_ce_stats<false>, dim3(1), dim3(1024), 0, st, row_loss, target, nullptr, stats, M);
     return CC_OK;
 }
 
@@ -132,16 +149,20 @@ int score_rows(const float* pmax, const float* psum, int npart, const int* keep,
 
 // img (bf16x3 build): the gradient is written as the [hi | hi | lo] operand image of the lm_head's input-gradient GEMM (rows of 3 ld
 // 16-bit elements) into img instead of in place over the fp32 logits
+template <bool WT>
 __global__ __launch_bounds__(256) void k_ce_dlogits(act_t* __restrict__ logits, int ld, int V, const int* __restrict__ target,
                                                     const float* __restrict__ lse, const float* __restrict__ denom,
-                                                    const float* __restrict__ loss_scale, int M, op16_t* __restrict__ img) {
+                                                    const float* __restrict__ loss_scale, const float* __restrict__ rw, int M,
+                                                    op16_t* __restrict__ img) {
     const int col = (blockIdx.x * 256 + threadIdx.x) * 8;
     if (col >= ld) return;
     const float inv = (loss_scale ? loss_scale[0] : 1.0f) / fmaxf(denom[0], 1.0f);
     for (int row = blockIdx.y; row < M; row += gridDim.y) {
         const int t = target[row];
         const float l = lse[row];
-        const float w = (t != 0) ? inv : 0.f;
+        // WT: the factor's magnitude; its sign goes onto the GEMMs' other side (k_lm_rowsign), so that the matrix cores, whose
+        // accumulation is not symmetric under negation of an operand, see the operand of the row with the weight's sign dropped
+        const float w = WT ? fabsf(row_factor<WT>(t, inv, rw, row)) : row_factor<WT>(t, inv, rw, row);
         act_t* p = logits + (size_t)row * ld + col;
         float f[8];
         act_ld8(p, f);
@@ -162,10 +183,12 @@ __global__ __launch_bounds__(256) void k_ce_dlogits(act_t* __restrict__ logits, 
     }
 }
 int ce_dlogits(act_t* logits, int ld, int V, const int* target, const float* lse, const float* denom, const float* loss_scale, int M,
-               hipStream_t st, op16_t* img) {
+               hipStream_t st, op16_t* img, const float* row_weight) {
     if (ld & 7) return CC_ERR_SHAPE;
     if (M <= 0) return CC_OK;
-    hipLaunchKernelGGL(k_ce_dlogits, dim3((ld / 8 + 255) / 256, std::min(M, 32768)), dim3(256), 0, st, logits, ld, V, target, lse, denom, loss_scale, M, img);
+    const dim3 grid((ld / 8 + 255) / 256, std::min(M, 32768));
+    if (row_weight) hipLaunchKernelGGL(k_ce_dlogits<true>, grid, dim3(256), 0, st, logits, ld, V, target, lse, denom, loss_scale, row_weight, M, img);
+    else hipLaunchKernelGGL(k_ce_dlogits<false>, grid, dim3(256), 0, st, logits, ld, V, target, lse, denom, loss_scale, nullptr, M, img);
     return CC_OK;
 }
 
@@ -201,21 +224,42 @@ int lm_tgt_ref(const act_t* hf, const op16_t* wte, int D, const int* target, flo
     hipLaunchKernelGGL(k_lm_tgt_ref, dim3((M + 3) / 4), dim3(256), 0, st, hf, wte, D, target, cref, M);
     return CC_OK;
 }
+// w: row_factor, of either sign with weights; a kept row of weight 0 has w == 0 and so r == 0, as an ignored row has — its gradient IS zero
+template <bool WT>
 __global__ void k_lm_rowfac(const float* __restrict__ cref, const float* __restrict__ lse, const int* __restrict__ target,
-                            const float* __restrict__ denom, const float* __restrict__ loss_scale, float* __restrict__ fac, int M) {
+                            const float* __restrict__ denom, const float* __restrict__ loss_scale, const float* __restrict__ rw,
+                            float* __restrict__ fac, int M) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M) return;
     const float inv = (loss_scale ? loss_scale[0] : 1.0f) / fmaxf(denom[0], 1.0f);
-    const float w = target[i] != 0 ? inv : 0.f;
+    const float w = row_factor<WT>(target[i], inv, rw, i);
     fac[2 * i] = w != 0.f ? __expf(cref[i] - lse[i]) * w : 0.f;
     fac[2 * i + 1] = w;
 }
-int lm_rowfac(const float* cref, const float* lse, const int* target, const float* denom, const float* loss_scale, float* fac, int M, hipStream_t st) {
+int lm_rowfac(const float* cref, const float* lse, const int* target, const float* denom, const float* loss_scale, float* fac, int M, hipStream_t st,
+              const float* row_weight) {
     if (M <= 0) return CC_OK;
-    hipLaunchKernelGGL(k_lm_rowfac, dim3((M + 255) / 256), dim3(256), 0, st, cref, lse, target, denom, loss_scale, fac, M);
+    if (row_weight) hipLaunchKernelGGL(k_lm_rowfac<true>, dim3((M + 255) / 256), dim3(256), 0, st, cref, lse, target, denom, loss_scale, row_weight, fac, M);
+    else hipLaunchKernelGGL(k_lm_rowfac<false>, dim3((M + 255) / 256), dim3(256), 0, st, cref, lse, target, denom, loss_scale, nullptr, fac, M);
     return CC_OK;
 }
-// MODE 0: dhf = r dhf - w wte[t];  1: out = r hf
+// logit form with weights: fac[m] = {s, 0}, s = -1 where the row factor (row_factor: loss_scale / max(denom, 1) * rw[m]) is negative, else 1.
+// k_ce_dlogits<true> puts the factor's magnitude into d logits; lm_scale_rows puts s onto the rows of d hf after the input-gradient GEMM and
+// onto the hf rows the tied weight-gradient GEMM reads.  Negating a weight then negates its row's gradient bit for bit.
+__global__ void k_lm_rowsign(const int* __restrict__ target, const float* __restrict__ denom, const float* __restrict__ loss_scale,
+                             const float* __restrict__ rw, float* __restrict__ fac, int M) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= M) return;
+    const float inv = (loss_scale ? loss_scale[0] : 1.0f) / fmaxf(denom[0], 1.0f);
+    fac[2 * i] = row_factor<true>(target[i], inv, rw, i) < 0.f ? -1.f : 1.f;
+    fac[2 * i + 1] = 0.f;
+}
+int lm_rowsign(const int* target, const float* denom, const float* loss_scale, const float* row_weight, float* fac, int M, hipStream_t st) {
+    if (M <= 0) return CC_OK;
+    hipLaunchKernelGGL(k_lm_rowsign, dim3((M + 255) / 256), dim3(256), 0, st, target, denom, loss_scale, row_weight, fac, M);
+    return CC_OK;
+}
+// MODE 0: dhf = r dhf - w wte[t];  1: out = r hf;  2: io = r io (in place)
 template <int MODE>
 __global__ __launch_bounds__(256) void k_lm_rows(act_t* __restrict__ io, const act_t* __restrict__ hf, const float* __restrict__ fac,
                                                  const int* __restrict__ target, const op16_t* __restrict__ wte, int D, int M) {
@@ -233,7 +277,7 @@ __global__ __launch_bounds__(256) void k_lm_rows(act_t* __restrict__ io, const a
             for (int e = 0; e < 8; e++) v[e] = r * v[e] - w * b[e];
             act_st8(io + (size_t)row * D + c, v);
         } else {
-            act_ld8(hf + (size_t)row * D + c, v);
+            act_ld8((MODE == 2 ? io : hf) + (size_t)row * D + c, v);
 #pragma unroll
             for (int e = 0; e < 8; e++) v[e] *= r;
             act_st8(io + (size_t)row * D + c, v);
@@ -253,6 +297,9 @@ int lm_dgrad_fix(act_t* dhf, const float* fac, const int* target, const op16_t* 
 }
 int lm_scale_rows(const act_t* hf, const float* fac, act_t* out, int D, int M, hipStream_t st) {
     return lm_rows_launch<1>(out, hf, fac, nullptr, nullptr, D, M, st);
+}
+int lm_scale_rows_inplace(act_t* x, const float* fac, int D, int M, hipStream_t st) {
+    return lm_rows_launch<2>(x, nullptr, fac, nullptr, nullptr, D, M, st);
 }
 
 // Targets of the caption rows: target[b*cap + c] = max(tokens[b,c], 0) (model.py:103-104); row_map[b*cap+c] = b*T + L-1+c.

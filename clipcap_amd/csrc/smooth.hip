@@ -80,10 +80,11 @@ int smooth_wbar(const act_t* wte, int V, int D, float* part, float* wbar, hipStr
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 
-// one wave per row: zbar[row] = hf[row] . wbar, term[row] = kept ? eps (z_t - zbar) : 0
+// one wave per row: zbar[row] = hf[row] . wbar, term[row] = kept ? eps (z_t - zbar) : 0;  WT: the kept rows' terms times rw[row] (row_factor)
+template <bool WT>
 __global__ __launch_bounds__(256) void k_smooth_rows(const act_t* __restrict__ hf, const float* __restrict__ wbar, int D,
                                                      const int* __restrict__ target, const float* __restrict__ tgt, float eps,
-                                                     float* __restrict__ zbar, float* __restrict__ term, int M) {
+                                                     const float* __restrict__ rw, float* __restrict__ zbar, float* __restrict__ term, int M) {
     const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
     const act_t* h = hf + (size_t)row * D;
@@ -99,10 +100,12 @@ __global__ __launch_bounds__(256) void k_smooth_rows(const act_t* __restrict__ h
     acc = wave_sum(acc);
     if (lane == 0) {
         zbar[row] = acc;
-        term[row] = target[row] != 0 ? eps * (tgt[row] - acc) : 0.f;
+        term[row] = row_factor<WT>(target[row], eps * (tgt[row] - acc), rw, row);
     }
 }
-// one block, the order of k_ce_stats: stats3[2] = the plain sum ce_rows left in stats3[0], stats3[0] = that + the sum of the rows' terms
+// one block, the order of k_ce_stats: stats3[2] = the plain sum ce_rows left in stats3[0], stats3[0] = that + the sum of the rows' terms.
+// WT: ce_rows left the weighted sum in stats3[0] and the plain one in stats3[2] already, which stays.
+template <bool WT>
 __global__ __launch_bounds__(1024) void k_smooth_stats(const float* __restrict__ term, float* __restrict__ stats3, int M) {
     __shared__ float sl[16];
     float a = 0.f;
@@ -114,27 +117,33 @@ __global__ __launch_bounds__(1024) void k_smooth_stats(const float* __restrict__
         float ta = 0.f;
         for (int w = 0; w < 16; w++) ta += sl[w];
         const float nll = stats3[0];
-        stats3[2] = nll;
+        if (!WT) stats3[2] = nll;
         stats3[0] = nll + ta;
     }
 }
 int smooth_rows(const act_t* hf, const float* wbar, int D, const int* target, const float* tgt, float eps, float* zbar, float* term,
-                float* stats3, int M, hipStream_t st) {
+                float* stats3, int M, hipStream_t st, const float* row_weight) {
     if (D & 7) return CC_ERR_SHAPE;
-    if (M > 0) hipLaunchKernelGGL(k_smooth_rows, dim3((M + 3) / 4), dim3(256), 0, st, hf, wbar, D, target, tgt, eps, zbar, term, M);
-    hipLaunchKernelGGL(k_smooth_stats, dim3(1), dim3(1024), 0, st, term, stats3, std::max(M, 0));
+    if (row_weight) {
+        if (M > 0) hipLaunchKernelGGL(k_smooth_rows<true>, dim3((M + 3) / 4), dim3(256), 0, st, hf, wbar, D, target, tgt, eps, row_weight, zbar, term, M);
+        hipLaunchKernelGGL(k_smooth_stats<true>, dim3(1), dim3(1024), 0, st, term, stats3, std::max(M, 0));
+    } else {
+        if (M > 0) hipLaunchKernelGGL(k_smooth_rows<false>, dim3((M + 3) / 4), dim3(256), 0, st, hf, wbar, D, target, tgt, eps, nullptr, zbar, term, M);
+        hipLaunchKernelGGL(k_smooth_stats<false>, dim3(1), dim3(1024), 0, st, term, stats3, std::max(M, 0));
+    }
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }
 
 // coef[row] = {0, -c}: c = eps * loss_scale / max(denom, 1) on kept rows, 0 elsewhere — the {r, w} layout of lm_rowfac, so that
-// scatter_rows' act form adds value(row) = fl(c hf[row]) and leaves the rows with c == 0 out
+// scatter_rows' act form adds value(row) = fl(c hf[row]) and leaves the rows with c == 0 out.  WT: c times rw[row] (row_factor), of either sign
+template <bool WT>
 __global__ void k_smooth_coef(const int* __restrict__ target, const float* __restrict__ denom, const float* __restrict__ loss_scale, float eps,
-                              float* __restrict__ coef, int M) {
+                              const float* __restrict__ rw, float* __restrict__ coef, int M) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M) return;
     const float inv = (loss_scale ? loss_scale[0] : 1.0f) / fmaxf(denom[0], 1.0f);
     coef[2 * i] = 0.f;
-    coef[2 * i + 1] = target[i] != 0 ? -(eps * inv) : 0.f;
+    coef[2 * i + 1] = row_factor<WT>(target[i], -(eps * inv), rw, i);
 }
 // dhf[row][:] += c (wte[target[row]][:] - wbar[:]) in the stored type; rows with c == 0 are not touched
 __global__ __launch_bounds__(256) void k_smooth_dhf(act_t* __restrict__ dhf, const float* __restrict__ coef, const int* __restrict__ target,
@@ -156,10 +165,11 @@ __global__ __launch_bounds__(256) void k_smooth_dhf(act_t* __restrict__ dhf, con
     }
 }
 int smooth_dhf(act_t* dhf, const int* target, const float* denom, const float* loss_scale, float eps, const act_t* wte, const float* wbar,
-               float* coef, int D, int M, hipStream_t st) {
+               float* coef, int D, int M, hipStream_t st, const float* row_weight) {
     if (D & 7) return CC_ERR_SHAPE;
     if (M <= 0) return CC_OK;
-    hipLaunchKernelGGL(k_smooth_coef, dim3((M + 255) / 256), dim3(256), 0, st, target, denom, loss_scale, eps, coef, M);
+    if (row_weight) hipLaunchKernelGGL(k_smooth_coef<true>, dim3((M + 255) / 256), dim3(256), 0, st, target, denom, loss_scale, eps, row_weight, coef, M);
+    else hipLaunchKernelGGL(k_smooth_coef<false>, dim3((M + 255) / 256), dim3(256), 0, st, target, denom, loss_scale, eps, nullptr, coef, M);
     hipLaunchKernelGGL(k_smooth_dhf, flat_grid((size_t)M * (D >> 3), 256, 4096), dim3(256), 0, st, dhf, coef, target, wte, wbar, D, M);
     return hipGetLastError() == hipSuccess ? CC_OK : CC_ERR_LAUNCH;
 }

@@ -636,6 +636,18 @@ def ema_decay_at(decay: float, t: int, warmup: bool) -> float:
     return min(decay, (1.0 + t) / (10.0 + t)) if warmup else decay
 
 
+def check_token_weights(token_weights, shape, name: str = "token_weights") -> None:
+    """A per-token loss weight tensor is fp32 of ``shape``; ValueError otherwise.  Looks at the type, dtype and shape only: the values
+    stay on whatever device they are (no host sync), any finite value of either sign is allowed and the weight of an ignored position
+    is never used."""
+    if not isinstance(token_weights, torch.Tensor):
+        raise ValueError(f"{name} must be a torch.Tensor, got {type(token_weights).__name__}")
+    if token_weights.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32, got {token_weights.dtype}")
+    if tuple(token_weights.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(token_weights.shape)}")
+
+
 class ClipCapEngine:
     """Training step of ClipCapModel (reference model.py:94-113) as straight-line forward + backward kernel chains."""
 
@@ -705,7 +717,8 @@ class ClipCapEngine:
             sc.update()
 
     def forward_backward(self, tokens: torch.Tensor, embeds: torch.Tensor, reduce_stats=None, backward: bool = True,
-                         on_grads_ready=None, dropout=None, label_smoothing: float = 0.0) -> torch.Tensor:
+                         on_grads_ready=None, dropout=None, label_smoothing: float = 0.0,
+                         token_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         """tokens int64 (B,cap) padded with -1; embeds fp32 (B,E)/(B,W,E).
 
         Returns the mean loss over kept targets (device scalar).  Gradients are ACCUMULATED into the arenas' g32.
@@ -723,8 +736,15 @@ class ClipCapEngine:
         makes exactly the calls (and the 2-float stats) of a step without the option; a positive value goes through
         cc_lmhead_ce_fwd_smooth / cc_lmhead_ce_bwd_smooth with a 3-float stats [smoothed loss sum, kept count, plain NLL sum], returns
         the smoothed mean as torch does and leaves the mean plain NLL (what perplexity is made of) in ``last_nll``, a device scalar.
+        ``token_weights``: fp32 (B, cap), a weight per target token: loss = sum over kept targets of weight * row loss / the kept COUNT
+        (not the weight sum; under ``reduce_stats`` the global count).  Any finite value: negative (self-critical training), zero (the
+        token still counts), large; the weight of an ignored target (token 0 or the -1 padding) is never used, whatever its bits.  None
+        makes exactly the calls of a step without the option; a tensor goes through cc_lmhead_ce_fwd_w / cc_lmhead_ce_bwd_w (with
+        ``label_smoothing`` as their eps) and the 3-float stats; the returned loss is the weighted mean, ``last_nll`` the plain one.
         """
         eps = check_label_smoothing(label_smoothing)
+        if token_weights is not None:
+            check_token_weights(token_weights, tokens.shape)
         l = _lib.lib()
         g, m = self.gpt2, self.mapper
         dev = g.arena.device
@@ -740,7 +760,9 @@ class ClipCapEngine:
         st = _stream(dev)
         ga = g.arena
         prefix = m.forward(embeds, save=True)
-        return self._forward_backward(l, g, m, ga, shp, ws, st, prefix, tokens, reduce_stats, backward, on_grads_ready, dev, eps)
+        if token_weights is not None:
+            token_weights = token_weights.to(device=dev).contiguous()
+        return self._forward_backward(l, g, m, ga, shp, ws, st, prefix, tokens, reduce_stats, backward, on_grads_ready, dev, eps, token_weights)
 
     def _smooth_buffers(self, l, g, shp, dev) -> Tuple[torch.Tensor, torch.Tensor]:
         """(3-float stats, scratch) of the label-smoothed loss: the caller's buffers of cc_lmhead_ce_*_smooth, kept between steps"""
@@ -751,10 +773,14 @@ class ClipCapEngine:
             self.smooth_scratch = torch.empty(n, dtype=torch.float32, device=dev)
         return self.stats3, self.smooth_scratch
 
-    def _forward_backward(self, l, g, m, ga, shp, ws, st, prefix, tokens, reduce_stats, backward, on_grads_ready, dev, eps=0.0):
+    def _forward_backward(self, l, g, m, ga, shp, ws, st, prefix, tokens, reduce_stats, backward, on_grads_ready, dev, eps=0.0, rw=None):
         check(l.cc_gpt2_embed(C.byref(g.cfg), C.byref(shp), _p(ga.w32), _p(prefix), _p(tokens), _p(ws), st), "cc_gpt2_embed")
         check(l.cc_gpt2_fwd(C.byref(g.cfg), C.byref(shp), _p(ga.w32), _p(ga.w16), _p(ws), st), "cc_gpt2_fwd")
-        if eps > 0.0:
+        if rw is not None:
+            stats, scratch = self._smooth_buffers(l, g, shp, dev)
+            check(l.cc_lmhead_ce_fwd_w(C.byref(g.cfg), C.byref(shp), _p(ga.w32), _p(ga.w16), _p(ws), _p(tokens), _p(rw), eps, _p(scratch),
+                                       _p(stats), st), "cc_lmhead_ce_fwd_w")
+        elif eps > 0.0:
             stats, scratch = self._smooth_buffers(l, g, shp, dev)
             check(l.cc_lmhead_ce_fwd_smooth(C.byref(g.cfg), C.byref(shp), _p(ga.w32), _p(ga.w16), _p(ws), _p(tokens), eps, _p(scratch),
                                             _p(stats), st), "cc_lmhead_ce_fwd_smooth")
@@ -769,7 +795,10 @@ class ClipCapEngine:
             g32 = ga.grads() if self.train_lm else None
             denom = stats[1:2]
             sc = self._scaler(dev)
-            if eps > 0.0:
+            if rw is not None:
+                check(l.cc_lmhead_ce_bwd_w(C.byref(g.cfg), C.byref(shp), _p(ga.w32), _p(ga.w16), _p(ws), _p(denom),
+                                           _p(sc.scale) if sc is not None else None, _p(rw), eps, _p(scratch), _p(g32), st), "cc_lmhead_ce_bwd_w")
+            elif eps > 0.0:
                 check(l.cc_lmhead_ce_bwd_smooth(C.byref(g.cfg), C.byref(shp), _p(ga.w32), _p(ga.w16), _p(ws), _p(denom),
                                                 _p(sc.scale) if sc is not None else None, eps, _p(scratch), _p(g32), st), "cc_lmhead_ce_bwd_smooth")
             else:
@@ -790,7 +819,7 @@ class ClipCapEngine:
                     hi = lo
             m.backward(dprefix, on_layers_done=(None if on_grads_ready is None else (lambda lo, hi: on_grads_ready(0, lo, hi))))
         loss = stats[0] / stats[1].clamp_min(1.0)
-        self.last_nll = loss if eps == 0.0 else stats[2] / stats[1].clamp_min(1.0)
+        self.last_nll = loss if (eps == 0.0 and rw is None) else stats[2] / stats[1].clamp_min(1.0)
         return loss
 
     @torch.no_grad()

@@ -20,7 +20,7 @@ from typing import Optional, Tuple
 import torch
 import torch.nn as nn
 
-from clipcap_amd.engine import ClipCapEngine, check_ema_decay, check_label_smoothing, ema_decay_at
+from clipcap_amd.engine import ClipCapEngine, check_ema_decay, check_label_smoothing, check_token_weights, ema_decay_at
 from clipcap_amd.model.config import Config, TrainingConfig
 from clipcap_amd.model.gpt2 import GPT2LM
 from clipcap_amd.model.mapper import TransformerMapper, TransformerMapperWindowed
@@ -54,6 +54,24 @@ class _StepLoss(torch.autograd.Function):
             src = mg if owner == 0 else lg
             outs.append(src[name] * gout if name in src else None)
         return (None, None) + tuple(outs)
+
+
+def combine_loss_weights(tokens_shape, token_weights: Optional[torch.Tensor] = None,
+                         sample_weights: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """The (B, cap) fp32 weights of a weighted step from ``token_weights`` (B, cap) and / or ``sample_weights`` (B,), the latter
+    broadcast over the caption; both: their product; neither: None (a step without weights).  ValueError for a wrong type, dtype or
+    shape, raised from the shapes alone, before anything is computed: no value is looked at (no host sync)."""
+    B, cap = tokens_shape
+    if token_weights is not None:
+        check_token_weights(token_weights, (B, cap))
+    if sample_weights is not None:
+        check_token_weights(sample_weights, (B,), name="sample_weights")
+    if sample_weights is None:
+        return token_weights
+    per_sample = sample_weights.reshape(B, 1)
+    if token_weights is None:
+        return per_sample.expand(B, cap).contiguous()
+    return token_weights * per_sample.to(token_weights.device)
 
 
 class ClipCapModel(nn.Module):
@@ -112,26 +130,34 @@ class ClipCapModel(nn.Module):
         return ps + (int(torch.randint(0, 2 ** 48, (1,)).item()) ^ (rank << 50),)
 
     def fused_step(self, batch: Tuple[torch.Tensor, torch.Tensor], lr: float, reducer=None, max_grad_norm: Optional[float] = None,
-                   label_smoothing: Optional[float] = None, ema_decay: Optional[float] = None) -> torch.Tensor:
+                   label_smoothing: Optional[float] = None, ema_decay: Optional[float] = None,
+                   token_weights: Optional[torch.Tensor] = None, sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One optimizer step: zero grads -> forward+backward kernel chains -> (all-reduce) -> fused AdamW. Returns the loss.
         ``max_grad_norm``: global gradient-norm clipping on the device (Lightning's gradient_clip_val; inf: only report the norm);
         the norm of this step's gradients is then ``last_grad_norm``.
         ``label_smoothing``: eps of F.cross_entropy(..., label_smoothing=eps) for this step (None: the ``label_smoothing`` attribute);
         the returned loss is the smoothed one, ``last_nll`` the plain mean NLL.
         ``ema_decay``: decay of the weight average for this step (None: the ``ema_decay`` attribute; both None: no average, and the
-        step launches what it always did).  With ``ema_warmup`` the step uses min(decay, (1 + t) / (10 + t)), t = this step's number."""
+        step launches what it always did).  With ``ema_warmup`` the step uses min(decay, (1 + t) / (10 + t)), t = this step's number.
+        ``token_weights`` fp32 (B, cap) / ``sample_weights`` fp32 (B,), broadcast over the caption; both: their product: a weight per
+        target token, loss = sum over kept targets of weight * row loss / the kept COUNT (scale the weights first for any other
+        normalisation).  Any finite value of either sign (``self_critical_step`` passes the advantage); the weight of an ignored target
+        is never used.  The returned loss is the weighted mean, ``last_nll`` the plain mean NLL.  Both None: the step it always was."""
         tokens, embeds = batch
         eps = check_label_smoothing(self.label_smoothing if label_smoothing is None else label_smoothing)
         decay = check_ema_decay(getattr(self, "ema_decay", None) if ema_decay is None else ema_decay)
+        wkw = {}
+        if token_weights is not None or sample_weights is not None:
+            wkw["token_weights"] = combine_loss_weights(tokens.shape, token_weights, sample_weights)
         eng = self.engine
         eng.zero_grad()
         if reducer is not None:
             reducer.begin()
             loss = eng.forward_backward(tokens, embeds, reduce_stats=reducer.reduce_stats, on_grads_ready=reducer.on_grads_ready,
-                                        dropout=self._dropout(), label_smoothing=eps)
+                                        dropout=self._dropout(), label_smoothing=eps, **wkw)
             reducer.finish()
         else:
-            loss = eng.forward_backward(tokens, embeds, dropout=self._dropout(), label_smoothing=eps)
+            loss = eng.forward_backward(tokens, embeds, dropout=self._dropout(), label_smoothing=eps, **wkw)
         self._opt_step += 1
         # partitioned gradients (ZeRO stage 2): a rank holds the reduced sum of its own slices only, so the squared norms are summed
         partitioned = reducer is not None and reducer.owners is not None

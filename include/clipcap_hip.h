@@ -69,7 +69,8 @@ extern "C" {
  * cc_grad_norm_scratch_floats, cc_grad_sqnorm, cc_grad_clip_coef, cc_adamw_step_clip, cc_logits_constrain, cc_beam_group_step,
  * cc_beam_group_ws_bytes, cc_decode_hidden_unit, cc_contrastive_topk, cc_contrastive_select, the decode-attention test hook
  * cc_decode_attention, and the label-smoothed loss cc_lmhead_smooth_scratch_floats, cc_lmhead_ce_fwd_smooth, cc_lmhead_ce_bwd_smooth,
- * the weight-averaging optimizer step cc_adamw_step_ema, and the decode-time guidance cc_logits_guide. */
+ * the weight-averaging optimizer step cc_adamw_step_ema, the decode-time guidance cc_logits_guide, and the loss with per-token weights
+ * cc_lmhead_ce_fwd_w, cc_lmhead_ce_bwd_w. */
 #define CC_ABI_VERSION 3
 int cc_abi_version(void);
 
@@ -230,6 +231,29 @@ int cc_lmhead_ce_fwd_smooth(const cc_gpt2_cfg* cfg, const cc_gpt2_shape* shp, co
                             const int64_t* tokens, float eps, float* scratch, float* stats3, void* stream);
 int cc_lmhead_ce_bwd_smooth(const cc_gpt2_cfg* cfg, const cc_gpt2_shape* shp, const float* w32, const uint16_t* w16, void* ws,
                             const float* denom, const float* loss_scale, float eps, float* scratch, float* g32, void* stream);
+/* The same loss with a weight per target token (and label smoothing eps, which may be 0):
+ *   loss = (1 / max(n, 1)) * sum over kept rows m of row_weight[m] * loss_row(eps)[m],   n = the kept rows (target != 0), NOT the sum of
+ *   the weights: a caller who wants that normalisation scales the weights first.  Any finite fp32 weight: negative (the REINFORCE term
+ *   of self-critical training, weight = reward(sample) - reward(greedy)), zero (the row still counts in n), large.  Every gradient of the
+ *   pass is that of this loss: the row factor loss_scale / max(denom, 1) of a kept row is multiplied by row_weight[m] where d logits (or,
+ *   in the exponential form, the pair {r, w}) is formed, and c of the smoothing corrections becomes row_weight[m] * eps * loss_scale /
+ *   max(denom, 1); everything after that (the input-gradient GEMM and its fix, the tied weight gradient, its scatters, ln_f) is the
+ *   plain chain's code.  Where d logits itself is formed (fp16; split-bf16 mode 2) it carries the factor's magnitude and the sign is put
+ *   onto the rows of d hf and of the weight-gradient operand: negating a weight negates its row's gradient bit for bit.  The weight of a row that is not kept is never used in arithmetic (selected away, not multiplied by 0): NaN or inf
+ *   there reaches no output.
+ * row_weight: device fp32 [B * cap], row-major like tokens; non-NULL; hand both calls of a pass the same values.  scratch: as for the
+ * smoothing pair (cc_lmhead_smooth_scratch_floats, 16-byte aligned, the same buffer in both calls); may be NULL only when eps == 0, and
+ * with eps == 0 no smoothing launch happens.  stats3 (3 device floats, fully written): [0] the weighted (smoothed) loss sum, [1] kept
+ * rows, [2] the plain unweighted NLL sum = what cc_lmhead_ce_fwd puts in stats[0], bit for bit.  denom = stats3 + 1 (or its all-reduced
+ * copy).  With every weight 1.0f the outputs are those of cc_lmhead_ce_fwd / _bwd (eps == 0) or of the smoothing pair, bit for bit.
+ * Every sum runs in a fixed order (no atomics): a mode-2 step is bit-reproducible from run to run.  CC_ERR_ARG with nothing written: a
+ * NULL row_weight, eps < 0, eps >= 1 or NaN, a NULL scratch with eps != 0, a misaligned scratch, mode 0, and whatever the plain entry
+ * points refuse.  CC_LM_ROW_LOSS (cc_lmhead_get) stays the plain row loss. */
+int cc_lmhead_ce_fwd_w(const cc_gpt2_cfg* cfg, const cc_gpt2_shape* shp, const float* w32, const uint16_t* w16, void* ws,
+                       const int64_t* tokens, const float* row_weight, float eps, float* scratch, float* stats3, void* stream);
+int cc_lmhead_ce_bwd_w(const cc_gpt2_cfg* cfg, const cc_gpt2_shape* shp, const float* w32, const uint16_t* w16, void* ws,
+                       const float* denom, const float* loss_scale, const float* row_weight, float eps, float* scratch, float* g32,
+                       void* stream);
 /* backward through the blocks.  dprefix fp32 [B, L, D] receives d loss / d prefix (rows 0..L-1 of d x0).
  * mode 2 additionally accumulates all GPT-2 weight gradients (incl. wte/wpe) into g32. */
 int cc_gpt2_bwd(const cc_gpt2_cfg* cfg, const cc_gpt2_shape* shp, const float* w32, const uint16_t* w16, void* ws,
