@@ -114,6 +114,7 @@ SIGNATURES = {
     "cc_beam_group_step": (_I, [_I, _I, _I, _I, _P, _L, _F, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cc_logits_constrain": (_I, [_P, _I, _I, _L, _P, _I, _P, _I, _L, _I, _I, _I, _P, _I, _P, _P]),
     "cc_logits_guide": (_I, [_P, _L, _P, _L, _I, _I, _F, _P, _L, _P, _P]),
+    "cc_logits_truncate": (_I, [_P, _I, _I, _L, _F, _P, _I, _I, _F, _F, _F, _F, _F, _P]),
     "cc_decode_hidden_unit": (_I, [_GC, _I, _I, _P, _P, _P, _L, _L, _P]),
     "cc_contrastive_topk": (_I, [_P, _L, _I, _I, _P, _I, _I, _P, _P, _P, _P]),
     "cc_contrastive_select": (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P]),

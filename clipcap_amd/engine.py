@@ -1159,6 +1159,40 @@ def guide_logits(cond: torch.Tensor, uncond: torch.Tensor, scale: float, *, out:
     return dst
 
 
+def truncate_logits(logits: torch.Tensor, *, temperature: float = 1.0, history: Optional[torch.Tensor] = None, hist_len: int = 0,
+                    repetition_penalty: float = 1.0, min_p: float = 0.0, typical_p: float = 1.0, epsilon_cutoff: float = 0.0,
+                    eta_cutoff: float = 0.0) -> torch.Tensor:
+    """The truncation rules of the sampling decoders on one step's fp32 ``logits`` (R, V), IN PLACE, after the guidance and the bans and
+    immediately before sample_step, called with the same ``temperature``, ``history`` (int64 (R, >= hist_len)), ``hist_len`` and
+    ``repetition_penalty`` (cc_logits_truncate, one launch): the rules act on the values the sampler draws from.  A token is kept iff every
+    rule that is on keeps it — min_p > 0: p >= min_p * p_max; epsilon_cutoff > 0: p >= epsilon; eta_cutoff > 0: p >= min(eta,
+    sqrt(eta) * exp(-entropy)); typical_p < 1: the tokens closest in -log p to the entropy whose mass reaches typical_p, ties kept — every
+    rule taken against the same incoming distribution (with one rule on, what the corresponding transformers warper keeps; transformers
+    renormalises between several, this does not).  An empty intersection keeps the most probable tokens.  The raw logit of a removed token
+    becomes -inf, kept ones stay bit-untouched; sample_step then applies its own top-k / top-p to the truncated row, so its mode-0 top_p
+    mass is relative to that row.  With all four off (0, 1, 0, 0) nothing is launched.  A view with a row stride is fine.  ValueError for
+    an option outside its range (inference.utils.validate_truncation).  Returns ``logits``."""
+    from clipcap_amd.inference.utils import truncation_is_on, validate_truncation
+    opts = validate_truncation(min_p, typical_p, epsilon_cutoff, eta_cutoff)
+    assert logits.dtype == torch.float32 and logits.dim() == 2
+    R, V = logits.shape
+    assert V >= 1 and (V == 1 or logits.stride(1) == 1)
+    hist_len = int(hist_len)
+    if hist_len < 0 or (hist_len > 0 and history is None):
+        raise ValueError(f"hist_len = {hist_len} needs a history of at least that many columns")
+    if history is not None:
+        assert history.dtype == torch.int64 and history.dim() == 2 and history.shape[0] == R and history.device == logits.device
+        assert history.shape[1] >= hist_len and (history.shape[1] <= 1 or history.stride(1) == 1)
+    if not truncation_is_on(opts) or R == 0:
+        return logits
+    ld = logits.stride(0) if R > 1 else max(logits.stride(0), V)
+    hld = 0 if history is None else (history.stride(0) if R > 1 else max(history.stride(0), hist_len))
+    check(_lib.lib().cc_logits_truncate(_p(logits), R, V, ld, float(temperature), _p(history) if history is not None else None, hist_len, hld,
+                                       float(repetition_penalty), opts["min_p"], opts["typical_p"], opts["epsilon_cutoff"], opts["eta_cutoff"],
+                                       _stream(logits.device)), "cc_logits_truncate")
+    return logits
+
+
 def contrastive_buffers(device, S: int, k: int, D: int, ctx_max: int, entry_length: int):
     """The device state of ONE contrastive-search decode of S captions with k candidates each (never shared between decodes, streams or
     threads), as a namespace: cand_tok int32 (S*k,), cand_prob fp32 (S*k,), cand_h fp32 (S*k, D) — the candidates of the step;

@@ -45,7 +45,8 @@ from clipcap_amd import engine
 from clipcap_amd.engine import (DecodeSession, beam_buffers, beam_group_buffers, beam_group_step, beam_step, constrain_logits, embed_tokens,
                                 sample_step)
 from clipcap_amd.inference.utils import (nucleus_distribution, repetition_penalty_apply, sentence_length_penalty_apply,  # noqa: F401
-                                         top_k_top_p_filtering, validate_beam_groups, validate_constraints, validate_guidance)
+                                         top_k_top_p_filtering, truncation_is_on, validate_beam_groups, validate_constraints,
+                                         validate_guidance, validate_truncation)
 
 
 def _persistent_decode_on() -> bool:
@@ -266,7 +267,8 @@ def sample_tokens(model, embeds: torch.Tensor, entry_length: int = 67, stop_toke
                   top_k: Optional[int] = None, temperature: float = 1.0, repetition_penalty: float = 1.0,
                   generator: Optional[torch.Generator] = None, head_tokens: Optional[torch.Tensor] = None,
                   desired_sentence_length: Optional[int] = None, sentence_length_factor: float = 1.0, no_repeat_ngram_size: int = 0,
-                  min_length: int = 0, suppress_tokens=None, guidance_scale: float = 1.0,
+                  min_length: int = 0, suppress_tokens=None, min_p: float = 0.0, typical_p: float = 1.0, epsilon_cutoff: float = 0.0,
+                  eta_cutoff: float = 0.0, guidance_scale: float = 1.0,
                   negative_embeds: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """KV-cached sampling for a batch of prefixes, every step on the device (cc_decode_fwd + cc_sample_step, no host sync except
     an all-rows-stopped poll every 4th step).  embeds fp32 (R, L, D).  mode 0 = the nucleus rule of generate_nucleus_sampling
@@ -281,7 +283,14 @@ def sample_tokens(model, embeds: torch.Tensor, entry_length: int = 67, stop_toke
     ``guidance_scale`` != 1 with ``negative_embeds`` (R, Ln, D) or (1, Ln, D) (module docstring; needed here): a second session of R rows is
     prefilled with the negative context and fed the same token embeddings; every step's logits are replaced by the guided scores
     (cc_logits_guide) before the bans and the sampling step.
+    ``min_p`` / ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff`` (off at 0 / 1 / 0 / 0; engine.truncate_logits, cc_logits_truncate): the
+    truncation rules, applied after the guidance and the bans and immediately before the sampling step, on the values it draws from (same
+    temperature, history and repetition penalty).  The kept set is the intersection of the rules that are on, all taken against the same
+    incoming distribution (transformers renormalises between several rules, this does not); the sampling step's own top_k / top_p then
+    act on the truncated row, so the mode-0 ``top_p`` mass is relative to it.  With all four off no launch is made.
     Returns (tokens int64 (R, n), stop_pos int64 (R,)): stop_pos[r] = index of the first stop token of row r (n if none)."""
+    trunc = validate_truncation(min_p, typical_p, epsilon_cutoff, eta_cutoff)
+    trunc_on = truncation_is_on(trunc)
     lm = model.language_model
     g = lm.engine
     dev = g.arena.device
@@ -305,6 +314,9 @@ def sample_tokens(model, embeds: torch.Tensor, entry_length: int = 67, stop_toke
             engine.guide_logits(logits, usess.forward(neg if step == 0 else x), gs)
         if bans is not None:
             bans.apply(logits, step, hist, H0 + step)
+        if trunc_on:                                                                 # on the values sample_step draws from
+            engine.truncate_logits(logits, temperature=temperature, history=hist, hist_len=H0 + step, repetition_penalty=repetition_penalty,
+                                   **trunc)
         u = torch.rand(R, device=dev, generator=generator)
         nxt = sample_step(logits, u, temperature=temperature, top_k=top_k or 0, top_p=top_p, mode=mode, history=hist, hist_len=H0 + step,
                           repetition_penalty=repetition_penalty,
@@ -334,7 +346,8 @@ def _negative_rows_for(negative_embeds: Optional[torch.Tensor], number_to_genera
 def generate_nucleus_sampling(model, tokenizer: Callable, embeds: torch.Tensor, number_to_generate: int = 1,
                               text_prefix_tokens: Optional[torch.Tensor] = None, entry_length: int = 67, top_p: float = 0.8, top_k=None,
                               temperature: float = 1.0, generator: Optional[torch.Generator] = None, rerank: bool = False, *,
-                              no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None, guidance_scale: float = 1.0,
+                              no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None, min_p: float = 0.0,
+                              typical_p: float = 1.0, epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0, guidance_scale: float = 1.0,
                               negative_embeds: Optional[torch.Tensor] = None) -> List[str]:
     """base.py:135-201 with a KV cache and the sampling step on the device.  The reference is batch-1 and loops number_to_generate
     times; here every (prefix row, repetition) is one row of a single batched decode.  The returned text of a row includes its
@@ -342,13 +355,16 @@ def generate_nucleus_sampling(model, tokenizer: Callable, embeds: torch.Tensor, 
     ``rerank`` (not in the reference; off by default): the ``number_to_generate`` texts of every prefix row come back ordered by their
     length-normalised likelihood under the model, best first (inference/score.py rerank_captions), instead of in sampling order.
     ``guidance_scale`` != 1 (module docstring): ``negative_embeds`` None = the embedding of tokenizer.bos_token; the text prefix follows it.
-    Guidance shapes what is sampled; ``rerank`` keeps ranking by the UNGUIDED likelihood, the model's own p(caption | prefix)."""
+    Guidance shapes what is sampled; ``rerank`` keeps ranking by the UNGUIDED likelihood, the model's own p(caption | prefix).
+    ``min_p`` / ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff``: the truncation rules of sample_tokens (off by default); ``top_p`` is
+    then a mass of the truncated row."""
     stop = _stop_id(tokenizer)
     negative_embeds = _negative_context(model, tokenizer, negative_embeds, text_prefix_tokens, guidance_scale)
     embeds = _with_text_prefix(model, embeds, text_prefix_tokens)
     toks, stop_pos = sample_tokens(model, _rows_for(embeds, number_to_generate), entry_length, stop, mode=0, top_p=top_p, top_k=top_k,
                                    temperature=temperature, generator=generator, no_repeat_ngram_size=no_repeat_ngram_size,
-                                   min_length=min_length, suppress_tokens=suppress_tokens, guidance_scale=guidance_scale,
+                                   min_length=min_length, suppress_tokens=suppress_tokens, min_p=min_p, typical_p=typical_p,
+                                   epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, guidance_scale=guidance_scale,
                                    negative_embeds=_negative_rows_for(negative_embeds, number_to_generate))
     rows = list(range(toks.shape[0]))
     if rerank and number_to_generate > 1:
@@ -373,13 +389,16 @@ def generate_no_beam(model, tokenizer: Callable, embeds: torch.Tensor, text_pref
                      top_p: float = 0.9, top_k: float = 0.0, entry_length: int = 67, temperature: float = 1.0,
                      repetition_penalty: float = 1.2, desired_sentence_length: int = 50, sentence_length_factor: float = 1.0,
                      sweep: bool = True, generator: Optional[torch.Generator] = None, *, no_repeat_ngram_size: int = 0, min_length: int = 0,
-                     suppress_tokens=None, guidance_scale: float = 1.0, negative_embeds: Optional[torch.Tensor] = None) -> List[str]:
+                     suppress_tokens=None, min_p: float = 0.0, typical_p: float = 1.0, epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0,
+                     guidance_scale: float = 1.0, negative_embeds: Optional[torch.Tensor] = None) -> List[str]:
     """base.py:204-279: the reference's debugging sweep over top_p x temperature (sweep=True reproduces it; sweep=False samples
     once with the given top_p / temperature).  Like the reference, ``repetition_penalty`` is accepted but not applied (its call is
     commented out, base.py:236-239).  The sentence-length penalty (base.py:248-254) is applied as the reference applies it: after the
     filter, history tokens whose VALUE equals the stop token id (utils.py:45 compares values, not ids) are scaled — on the device,
     inside the sampling step.  The text of a row excludes its stop token (the reference breaks before appending, base.py:261-262).
-    ``guidance_scale`` != 1 (module docstring): ``negative_embeds`` None = the embedding of tokenizer.bos_token; the text prefix follows it."""
+    ``guidance_scale`` != 1 (module docstring): ``negative_embeds`` None = the embedding of tokenizer.bos_token; the text prefix follows it.
+    ``min_p`` / ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff``: the truncation rules of sample_tokens (off by default), like the
+    sampling step here without a repetition penalty; the filter's top_k / top_p then act on the truncated row."""
     stop = _stop_id(tokenizer)
     negative_embeds = _negative_context(model, tokenizer, negative_embeds, text_prefix_tokens, guidance_scale)
     embeds = _with_text_prefix(model, embeds, text_prefix_tokens)
@@ -391,7 +410,8 @@ def generate_no_beam(model, tokenizer: Callable, embeds: torch.Tensor, text_pref
         toks, stop_pos = sample_tokens(model, embeds, entry_length, stop, mode=1, top_p=p, top_k=int(top_k), temperature=t, generator=generator,
                                        head_tokens=text_prefix_tokens, desired_sentence_length=desired_sentence_length,
                                        sentence_length_factor=sentence_length_factor, no_repeat_ngram_size=no_repeat_ngram_size,
-                                       min_length=min_length, suppress_tokens=suppress_tokens, guidance_scale=guidance_scale,
+                                       min_length=min_length, suppress_tokens=suppress_tokens, min_p=min_p, typical_p=typical_p,
+                                       epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, guidance_scale=guidance_scale,
                                        negative_embeds=negative_embeds)
         toks, stop_pos = toks.cpu(), stop_pos.cpu()
         gens.extend(tokenizer.decode(head + toks[r, :int(stop_pos[r])].tolist()) for r in range(toks.shape[0]))

@@ -11,6 +11,7 @@ from clipcap_amd.inference.no_beam import generate_no_beam
 def generate(model, tokenizer: Callable, embeddings: torch.Tensor, top_p: float = 0.95, top_k: int = 0, temperature: float = 1.0,
              number_to_generate: int = 5, text_prefix: Optional[str] = None, stop_token: Optional[str] = None,
              generator: Optional[torch.Generator] = None, *, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None,
+             min_p: float = 0.0, typical_p: float = 1.0, epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0,
              guidance_scale: float = 1.0, negative_embeds: Optional[torch.Tensor] = None):
     batch_size = embeddings.shape[0]
     assert batch_size == 1, "Batch size > 1 support coming soon - for now leave embeddings.shape[0] as 1."   # generate.py:19-20
@@ -24,5 +25,5 @@ def generate(model, tokenizer: Callable, embeddings: torch.Tensor, top_p: float 
     # the language model sees [prefix ; bos+text ; bos+text ; generated...]
     return generate_no_beam(model, tokenizer, inputs_embeds, number_to_generate=number_to_generate, text_prefix_tokens=text_prefix_tokens,
                             top_p=top_p, top_k=top_k, temperature=temperature, generator=generator, no_repeat_ngram_size=no_repeat_ngram_size,
-                            min_length=min_length, suppress_tokens=suppress_tokens, guidance_scale=guidance_scale,
-                            negative_embeds=negative_embeds)
+                            min_length=min_length, suppress_tokens=suppress_tokens, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff,
+                            eta_cutoff=eta_cutoff, guidance_scale=guidance_scale, negative_embeds=negative_embeds)

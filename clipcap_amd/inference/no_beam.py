@@ -14,6 +14,8 @@ Not in the reference: the keyword-only constraints ``no_repeat_ngram_size`` / ``
 (off by default), applied to the logits before everything above; their history is ``tokens`` too, and "stop" is the token of ``"."``.
 Nor is classifier-free guidance, ``guidance_scale`` / ``negative_embeds`` of inference/base.py (off by default): the guided scores replace
 the logits before the bans; ``negative_embeds`` None = the embedding of tokenizer.bos_token, followed by the text prefix.
+Nor are the truncation rules ``min_p`` / ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff`` of inference/base.py sample_tokens (off by
+default): after the bans, on the penalised and tempered values the sampling step draws from; top-k / top-p then act on the truncated row.
 
 Device path: one KV-cached batched decode (cc_decode_fwd) with all ``number_to_generate`` repetitions as rows, the whole
 per-step rule (penalties with a history bitmap, temperature, filter, softmax, draw) in cc_sample_step_lp.
@@ -31,8 +33,8 @@ def generate_no_beam(model, tokenizer: Callable, embeds: torch.Tensor, number_to
                      text_prefix_tokens: Optional[torch.Tensor] = None, top_p: float = 0.9, top_k: float = 0.0, entry_length: int = 67,
                      temperature: float = 1.0, repetition_penalty: float = 1.2, desired_sentence_length: int = 50,
                      sentence_length_factor: float = 1.0, generator: Optional[torch.Generator] = None, *, no_repeat_ngram_size: int = 0,
-                     min_length: int = 0, suppress_tokens=None, guidance_scale: float = 1.0,
-                     negative_embeds: Optional[torch.Tensor] = None) -> List[str]:
+                     min_length: int = 0, suppress_tokens=None, min_p: float = 0.0, typical_p: float = 1.0, epsilon_cutoff: float = 0.0,
+                     eta_cutoff: float = 0.0, guidance_scale: float = 1.0, negative_embeds: Optional[torch.Tensor] = None) -> List[str]:
     stop = tokenizer.encode(".")[0]                                                   # no_beam.py:24
     negative_embeds = _negative_context(model, tokenizer, negative_embeds, text_prefix_tokens, guidance_scale)
     embeds = _with_text_prefix(model, embeds, text_prefix_tokens)                     # no_beam.py:28-30
@@ -41,6 +43,7 @@ def generate_no_beam(model, tokenizer: Callable, embeds: torch.Tensor, number_to
                                    repetition_penalty=repetition_penalty, generator=generator, head_tokens=text_prefix_tokens,
                                    desired_sentence_length=desired_sentence_length, sentence_length_factor=sentence_length_factor,
                                    no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, suppress_tokens=suppress_tokens,
+                                   min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff,
                                    guidance_scale=guidance_scale, negative_embeds=_negative_rows_for(negative_embeds, number_to_generate))
     head = [] if text_prefix_tokens is None else [int(v) for v in text_prefix_tokens.flatten()]
     toks, stop_pos = toks.cpu(), stop_pos.cpu()

@@ -156,3 +156,28 @@ def validate_contrastive(top_k: int, penalty_alpha: float) -> None:
         raise ValueError(f"penalty_alpha must be a number in [0, 1], got {penalty_alpha!r}") from None
     if not math.isfinite(a) or not 0.0 <= a <= 1.0:
         raise ValueError(f"penalty_alpha must be finite and in [0, 1], got {penalty_alpha!r}")
+
+
+# ---- truncation rules of the sampling decoders (not in the reference: min_p / typical_p / epsilon_cutoff / eta_cutoff) ------------------
+
+def validate_truncation(min_p: float = 0.0, typical_p: float = 1.0, epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0) -> dict:
+    """Checks the four truncation options of the sampling decoders and returns them as a dict of floats, keyed as engine.truncate_logits
+    takes them.  ValueError unless min_p is in [0, 1] (0: off), typical_p in (0, 1] (1: off), epsilon_cutoff and eta_cutoff in [0, 1)
+    (0: off); NaN and non-numbers are refused.  Pure: touches no device."""
+    out = {}
+    for name, val, ok, rng in (("min_p", min_p, lambda a: 0.0 <= a <= 1.0, "[0, 1]"), ("typical_p", typical_p, lambda a: 0.0 < a <= 1.0, "(0, 1]"),
+                               ("epsilon_cutoff", epsilon_cutoff, lambda a: 0.0 <= a < 1.0, "[0, 1)"),
+                               ("eta_cutoff", eta_cutoff, lambda a: 0.0 <= a < 1.0, "[0, 1)")):
+        try:
+            a = float(val)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a number in {rng}, got {val!r}") from None
+        if isinstance(val, bool) or not ok(a):                  # NaN fails every comparison
+            raise ValueError(f"{name} must be in {rng}, got {val!r}")
+        out[name] = a
+    return out
+
+
+def truncation_is_on(opts: dict) -> bool:
+    """whether any rule of a validate_truncation result does anything"""
+    return opts["min_p"] > 0.0 or opts["typical_p"] < 1.0 or opts["epsilon_cutoff"] > 0.0 or opts["eta_cutoff"] > 0.0

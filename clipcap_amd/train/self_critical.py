@@ -29,11 +29,13 @@ def scst_tokens_and_weights(sampled: torch.Tensor, advantage: torch.Tensor, stop
 
 def self_critical_step(model, batch_embeds: torch.Tensor, reward_fn: Callable, lr: float, *, temperature: float = 1.0,
                        top_k: Optional[int] = None, top_p: float = 1.0, entry_length: int = 67, stop_token: int = 50256,
-                       generator: Optional[torch.Generator] = None, **fused_step_kw) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                       generator: Optional[torch.Generator] = None, min_p: float = 0.0, typical_p: float = 1.0, epsilon_cutoff: float = 0.0,
+                       eta_cutoff: float = 0.0, **fused_step_kw) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """One self-critical optimizer step on ``batch_embeds`` (the encoder embeddings ``fused_step`` takes).
 
     1. prefix = mapper(batch_embeds);  2. one SAMPLED caption per row (``sample_tokens`` with ``temperature`` / ``top_k`` / ``top_p`` /
-    ``generator``);  3. one GREEDY caption per row (the same function at its deterministic setting, top_k = 1);
+    ``generator``, and the truncation rules ``min_p`` / ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff`` of ``sample_tokens``, off by
+    default: they cut the tail whose advantage is noise and go to the SAMPLED decode only);  3. one GREEDY caption per row (the same function at its deterministic setting, top_k = 1);
     4. ``reward_fn(sampled, greedy)`` -> two (B,) tensors, the rewards of the sampled and of the greedy captions.  It gets token ids,
     int64 (B, n_s) and (B, n_g), each row valid up to and including its first ``stop_token``;  5. advantage A = r_sample - r_greedy;
     6. the loss's tokens = the sampled caption up to and including its stop token, -1 after it;  7. ``fused_step`` with the advantage
@@ -50,7 +52,8 @@ def self_critical_step(model, batch_embeds: torch.Tensor, reward_fn: Callable, l
     with torch.no_grad():
         prefix = eng.mapper.forward(batch_embeds, save=False)
         common = dict(entry_length=entry_length, stop_token=stop_token, suppress_tokens=[0])
-        sampled, _ = sample_tokens(model, prefix, mode=0, top_p=top_p, top_k=top_k, temperature=temperature, generator=generator, **common)
+        sampled, _ = sample_tokens(model, prefix, mode=0, top_p=top_p, top_k=top_k, temperature=temperature, generator=generator,
+                                   min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, **common)
         greedy, _ = sample_tokens(model, prefix, mode=0, top_p=1.0, top_k=1, temperature=1.0, **common)
         r_sample, r_greedy = reward_fn(sampled, greedy)
         r_sample = torch.as_tensor(r_sample, dtype=torch.float32, device=sampled.device)

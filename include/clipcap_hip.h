@@ -69,8 +69,8 @@ extern "C" {
  * cc_grad_norm_scratch_floats, cc_grad_sqnorm, cc_grad_clip_coef, cc_adamw_step_clip, cc_logits_constrain, cc_beam_group_step,
  * cc_beam_group_ws_bytes, cc_decode_hidden_unit, cc_contrastive_topk, cc_contrastive_select, the decode-attention test hook
  * cc_decode_attention, and the label-smoothed loss cc_lmhead_smooth_scratch_floats, cc_lmhead_ce_fwd_smooth, cc_lmhead_ce_bwd_smooth,
- * the weight-averaging optimizer step cc_adamw_step_ema, the decode-time guidance cc_logits_guide, and the loss with per-token weights
- * cc_lmhead_ce_fwd_w, cc_lmhead_ce_bwd_w. */
+ * the weight-averaging optimizer step cc_adamw_step_ema, the decode-time guidance cc_logits_guide, the loss with per-token weights
+ * cc_lmhead_ce_fwd_w, cc_lmhead_ce_bwd_w, and the sampling truncation rules cc_logits_truncate. */
 #define CC_ABI_VERSION 3
 int cc_abi_version(void);
 
@@ -364,6 +364,38 @@ int cc_logits_constrain(float* logits, int32_t R, int32_t V, int64_t ldl, float*
  * scale not finite or < 0, cond or uncond NULL with R > 0.  CC_ERR_SHAPE: V > 2^30. */
 int cc_logits_guide(const float* cond, int64_t ld_c, const float* uncond, int64_t ld_u, int32_t R, int32_t V, float scale, float* out,
                     int64_t ld_o, const uint8_t* skip_rows, void* stream);
+/* Truncation rules for the sampling decoders (since 3, added without a version bump; not in the reference): min-p (Nguyen et al., 2024),
+ * the epsilon and eta cutoffs (Hewitt et al., 2022, "Truncation sampling as language model desmoothing") and locally typical sampling
+ * (Meister et al., 2022) on one step's logits [R][ldl], in place, AFTER the guidance and the token bans and immediately BEFORE
+ * cc_sample_step / cc_sample_step_lp, called with the same temperature, history, hist_len, hist_ld and repetition_penalty.  The rules act
+ * on exactly the values the sampler draws from: v_i = fl32(pen(x_i) * fl32(1 / T)), the repetition penalty applied once to every id of
+ * history[r * hist_ld + 0 .. hist_len) that lies in [0, V), before the temperature (temperature <= 0 is taken as 1; no penalty with
+ * hist_len == 0, a NULL history or repetition_penalty == 1).  Per row, over the V real columns, with m = max v, lse = log sum exp(v_i)
+ * (max-subtracted; -inf adds nothing), p_i = exp(v_i - lse), H = -sum over p_i > 0 of p_i (v_i - lse) in nats, token i is kept iff
+ *     min_p > 0           v_i >= m + ln(min_p)                                      (p_i >= min_p * p_max)
+ *     epsilon_cutoff > 0  v_i >= lse + ln(epsilon_cutoff)                           (p_i >= epsilon)
+ *     eta_cutoff > 0      v_i >= lse + min(ln eta, 0.5 ln eta - H)                  (p_i >= min(eta, sqrt(eta) e^-H))
+ *     typical_p < 1       d_i <= d*, d_i = |lse - v_i - H| (+inf for v_i = -inf); with the tokens ordered by d ascending, d* is the d of
+ *                         the first token at which the cumulative p reaches >= typical_p (never: the last finite d); ties at d* are kept
+ *   for every rule that is on (off values: 0, 0, 0, 1).  The kept set is the intersection, every rule taken against the same p and H of
+ *   the incoming row (with one rule on this is what the corresponding HF transformers warper keeps; with several on, transformers
+ *   renormalises between them and this does not).  An empty intersection keeps every token with v_i == m.  A row of only -inf is left as
+ *   it is.  -0.0 == +0.0.  NaN inputs are not supported.
+ *   - Effect: the RAW logit x_i of every removed token becomes -inf; every kept logit is left bit-untouched; columns [V, ldl) are neither
+ *     read nor written.  The sampling step that follows sees the truncated row and applies its own top-k / top-p to it: its mode-0 top_p
+ *     mass is therefore relative to the truncated row.
+ * One launch, one workgroup per row; the row is re-read per pass (L2): maximum; the sums that give lse and H (epsilon, eta, typical
+ * only); for typical four passes of a bucket / radix threshold search on the fp32 image of d with masses in 2^-32 fixed point; one more
+ * when typical and a threshold rule are both on (the empty-intersection test); the pass that writes.  The masses go through __expf; lse, H and the
+ * thresholds are held in fp64.  Integer atomics and fixed-order sums only: a row's result is bit-identical from run to run and does not
+ * depend on R or on the other rows.  Leading dimensions in elements.  Nothing is launched, and CC_OK returned, when all four rules are off
+ * or R == 0.  CC_ERR_ARG: R < 0, V <= 0, ldl < V, min_p outside [0, 1], typical_p outside (0, 1], epsilon_cutoff or eta_cutoff outside
+ * [0, 1), any of them NaN, hist_len < 0, hist_len > 0 with a NULL history or hist_ld < hist_len, logits NULL with R > 0 (a bad argument is
+ * one whatever R and the rules are).  CC_ERR_SHAPE: V beyond what the history bitmap in LDS admits: 16928 + 4 * ceil(V / 32) bytes must not exceed
+ * 150 KiB, i.e. V <= 1093376. */
+int cc_logits_truncate(float* logits, int32_t R, int32_t V, int64_t ldl, float temperature, const int64_t* history, int32_t hist_len,
+                       int32_t hist_ld, float repetition_penalty, float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff,
+                       void* stream);
 /* Contrastive search (since 3, added without a version bump; not in the reference: Su et al., 2022, "A Contrastive Framework for Neural
  * Text Generation"): at every step the k most probable tokens of a caption are run through the model as k rows of one group, and the
  * token kept is the one with the largest  (1 - alpha) p(c) - alpha max_j cos(h_c, h_j),  h_c = the candidate's final hidden state, h_j =
