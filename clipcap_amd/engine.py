@@ -1109,6 +1109,34 @@ def beam_group_step(logits: torch.Tensor, samples: int, beam: int, groups: int, 
     return nt, sr
 
 
+def beam_gumbel_buffers(device, samples: int, beam: int, V: int) -> tuple:
+    """beam_buffers for beam_gumbel_step: (next_tokens, src_rows, scratch of cc_beam_gumbel_ws_bytes).  Owned by ONE decode, like those."""
+    nbytes = _lib.lib().cc_beam_gumbel_ws_bytes(samples, beam, V)
+    check(nbytes, "cc_beam_gumbel_ws_bytes")
+    return (torch.empty(samples * beam, dtype=torch.int32, device=device), torch.empty(samples * beam, dtype=torch.int32, device=device),
+            torch.empty(nbytes, dtype=torch.uint8, device=device))
+
+
+def beam_gumbel_step(logits: torch.Tensor, samples: int, beam: int, temperature: float, first: bool, stop_token: int, seed: int, step: int,
+                     scores: torch.Tensor, gumbels: torch.Tensor, seq_lengths: torch.Tensor, has_stopped: torch.Tensor,
+                     bufs: Optional[tuple] = None):
+    """One device-side update of stochastic beam search (cc_beam_gumbel_step; Kool et al., 2019): every sample's ``beam`` slots become
+    ``beam`` continuations sampled without replacement from the model, best perturbed log-probability first.  logits fp32 (samples*beam, V)
+    (a view with a row stride is fine; ``first``: only row 0 of every sample is read).  State IN PLACE, fp32 (samples*beam,): ``scores`` =
+    the summed token log-probabilities (not length-normalised), ``gumbels`` = the perturbed log-probabilities; ``seq_lengths`` and
+    ``has_stopped`` (uint8) as beam_step's.  The Gumbel noise is a pure function of (``seed`` in [0, 2^64), ``step`` >= 0, the logits row's
+    index, the token): counter-based, drawn inside the kernel.  ``bufs``: the caller's beam_gumbel_buffers(...).
+    Returns (next_tokens int32 (samples*beam,), src_rows int32 (samples*beam,) — the source row inside the sample)."""
+    dev = logits.device
+    V = logits.shape[1]
+    nt, sr, ws = bufs if bufs is not None else beam_gumbel_buffers(dev, samples, beam, V)
+    ldl = logits.stride(0) if logits.shape[0] > 1 else max(logits.stride(0), V)
+    check(_lib.lib().cc_beam_gumbel_step(samples, beam, V, _p(logits), ldl, float(temperature), int(first), int(stop_token), int(seed), int(step),
+                                        _p(scores), _p(gumbels), _p(seq_lengths), _p(has_stopped), _p(nt), _p(sr), _p(ws), _stream(dev)),
+          "cc_beam_gumbel_step")
+    return nt, sr
+
+
 def constrain_logits(logits: torch.Tensor, *, lpart: Optional[tuple] = None, history: Optional[torch.Tensor] = None, hist_len: int = 0,
                      no_repeat_ngram: int = 0, ban_token: int = -1, suppress: Optional[torch.Tensor] = None,
                      skip_rows: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -3,3 +3,5 @@ from clipcap_amd.inference.base import generate_beam, generate_beam_tokens, gene
 from clipcap_amd.inference.contrastive import generate_contrastive, generate_contrastive_tokens  # noqa: F401
 from clipcap_amd.inference.generate import generate  # noqa: F401
 from clipcap_amd.inference.score import CaptionScores, rerank_captions, score_captions  # noqa: F401
+from clipcap_amd.inference.stochastic_beam import (StochasticBeams, generate_stochastic_beam, generate_stochastic_beam_tokens,  # noqa: F401
+                                                   sbs_importance_weights)

@@ -181,3 +181,21 @@ def validate_truncation(min_p: float = 0.0, typical_p: float = 1.0, epsilon_cuto
 def truncation_is_on(opts: dict) -> bool:
     """whether any rule of a validate_truncation result does anything"""
     return opts["min_p"] > 0.0 or opts["typical_p"] < 1.0 or opts["epsilon_cutoff"] > 0.0 or opts["eta_cutoff"] > 0.0
+
+
+# ---- stochastic beam search (not in the reference: inference/stochastic_beam.py) ----------------------------------------------------------
+
+MAX_STOCHASTIC_BEAM = 16        # the beam widths cc_beam_gumbel_step accepts
+
+
+def validate_stochastic_beam(beam_size: int, num_return_sequences=None, seed=None) -> None:
+    """Checks the options of the stochastic-beam-search decoders.  ValueError for a beam_size that is not an int in [1,
+    MAX_STOCHASTIC_BEAM], a num_return_sequences that is neither None (all) nor an int in [1, beam_size], and a seed that is neither None
+    (drawn from a generator) nor an int in [0, 2^64).  Pure: touches no device."""
+    if isinstance(beam_size, bool) or not isinstance(beam_size, int) or not 1 <= beam_size <= MAX_STOCHASTIC_BEAM:
+        raise ValueError(f"beam_size must be an int in [1, {MAX_STOCHASTIC_BEAM}], got {beam_size!r}")
+    n = num_return_sequences
+    if n is not None and (isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= beam_size):
+        raise ValueError(f"num_return_sequences must be None or an int in [1, beam_size = {beam_size}], got {n!r}")
+    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64):
+        raise ValueError(f"seed must be None or an int in [0, 2^64), got {seed!r}")

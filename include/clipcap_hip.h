@@ -70,7 +70,8 @@ extern "C" {
  * cc_beam_group_ws_bytes, cc_decode_hidden_unit, cc_contrastive_topk, cc_contrastive_select, the decode-attention test hook
  * cc_decode_attention, and the label-smoothed loss cc_lmhead_smooth_scratch_floats, cc_lmhead_ce_fwd_smooth, cc_lmhead_ce_bwd_smooth,
  * the weight-averaging optimizer step cc_adamw_step_ema, the decode-time guidance cc_logits_guide, the loss with per-token weights
- * cc_lmhead_ce_fwd_w, cc_lmhead_ce_bwd_w, and the sampling truncation rules cc_logits_truncate. */
+ * cc_lmhead_ce_fwd_w, cc_lmhead_ce_bwd_w, the sampling truncation rules cc_logits_truncate, and stochastic beam search
+ * cc_beam_gumbel_ws_bytes, cc_beam_gumbel_step with its noise test hooks cc_gumbel_noise, cc_gumbel_from_bits. */
 #define CC_ABI_VERSION 3
 int cc_abi_version(void);
 
@@ -324,6 +325,46 @@ int64_t cc_beam_group_ws_bytes(int32_t S, int32_t beam, int32_t groups, int32_t 
 int cc_beam_group_step(int32_t S, int32_t beam, int32_t groups, int32_t V, const float* logits, int64_t ldl, float temperature,
                        float diversity_penalty, int32_t first, int32_t stop_token, float* scores, float* seq_lengths, uint8_t* has_stopped,
                        int32_t* next_tokens, int32_t* src_rows, void* ws, void* stream);
+/* Stochastic beam search (since 3, added without a version bump; not in the reference: Kool, van Hoof, Welling, ICML 2019, "Stochastic
+ * Beams and Where to Find Them"): one update that gives every sample `beam` continuations sampled WITHOUT replacement from the model, in
+ * sampling order.  State per beam row b of a sample: scores[b] = phi_b, the sum of the token log-probabilities so far (NOT
+ * length-normalised); gumbels[b] = Gamma_b, the row's perturbed log-probability; seq_lengths, has_stopped as in cc_beam_step.  first != 0:
+ * one parent, row 0, with phi = 0, Gamma = 0, not stopped.
+ *   Noise of token v of logits row `row` = s * beam + b of this call (first: row s * beam, under that index) at decode step `step` under
+ *   `seed`: h = word v & 3 of Philox4x32-10(counter = (v >> 2, row, step, 0), key = (lo32(seed), hi32(seed))); u = (h + 0.5) / 2^32,
+ *   n_v = -ln(-ln u), a real in (-3.14, 22.9).  In fp32: E = -logf(((float)h + 0.5f) 2^-32) for h < 2^31, else
+ *   E = -log1pf(-((float)(0xffffffff - h) + 0.5f) 2^-32); n = -logf(E): u is never formed near 1.
+ *   Stage 1, per parent row.  A stopped parent has exactly one candidate: token 0 (padding) with Gamma_c = Gamma_b, phi_c = phi_b; no
+ *   noise is drawn and its logits are not read.  A live parent: x_v = logits[row][v] / T (T <= 0: 1), lp_v = log_softmax(x)_v from
+ *   the row's running (max m, sum of exp(x - m)) pair, y_v = x_v + n_v, Y = max_v y_v.  The row keeps its `beam` best tokens by (y_v
+ *   descending, v ascending); tokens with x_v = -inf (bans) are no candidates.  Gamma_c below is non-decreasing in y_v within a row, so the
+ *   pruning is exact.
+ *   Stage 2, per sample, for every kept candidate of parent b: phi_c = phi_b + lp_v; g = phi_c + n_v; delta = Y - y_v >= 0 (from the y
+ *   values: exact in fp32 when small); t = Gamma_b - g + log(1 - exp(-delta)) (delta = 0: -inf); Gamma_c = Gamma_b - max(0, t) -
+ *   log1p(exp(-|t|)), the stable form of -log(exp(-Gamma_b) - exp(-Z) + exp(-g)).  Gamma_c <= Gamma_b always; the row's best child has
+ *   Gamma_c == Gamma_b bit for bit.  A candidate with Gamma_c = -inf is no candidate.
+ *   Selection and commit: the `beam` best candidates under (Gamma_c descending, flat index b V + v ascending) fill the slots best first:
+ *   next_tokens = v, src_rows = the source row inside the sample (0 on the first step), scores = phi_c, gumbels = Gamma_c, seq_lengths =
+ *   the parent's + (stopped ? 0 : 1) (first: 1), has_stopped = the parent's | (v == stop_token).  Fewer candidates than slots (extreme
+ *   bans): an empty slot gets token 0, source row 0, scores = gumbels = -inf, has_stopped = 1 and row 0's seq_lengths as a stopped parent
+ *   passes it on (first: 1); it stays empty in later steps by the rules above.  Every index written is in bounds.
+ * Two launches, stream-ordered, one read of the logits, no atomics, no host sync, no allocation: one block per live parent row (running
+ * softmax pair, per-thread sorted lists of the `beam` best (y, v) in fp32 with the fp32 noise above, one Philox call per four tokens;
+ * widths 1-5 and 8 with lists of that length, the others with lists of 16), then one 64-thread block per sample over at most beam^2
+ * candidates.  Stage 2 is evaluated in fp64 (the kept candidates' noise drawn again from the same bits, x = logit / T, lp = x - m -
+ * log(sum) from the row's fp32 softmax pair, y, delta and the transform), phi_c and Gamma_c rounded to fp32 once: fp32 y values would
+ * put ~3e-6 into delta, which log(1 - exp(-delta)) amplifies by 1 / delta.  Results are bit-identical from run to run.  ws: cc_beam_gumbel_ws_bytes(S, beam, V) bytes; every byte read was written in this call.  Leading dimension in elements.
+ * CC_ERR_ARG: a NULL pointer argument, S < 0, beam outside [1, 16], V < 1, ldl < V, step < 0, a NaN temperature.  CC_ERR_SHAPE:
+ * V > 2097152.  S == 0: CC_OK, nothing is launched.  All checks come before anything touches the device. */
+int64_t cc_beam_gumbel_ws_bytes(int32_t S, int32_t beam, int32_t V);
+int cc_beam_gumbel_step(int32_t S, int32_t beam, int32_t V, const float* logits, int64_t ldl, float temperature, int32_t first,
+                        int32_t stop_token, uint64_t seed, int32_t step, float* scores, float* gumbels, float* seq_lengths,
+                        uint8_t* has_stopped, int32_t* next_tokens, int32_t* src_rows, void* ws, void* stream);
+/* test hooks, like cc_dropout_mask: the noise cc_beam_gumbel_step uses.  cc_gumbel_noise: out[v] = n_v, v in [0, V), of logits row `row`
+ * at `step` under `seed` (CC_ERR_ARG: step < 0, row < 0, V < 1, out NULL).  cc_gumbel_from_bits: out[i] = n(h[i]), i in [0, n)
+ * (CC_ERR_ARG: n < 0, a NULL pointer; n == 0: nothing is launched). */
+int cc_gumbel_noise(uint64_t seed, int32_t step, int32_t row, int32_t V, float* out, void* stream);
+int cc_gumbel_from_bits(const uint32_t* h, int32_t n, float* out, void* stream);
 /* Constrained decoding (since 3, added without a version bump): token bans on one step's logits [R][ldl], in place, BEFORE the beam update
  * or the sampling step.  A ban sets the token's logit to -inf, i.e. before the softmax (the convention of the reference's
  * top_k_top_p_filtering, utils.py:5-30): its mass is renormalised over the allowed tokens.  The banned set of row r:
