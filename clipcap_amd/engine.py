@@ -1221,6 +1221,67 @@ def truncate_logits(logits: torch.Tensor, *, temperature: float = 1.0, history: 
     return logits
 
 
+CIDER_MAX_LEN, CIDER_MAX_REF_TOKENS, CIDER_TOKEN_LIMIT = 256, 4096, 65535       # cc_cider_score's limits (include/clipcap_hip.h)
+
+
+def cider_score(cand: torch.Tensor, refs: torch.Tensor, tab_keys: torch.Tensor, tab_idf: torch.Tensor, log_ndocs: float, *,
+                sigma: float = 6.0, stop_token: int = 50256, count_stop: bool = False, ref_count: Optional[torch.Tensor] = None,
+                cand_group: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """CIDEr-D over TOKEN IDS (cc_cider_score, one launch; nothing is read back): ``cand`` int64 (C, n) candidates, each running to its
+    first ``stop_token`` (excluded, or included with ``count_stop``; a negative ``stop_token`` = none), else to its first negative id, else
+    n; ``refs`` int32 (G, Rmax, Lr), each row ending at its first negative id; image g uses its first ``ref_count[g]`` rows (int32 (G,),
+    1..Rmax; None: all).  Candidate c belongs to image ``cand_group[c]`` (int32 (C,)), or c % G when None (C a multiple of G).
+    ``tab_keys`` int64 (cap,) / ``tab_idf`` fp32 (cap,): the idf table of ``train.cider.CiderReward.from_corpus`` (the keys' bit
+    patterns), cap a power of two; an n-gram it does not hold gets ``log_ndocs``.  A view with a row stride is fine for ``cand``.
+    ValueError for anything cc_cider_score would refuse, before a device is touched.  Returns fp32 (C,) scores (``out`` if given)."""
+    import math
+    if cand.dim() != 2 or cand.dtype != torch.int64:
+        raise ValueError(f"cand must be int64 (C, n), got {cand.dtype} {tuple(cand.shape)}")
+    if refs.dim() != 3 or refs.dtype != torch.int32 or not refs.is_contiguous():
+        raise ValueError(f"refs must be contiguous int32 (G, Rmax, Lr), got {refs.dtype} {tuple(refs.shape)}")
+    C_, n = cand.shape
+    G, Rmax, Lr = refs.shape
+    if G < 1 or Rmax < 1 or Lr < 1:
+        raise ValueError(f"refs must hold at least one image, reference and position, got {tuple(refs.shape)}")
+    if n > CIDER_MAX_LEN or Lr > CIDER_MAX_LEN or Rmax * Lr > CIDER_MAX_REF_TOKENS:
+        raise ValueError(f"cider_score takes candidates and references of at most {CIDER_MAX_LEN} positions and at most "
+                         f"{CIDER_MAX_REF_TOKENS} reference positions per image, got n = {n}, Rmax = {Rmax}, Lr = {Lr}")
+    stop_token = int(stop_token)
+    if stop_token >= CIDER_TOKEN_LIMIT:
+        raise ValueError(f"stop_token must be below {CIDER_TOKEN_LIMIT}, got {stop_token}")
+    sigma, log_ndocs = float(sigma), float(log_ndocs)
+    if not (sigma > 0.0 and math.isfinite(sigma)) or not math.isfinite(log_ndocs):
+        raise ValueError(f"sigma must be positive and finite and log_ndocs finite, got {sigma}, {log_ndocs}")
+    if (n > 1 and cand.stride(1) != 1) or (C_ > 1 and cand.stride(0) < n):
+        raise ValueError("cand rows must be dense and must not overlap")
+    cap = tab_keys.numel()
+    if tab_keys.dtype != torch.int64 or tab_idf.dtype != torch.float32 or tab_idf.numel() != cap or cap < 1 or cap & (cap - 1) or \
+            not tab_keys.is_contiguous() or not tab_idf.is_contiguous():
+        raise ValueError("tab_keys int64 / tab_idf fp32 must be contiguous and hold the same power-of-two number of slots")
+    if cand_group is None:
+        if C_ % G:
+            raise ValueError(f"without cand_group the {C_} candidates must be a multiple of the {G} images")
+    elif cand_group.dtype != torch.int32 or cand_group.shape != (C_,) or not cand_group.is_contiguous():
+        raise ValueError(f"cand_group must be contiguous int32 ({C_},)")
+    if ref_count is not None and (ref_count.dtype != torch.int32 or ref_count.shape != (G,) or not ref_count.is_contiguous()):
+        raise ValueError(f"ref_count must be contiguous int32 ({G},)")
+    if out is None:
+        out = torch.empty(C_, dtype=torch.float32, device=cand.device)
+    elif out.dtype != torch.float32 or out.shape != (C_,) or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous fp32 ({C_},)")
+    for t in (refs, tab_keys, tab_idf, ref_count, cand_group, out):
+        if t is not None and t.device != cand.device:
+            raise ValueError(f"every tensor must be on the candidates' device {cand.device}, got {t.device}")
+    if C_ == 0:
+        return out
+    _require_cuda(cand, "cider_score")
+    ld = cand.stride(0) if C_ > 1 else max(cand.stride(0), n)
+    check(_lib.lib().cc_cider_score(_p(cand), C_, n, ld, stop_token, 1 if count_stop else 0, _p(cand_group) if cand_group is not None else None,
+                                    _p(refs), G, Rmax, Lr, _p(ref_count) if ref_count is not None else None, _p(tab_keys), _p(tab_idf), cap,
+                                    log_ndocs, sigma, _p(out), _stream(cand.device)), "cc_cider_score")
+    return out
+
+
 def contrastive_buffers(device, S: int, k: int, D: int, ctx_max: int, entry_length: int):
     """The device state of ONE contrastive-search decode of S captions with k candidates each (never shared between decodes, streams or
     threads), as a namespace: cand_tok int32 (S*k,), cand_prob fp32 (S*k,), cand_h fp32 (S*k, D) — the candidates of the step;

@@ -1,4 +1,5 @@
-"""clipcap_amd.train — mirrors clipcap/train/__init__.py:1-2 (``train``, ``start_training``, ``add_training_args``), plus ``evaluate`` and ``self_critical_step``."""
+"""clipcap_amd.train — mirrors clipcap/train/__init__.py:1-2 (``train``, ``start_training``, ``add_training_args``), plus ``evaluate``, ``self_critical_step`` and its device-side reward ``CiderReward``."""
 from clipcap_amd.train.args import add_training_args  # noqa: F401
 from clipcap_amd.train.train import evaluate, start_training, train  # noqa: F401
 from clipcap_amd.train.self_critical import scst_tokens_and_weights, self_critical_step  # noqa: F401
+from clipcap_amd.train.cider import CiderReward  # noqa: F401

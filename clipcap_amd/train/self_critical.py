@@ -3,7 +3,8 @@
 The REINFORCE term with the model's own greedy caption as the baseline is a cross-entropy over the SAMPLED caption in which every token
 carries the weight ``reward(sample) - reward(greedy)``: exactly the weighted loss of ``ClipCapModel.fused_step(token_weights=...)``.
 This module adds no device code; it decodes twice with ``sample_tokens``, asks the caller for the rewards and takes the weighted step.
-The metric (CIDEr, SPICE, ...) and the detokenising are the caller's: ``reward_fn`` gets token ids.
+``reward_fn`` gets token ids and may be any metric of the caller's; ``clipcap_amd.train.cider.CiderReward(...).for_batch(refs)`` is one
+that never leaves the device: CIDEr-D over token ids against token-id references, one launch for both decodes (cc_cider_score).
 """
 from typing import Callable, Optional, Tuple
 

@@ -71,7 +71,8 @@ extern "C" {
  * cc_decode_attention, and the label-smoothed loss cc_lmhead_smooth_scratch_floats, cc_lmhead_ce_fwd_smooth, cc_lmhead_ce_bwd_smooth,
  * the weight-averaging optimizer step cc_adamw_step_ema, the decode-time guidance cc_logits_guide, the loss with per-token weights
  * cc_lmhead_ce_fwd_w, cc_lmhead_ce_bwd_w, the sampling truncation rules cc_logits_truncate, and stochastic beam search
- * cc_beam_gumbel_ws_bytes, cc_beam_gumbel_step with its noise test hooks cc_gumbel_noise, cc_gumbel_from_bits. */
+ * cc_beam_gumbel_ws_bytes, cc_beam_gumbel_step with its noise test hooks cc_gumbel_noise, cc_gumbel_from_bits, and the CIDEr-D reward
+ * cc_cider_score with its host-only table builder cc_cider_table_build. */
 #define CC_ABI_VERSION 3
 int cc_abi_version(void);
 
@@ -437,6 +438,39 @@ int cc_logits_guide(const float* cond, int64_t ld_c, const float* uncond, int64_
 int cc_logits_truncate(float* logits, int32_t R, int32_t V, int64_t ldl, float temperature, const int64_t* history, int32_t hist_len,
                        int32_t hist_ld, float repetition_penalty, float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff,
                        void* stream);
+/* CIDEr-D over token ids, the reward of self-critical training (since 3, added without a version bump; the metric of the reference's
+ * eval/pycocoevalcap/cider/cider_scorer.py: clipped counts, Gaussian length penalty).  Words are TOKEN IDS: nothing is detokenised and no
+ * PTB tokenizer runs, so the numbers are CIDEr-D over BPE tokens, not the published word-level metric.  For a caption x of L words and
+ * n = 1..4, its n-grams are w[i .. i + n), i in [0, L - n]; tf_x(g) = occurrences of g in x; idf(g) = the table's value, log_ndocs for an
+ * n-gram the table does not hold.  For candidate c and the R references of its image:
+ *     v_x,n(g) = tf_x(g) idf(g);  norm_x,n = sqrt(sum over the distinct g of x of v_x,n(g)^2)
+ *     val_n(c, r) = sum over the distinct g of c of min(v_c,n(g), v_r,n(g)) v_r,n(g),  divided by norm_c,n norm_r,n only if both are non-zero
+ *     out[c] = 10 / (4 R) sum_r exp(-(len(c) - len(r))^2 / (2 sigma^2)) sum_n val_n(c, r),   len(x) = max(L_x - 1, 0)
+ *   (len counts bigrams: the reference's behaviour, reproduced).  An empty candidate scores 0; an empty reference still counts in R.
+ * Candidates: cand int64 [C][cand_ld], cand_len columns read.  A candidate's words run to the first of: a stop_token (excluded; included
+ *   when count_stop != 0), a negative id, cand_len.  stop_token < 0: no stop token.  Candidate c belongs to image cand_group[c], or to
+ *   c % G when cand_group is NULL (C must then be a multiple of G); a cand_group value outside [0, G) gives out[c] = 0.
+ * References: refs int32 [G][Rmax][Lr]; a row ends at its first negative id; image g uses its first ref_count[g] rows (1..Rmax, clamped;
+ *   NULL: all Rmax), the other rows are not read.
+ * Table: cc_cider_table_build's tab_keys[cap] / tab_idf[cap] in device memory, cap a power of two.  A key is an n-gram of ids in
+ *   [0, 65535), 16 bits per token, unused slots 0xFFFF; the slot is the top log2(cap) bits of key * 0x9E3779B97F4A7C15, probed linearly
+ *   with wrap-around (clipcap_amd/csrc/cider_table.h).  A token id >= 65535 inside a caption cannot be packed: every n-gram that holds
+ *   it misses the table (idf = log_ndocs) and is still compared exactly, token by token, within and between the captions.
+ * One launch, one workgroup per candidate, candidate and references in LDS; tf and first occurrence by exact comparison; the references'
+ * norms are computed in the same launch.  fp32 sums over n-grams, fp64 for the per-reference scalars, the result rounded once to fp32.
+ * Every sum in a fixed order, no floating-point atomics: the same input gives the same bits on every run, and out[c] does not depend on
+ * the other candidates.  out[0 .. C) is written, nothing else.
+ * Limits (CC_ERR_SHAPE): cand_len <= 256, Lr <= 256, Rmax * Lr <= 4096, stop_token < 65535.
+ * CC_ERR_ARG: C < 0, cand_len < 0, cand_ld < cand_len, G < 1, Rmax < 1, Lr < 1, cap not a power of two, sigma <= 0 or not finite,
+ * log_ndocs not finite, cand_group NULL with C not a multiple of G; with C > 0, a NULL cand, refs, tab_keys, tab_idf or out.  C == 0:
+ * CC_OK, nothing is launched.  All of this is decided before anything touches the device. */
+int cc_cider_score(const int64_t* cand, int32_t C, int32_t cand_len, int64_t cand_ld, int32_t stop_token, int32_t count_stop,
+                   const int32_t* cand_group, const int32_t* refs, int32_t G, int32_t Rmax, int32_t Lr, const int32_t* ref_count,
+                   const uint64_t* tab_keys, const float* tab_idf, int64_t cap, float log_ndocs, float sigma, float* out, void* stream);
+/* The table of cc_cider_score in HOST memory (host-only: no device is touched; the caller copies tab_keys / tab_idf to the device): n
+ * distinct keys with their idf into tab_keys[cap] / tab_idf[cap].  CC_ERR_ARG, the table's contents then unspecified: cap not a power
+ * of two, 2 n > cap (the load factor stays at or below 0.5), a duplicate key, the all-ones key (the empty marker), NULL pointers. */
+int cc_cider_table_build(const uint64_t* keys, const float* idf, int64_t n, uint64_t* tab_keys, float* tab_idf, int64_t cap);
 /* Contrastive search (since 3, added without a version bump; not in the reference: Su et al., 2022, "A Contrastive Framework for Neural
  * Text Generation"): at every step the k most probable tokens of a caption are run through the model as k rows of one group, and the
  * token kept is the one with the largest  (1 - alpha) p(c) - alpha max_j cos(h_c, h_j),  h_c = the candidate's final hidden state, h_j =
