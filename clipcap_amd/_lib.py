@@ -116,6 +116,8 @@ SIGNATURES = {
     "cc_beam_gumbel_step": (_I, [_I, _I, _I, _P, _L, _F, _I, _I, C.c_uint64, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cc_gumbel_noise": (_I, [C.c_uint64, _I, _I, _I, _P, _P]),
     "cc_gumbel_from_bits": (_I, [_P, _I, _P, _P]),
+    "cc_beam_lex_ws_bytes": (_L, [_I, _I, _I, _I]),
+    "cc_beam_lex_step": (_I, [_I, _I, _I, _P, _L, _F, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cc_logits_constrain": (_I, [_P, _I, _I, _L, _P, _I, _P, _I, _L, _I, _I, _I, _P, _I, _P, _P]),
     "cc_logits_guide": (_I, [_P, _L, _P, _L, _I, _I, _F, _P, _L, _P, _P]),
     "cc_logits_truncate": (_I, [_P, _I, _I, _L, _F, _P, _I, _I, _F, _F, _F, _F, _F, _P]),

@@ -1137,6 +1137,38 @@ def beam_gumbel_step(logits: torch.Tensor, samples: int, beam: int, temperature:
     return nt, sr
 
 
+def beam_lex_buffers(device, samples: int, beam: int, n_phr: int, V: int) -> tuple:
+    """beam_buffers for beam_lex_step: (next_tokens, src_rows, scratch of cc_beam_lex_ws_bytes).  Owned by ONE decode, like those."""
+    nbytes = _lib.lib().cc_beam_lex_ws_bytes(samples, beam, n_phr, V)
+    check(nbytes, "cc_beam_lex_ws_bytes")
+    return (torch.empty(samples * beam, dtype=torch.int32, device=device), torch.empty(samples * beam, dtype=torch.int32, device=device),
+            torch.empty(nbytes, dtype=torch.uint8, device=device))
+
+
+def beam_lex_step(logits: torch.Tensor, samples: int, beam: int, temperature: float, first: bool, stop_token: int, scores: torch.Tensor,
+                  seq_lengths: torch.Tensor, has_stopped: torch.Tensor, lex_state: torch.Tensor, phrases: Optional[torch.Tensor],
+                  bufs: Optional[tuple] = None):
+    """One device-side update of lexically constrained beam search (cc_beam_lex_step; dynamic beam allocation, Post & Vilar, 2018): a beam
+    may stop only after it has produced every phrase of its sample, and the ``beam`` slots are divided between the candidates by the number
+    of constraint tokens they have met, slot 0 the most.  logits fp32 (samples*beam, V) (a view with a row stride is fine; ``first``: only
+    row 0 of every sample is read).  ``phrases``: int32 (samples, n_phr, phr_len) on the device, -1 after a phrase's last token, at most 8
+    phrases of at most 8 tokens, or None for no phrases (then this is beam_step without partials, bit for bit).  State IN PLACE:
+    ``scores``, ``seq_lengths``, ``has_stopped`` as beam_step's and ``lex_state`` int32 (samples*beam,), zeros before the first step (what
+    it holds: inference/utils.py unpack_lex_state).  ``bufs``: the caller's beam_lex_buffers(...).
+    Returns (next_tokens int32 (samples*beam,), src_rows int32 (samples*beam,) — the source row inside the sample)."""
+    dev = logits.device
+    V = logits.shape[1]
+    n_phr, phr_len = (0, 1) if phrases is None else (int(phrases.shape[1]), int(phrases.shape[2]))
+    if phrases is not None and (phrases.dtype != torch.int32 or phrases.dim() != 3 or phrases.shape[0] != samples or not phrases.is_contiguous()):
+        raise ValueError(f"phrases must be a contiguous int32 tensor ({samples}, n_phr, phr_len), got {phrases.dtype} {tuple(phrases.shape)}")
+    nt, sr, ws = bufs if bufs is not None else beam_lex_buffers(dev, samples, beam, n_phr, V)
+    ldl = logits.stride(0) if logits.shape[0] > 1 else max(logits.stride(0), V)
+    check(_lib.lib().cc_beam_lex_step(samples, beam, V, _p(logits), ldl, float(temperature), int(first), int(stop_token),
+                                     _p(phrases) if n_phr > 0 else None, n_phr, phr_len, _p(scores), _p(seq_lengths), _p(has_stopped),
+                                     _p(lex_state), _p(nt), _p(sr), _p(ws), _stream(dev)), "cc_beam_lex_step")
+    return nt, sr
+
+
 def constrain_logits(logits: torch.Tensor, *, lpart: Optional[tuple] = None, history: Optional[torch.Tensor] = None, hist_len: int = 0,
                      no_repeat_ngram: int = 0, ban_token: int = -1, suppress: Optional[torch.Tensor] = None,
                      skip_rows: Optional[torch.Tensor] = None) -> torch.Tensor:

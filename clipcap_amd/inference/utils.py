@@ -199,3 +199,81 @@ def validate_stochastic_beam(beam_size: int, num_return_sequences=None, seed=Non
         raise ValueError(f"num_return_sequences must be None or an int in [1, beam_size = {beam_size}], got {n!r}")
     if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64):
         raise ValueError(f"seed must be None or an int in [0, 2^64), got {seed!r}")
+
+
+# ---- lexically constrained beam search (not in the reference: inference/lexical.py) ------------------------------------------------------
+
+MAX_PHRASES = 8                 # the phrases per prefix and the tokens per phrase cc_beam_lex_step accepts
+MAX_PHRASE_TOKENS = 8
+
+
+def validate_phrases(phrases, samples: int, vocab_size: int, stop_token: int, suppress_tokens=None) -> torch.Tensor:
+    """Checks the forced phrases of a constrained beam search over ``samples`` prefixes and returns them as the table cc_beam_lex_step
+    reads: int32 (samples, C, L) on the CPU, -1 after a phrase's last token (a row of -1: no phrase; C = 0 when there is none at all).
+    ``phrases``: an int tensor (samples, C, L) or (1, C, L) padded with negative ids, or nested lists of ids — one list of phrases per
+    prefix, or one list of phrases for all prefixes.  ValueError for more than MAX_PHRASES phrases for a prefix, a phrase that is empty or
+    longer than MAX_PHRASE_TOKENS, an id outside [0, vocab_size), the stop token inside a phrase, a phrase token in ``suppress_tokens``
+    (it could never be produced), the same phrase twice for one prefix, and a batch dimension that is neither 1 nor ``samples``.  Pure:
+    touches no device."""
+    S = int(samples)
+    if isinstance(phrases, torch.Tensor):
+        if phrases.dim() != 3 or phrases.dtype in (torch.float16, torch.bfloat16, torch.float32, torch.float64, torch.bool):
+            raise ValueError(f"phrases must be an int tensor ({S}, C, L) or (1, C, L), got {phrases.dtype} {tuple(phrases.shape)}")
+        rows = []
+        for sample in phrases.tolist():
+            kept = []
+            for p in sample:
+                n = next((i for i, t in enumerate(p) if t < 0), len(p))
+                if any(t >= 0 for t in p[n:]):
+                    raise ValueError(f"a phrase row has ids after its padding: {p}")
+                if n:                                                          # a row that is all padding is no phrase
+                    kept.append(p[:n])
+            rows.append(kept)
+    else:
+        seq = (list, tuple, torch.Tensor)
+        rows = [] if phrases is None else [p.tolist() if isinstance(p, torch.Tensor) else list(p) for p in phrases]
+        # one list of phrases per prefix iff the elements hold lists themselves (or are all empty: no phrase for any prefix)
+        if rows and not (any(isinstance(q, seq) for p in rows for q in p) or all(len(p) == 0 for p in rows)):
+            rows = [rows]
+        rows = [[[int(t) for t in (p.tolist() if isinstance(p, torch.Tensor) else p)] for p in sample] for sample in rows] or [[]]
+    if len(rows) not in (1, S):
+        raise ValueError(f"phrases are given for {len(rows)} prefixes; the batch has {S} (one list for all prefixes, or one per prefix)")
+    if len(rows) == 1:
+        rows = rows * S
+    banned = set() if suppress_tokens is None else {int(t) for t in (suppress_tokens.tolist() if hasattr(suppress_tokens, "tolist") else suppress_tokens)}
+    for sample in rows:
+        if len(sample) > MAX_PHRASES:
+            raise ValueError(f"{len(sample)} phrases for one prefix; at most {MAX_PHRASES} are supported")
+        for p in sample:
+            if not 1 <= len(p) <= MAX_PHRASE_TOKENS:
+                raise ValueError(f"a phrase must hold 1 to {MAX_PHRASE_TOKENS} tokens, got {len(p)}: {p}")
+            bad = [t for t in p if not 0 <= t < vocab_size]
+            if bad:
+                raise ValueError(f"phrase ids outside [0, {vocab_size}): {bad}")
+            if int(stop_token) in p:
+                raise ValueError(f"the stop token {stop_token} inside a phrase: {p}")
+            if banned.intersection(p):
+                raise ValueError(f"phrase tokens {sorted(banned.intersection(p))} are in suppress_tokens: the phrase {p} could never be produced")
+        if len({tuple(p) for p in sample}) != len(sample):
+            raise ValueError(f"the same phrase twice for one prefix: {sample}")
+    C = max((len(sample) for sample in rows), default=0)
+    L = max((len(p) for sample in rows for p in sample), default=1)
+    table = torch.full((S, C, L), -1, dtype=torch.int32)
+    for s, sample in enumerate(rows):
+        for c, p in enumerate(sample):
+            table[s, c, :len(p)] = torch.tensor(p, dtype=torch.int32)
+    return table
+
+
+def unpack_lex_state(lex_state: torch.Tensor, table: torch.Tensor):
+    """(tokens_met int32, all_met bool), each (S, beam), of cc_beam_lex_step's row states ``lex_state`` int32 (S * beam,) under the phrase
+    ``table`` (S, C, L) of validate_phrases: bits 0-7 of a state are the met phrases, bits 8-11 the phrase in progress + 1, bits 12-15 the
+    tokens of it matched so far; tokens_met = the summed lengths of the met phrases plus that progress.  Pure torch, on the state's device."""
+    S, C = table.shape[0], table.shape[1]
+    st = lex_state.view(S, -1).to(torch.int64)
+    table = table.to(st.device)
+    lens = (table >= 0).to(torch.int64).cumprod(dim=2).sum(dim=2)                  # (S, C): a phrase ends at its first negative id
+    bits = (st.unsqueeze(-1) >> torch.arange(C, device=st.device)) & 1             # (S, beam, C)
+    progress = torch.where(((st >> 8) & 0xF) > 0, (st >> 12) & 0xF, torch.zeros_like(st))
+    full = ((lens > 0).to(torch.int64) << torch.arange(C, device=st.device)).sum(dim=1, keepdim=True)
+    return ((bits * lens.unsqueeze(1)).sum(dim=2) + progress).to(torch.int32), (st & 0xFF) == full

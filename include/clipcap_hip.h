@@ -71,8 +71,9 @@ extern "C" {
  * cc_decode_attention, and the label-smoothed loss cc_lmhead_smooth_scratch_floats, cc_lmhead_ce_fwd_smooth, cc_lmhead_ce_bwd_smooth,
  * the weight-averaging optimizer step cc_adamw_step_ema, the decode-time guidance cc_logits_guide, the loss with per-token weights
  * cc_lmhead_ce_fwd_w, cc_lmhead_ce_bwd_w, the sampling truncation rules cc_logits_truncate, and stochastic beam search
- * cc_beam_gumbel_ws_bytes, cc_beam_gumbel_step with its noise test hooks cc_gumbel_noise, cc_gumbel_from_bits, and the CIDEr-D reward
- * cc_cider_score with its host-only table builder cc_cider_table_build. */
+ * cc_beam_gumbel_ws_bytes, cc_beam_gumbel_step with its noise test hooks cc_gumbel_noise, cc_gumbel_from_bits, the CIDEr-D reward
+ * cc_cider_score with its host-only table builder cc_cider_table_build, and lexically constrained beam search cc_beam_lex_ws_bytes,
+ * cc_beam_lex_step. */
 #define CC_ABI_VERSION 3
 int cc_abi_version(void);
 
@@ -366,6 +367,48 @@ int cc_beam_gumbel_step(int32_t S, int32_t beam, int32_t V, const float* logits,
  * (CC_ERR_ARG: n < 0, a NULL pointer; n == 0: nothing is launched). */
 int cc_gumbel_noise(uint64_t seed, int32_t step, int32_t row, int32_t V, float* out, void* stream);
 int cc_gumbel_from_bits(const uint32_t* h, int32_t n, float* out, void* stream);
+/* Lexically constrained beam search with dynamic beam allocation (since 3, added without a version bump; not in the reference: Post &
+ * Vilar, NAACL 2018, "Fast Lexically Constrained Decoding with Dynamic Beam Allocation for Neural Machine Translation"; the idea of forcing
+ * words into a caption: Anderson et al., EMNLP 2017): one beam update at a fixed width `beam` that tracks per beam row which phrases it has
+ * produced and divides the slots between hypotheses by how much of the constraint set they have met.
+ *   Phrases: device int32 [S][n_phr][phr_len], -1 after a phrase's last token.  Phrase c of sample s exists iff its first entry is >= 0; its
+ *   length is the index of its first negative entry, or phr_len.  0 <= n_phr <= 8, 1 <= phr_len <= 8; n_phr == 0: no phrases, the pointer
+ *   is not followed (the same as a table of -1).  Phrase tokens are in [0, V) and never the stop token (the callers validate); on the device
+ *   an id outside [0, V) never matches.
+ *   Row state: lex_state int32 [S * beam], in place like scores: bits 0-7 met (bit c: phrase c has been produced), bits 8-11 cur + 1 (the
+ *   phrase in progress, 0 = none), bits 12-15 pos (the tokens of that phrase matched so far); 0 is the initial state.  full(s) = the mask
+ *   of the sample's existing phrases; tokens_met(state) = the summed lengths of the met phrases, plus pos when a phrase is in progress.
+ *   Transition for token v from a parent that has not stopped: a phrase in progress whose next token is v moves on (pos + 1; met, with cur
+ *   and pos cleared, when that was its last token); otherwise the progress is dropped, and if v is the first token of an unmet existing
+ *   phrase the lowest-index such phrase starts (pos = 1, or met at once when its length is 1).  No fallback to a shorter partial match.  A
+ *   stopped parent passes its state on unchanged.  (One definition: csrc/lex_state.h.)
+ *   Values are cc_beam_step's: the length-normalised sum of softmax().log() over logits / temperature; first != 0 reads row 0 of the sample
+ *   with state 0; a stopped parent has the single continuation token 0 at its own average.  A candidate (b, v), flat index b V + v, is
+ *   valid iff its value is > -inf and it is not the stop token from a non-stopped parent with met != full(s): a hypothesis may end only when
+ *   every phrase has been produced.  The ban is on the candidate, not the logit: the softmax keeps the stop token, so scores stay sums of
+ *   the model's own log-probabilities.
+ *   Candidate set K of a sample (a set over flat indices; order: value descending, flat index ascending): T, the `beam` best valid
+ *   candidates of the sample; B, every parent row's best valid candidate (a stopped parent has exactly one, so a finished caption that
+ *   holds every phrase cannot fall out); P, for every non-stopped parent the valid candidates for the next token of its phrase in progress
+ *   and for the first token of each of its unmet phrases.
+ *   Allocation: every member of K gets its new state and its bank = tokens_met of that state.  The banks are visited from the highest to
+ *   the lowest, round after round; each non-empty bank gives its best untaken candidate to the next free slot, until `beam` slots are
+ *   filled or K is empty.  Slots are in picking order, so slot 0 has the largest tokens_met.  Commit as cc_beam_step, lex_state = the new
+ *   state.  Fewer candidates than slots: an empty slot gets token 0, source row 0, scores = -inf, has_stopped = 1, state 0 and row 0's
+ *   seq_lengths as a stopped parent passes it on (first: 1); it stays empty.  Every index written is in bounds.
+ *   Without a phrase in the sample there is one bank and the result is cc_beam_step's (without partials) bit for bit, scores included.
+ * Three launches, stream-ordered, no atomics, no host sync, no allocation: the row statistics of cc_beam_step; one block per live parent row
+ * (per-thread sorted lists of the `beam` best valid (value, token), widths 1-5 and 8 with lists of that length, the others with lists of
+ * 16; a direct gather of the at most n_phr + 1 phrase tokens); one 64-thread block per sample over at most beam * (beam + n_phr + 1)
+ * candidates.  The logits are read twice.  Results are bit-identical from run to run.  ws: cc_beam_lex_ws_bytes(S, beam, n_phr, V) bytes;
+ * every byte read was written in this call.  Leading dimension in elements.
+ * CC_ERR_ARG: a NULL pointer argument (phrases only when n_phr > 0), S < 0, beam outside [1, 16], V < 1, ldl < V, n_phr outside [0, 8],
+ * phr_len outside [1, 8] when n_phr > 0, a NaN temperature.  CC_ERR_SHAPE: V > 2097152.  S == 0: CC_OK, nothing is launched.  All checks
+ * come before anything touches the device; cc_beam_lex_ws_bytes returns < 0 for the same bad arguments. */
+int64_t cc_beam_lex_ws_bytes(int32_t S, int32_t beam, int32_t n_phr, int32_t V);
+int cc_beam_lex_step(int32_t S, int32_t beam, int32_t V, const float* logits, int64_t ldl, float temperature, int32_t first,
+                     int32_t stop_token, const int32_t* phrases, int32_t n_phr, int32_t phr_len, float* scores, float* seq_lengths,
+                     uint8_t* has_stopped, int32_t* lex_state, int32_t* next_tokens, int32_t* src_rows, void* ws, void* stream);
 /* Constrained decoding (since 3, added without a version bump): token bans on one step's logits [R][ldl], in place, BEFORE the beam update
  * or the sampling step.  A ban sets the token's logit to -inf, i.e. before the softmax (the convention of the reference's
  * top_k_top_p_filtering, utils.py:5-30): its mass is renormalised over the allowed tokens.  The banned set of row r:
