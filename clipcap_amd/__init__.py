@@ -1,7 +1,7 @@
 """clipcap_amd — MI355X-native ClipCap training + caption-generation path (HIP kernels behind a C ABI).
 
 Mirrors the reference's import surface (clipcap/__init__.py:1-2): ``clipcap_amd.load``, ``get_encoder`` / ``get_encoder_from_model`` and the
-``clipcap_amd.model`` / ``clipcap_amd.train`` / ``clipcap_amd.inference`` / ``clipcap_amd.encoders`` sub-packages.
+``clipcap_amd.model`` / ``clipcap_amd.train`` / ``clipcap_amd.inference`` / ``clipcap_amd.encoders`` / ``clipcap_amd.eval`` sub-packages.
 ``install_as_clipcap()`` registers the same modules under the reference's own name so that ``import clipcap`` / ``python -m clipcap.train``
 call sites need no edit.
 """
@@ -13,7 +13,7 @@ __version__ = "0.2.0"
 # modules of the reference's package that have a counterpart here (clipcap/<name>.py -> clipcap_amd/<name>.py)
 _ALIASED = ("model", "model.model", "model.config", "model.args", "model.load", "model.mapper", "train", "train.train", "train.args",
             "train.callback", "train.dataloader", "train.__main__", "inference", "inference.base", "inference.generate", "inference.no_beam",
-            "inference.nucleus_sampling", "inference.utils", "encoders", "encoders.base", "encoders.config")
+            "inference.nucleus_sampling", "inference.utils", "encoders", "encoders.base", "encoders.config", "eval", "eval.base", "eval.metrics", "eval.__main__")
 
 
 def load(*args, **kwargs):
@@ -36,7 +36,7 @@ def get_encoder_from_model(*args, **kwargs):
 
 def install_as_clipcap(force: bool = False) -> None:
     """Makes ``import clipcap``, ``clipcap.model``, ``clipcap.train``, ``clipcap.inference[.base|.generate|.no_beam|.nucleus_sampling]`` and
-    ``clipcap.encoders[.config]`` resolve to this package (entries in ``sys.modules``; ``python -m clipcap_amd.train`` stays the CLI, and after
+    ``clipcap.encoders[.config]``, ``clipcap.eval[.metrics]`` resolve to this package (entries in ``sys.modules``; ``python -m clipcap_amd.train`` stays the CLI, and after
     the call ``runpy.run_module("clipcap.train")`` works too).  Refuses when a different ``clipcap`` package is already imported —
     silently shadowing the reference inside a process that uses it would mix the two — unless ``force`` is set.  Idempotent."""
     me = sys.modules[__name__]

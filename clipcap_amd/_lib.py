@@ -123,6 +123,8 @@ SIGNATURES = {
     "cc_logits_truncate": (_I, [_P, _I, _I, _L, _F, _P, _I, _I, _F, _F, _F, _F, _F, _P]),
     "cc_cider_score": (_I, [_P, _I, _I, _L, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _L, _F, _F, _P, _P]),
     "cc_cider_table_build": (_I, [_P, _P, _L, _P, _P, _L]),
+    "cc_bleu_stats": (_I, [_P, _I, _I, _L, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "cc_rouge_l": (_I, [_P, _I, _I, _L, _I, _I, _P, _P, _I, _I, _I, _P, _F, _P, _P, _P]),
     "cc_decode_hidden_unit": (_I, [_GC, _I, _I, _P, _P, _P, _L, _L, _P]),
     "cc_contrastive_topk": (_I, [_P, _L, _I, _I, _P, _I, _I, _P, _P, _P, _P]),
     "cc_contrastive_select": (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P]),

@@ -15,37 +15,13 @@
 // fp32 / integer work only: built once (Makefile SRCS_ONCE).
 #include "layout.h"
 #include "cider_table.h"
+#include "caption_lds.h"
 
 using namespace CC_NS;
 using namespace cc_cider;
+using namespace cc_caption;
 
 namespace {
-
-constexpr int CD_T = 256;                    // threads per candidate; >= CD_LMAX: one caption position per thread
-constexpr int CD_W = CD_T / 64;
-constexpr int CD_LMAX = 256;                 // cand_len and Lr
-constexpr int CD_REFMAX = 4096;              // Rmax * Lr: the references of one image in LDS (16 KiB)
-
-template <int N, class A, class B>
-__device__ __forceinline__ bool cd_eq(const A* a, const B* b) {
-    bool e = true;
-#pragma unroll
-    for (int k = 0; k < N; k++) e = e && ((long long)a[k] == (long long)b[k]);
-    return e;
-}
-
-// occurrences of the n-gram g[0..N) in x[0..L); *before = occurrences that start before position `upto`
-template <int N, class A, class B>
-__device__ __forceinline__ int cd_count(const A* g, const B* x, int L, int upto, int* before) {
-    int tf = 0, bf = 0;
-    for (int j = 0; j + N <= L; j++) {
-        const int m = cd_eq<N>(g, x + j) ? 1 : 0;
-        tf += m;
-        bf += j < upto ? m : 0;
-    }
-    *before = bf;
-    return tf;
-}
 
 struct CdTable {
     const uint64_t* keys;
@@ -138,19 +114,7 @@ __global__ __launch_bounds__(CD_T) void k_cider_score(const long long* __restric
     }
     int R = ref_count ? ref_count[g] : Rmax;
     R = R < 0 ? 0 : R > Rmax ? Rmax : R;
-    // the candidate: to its first stop token (kept with count_stop), else its first negative id, else cand_len
-    if (tid == 0) s_len = cand_len;
-    __syncthreads();
-    for (int i = tid; i < cand_len; i += CD_T) {
-        const long long t = cand[(size_t)c * cand_ld + i];
-        cw[i] = t;
-        if (t < 0) atomicMin(&s_len, i);
-        else if (stop_token >= 0 && t == (long long)stop_token) atomicMin(&s_len, count_stop ? i + 1 : i);
-    }
-    const int* rg = refs + (size_t)g * Rmax * Lr;
-    for (int i = tid; i < R * Lr; i += CD_T) rw[i] = rg[i];
-    __syncthreads();
-    const int Lc = s_len;
+    const int Lc = cd_load_captions(cand, c, cand_len, cand_ld, stop_token, count_stop, refs, g, Rmax, Lr, R, cw, rw, &s_len);
     float nc[4];
     nc[0] = cd_cand_pass<1>(cw, Lc, tab, ctf[0], cidf[0]);
     nc[1] = cd_cand_pass<2>(cw, Lc, tab, ctf[1], cidf[1]);

@@ -1314,6 +1314,109 @@ def cider_score(cand: torch.Tensor, refs: torch.Tensor, tab_keys: torch.Tensor, 
     return out
 
 
+def _caption_metric_shapes(what: str, cand: torch.Tensor, refs: torch.Tensor, ref_count: Optional[torch.Tensor],
+                           cand_group: Optional[torch.Tensor]):
+    """What cc_bleu_stats and cc_rouge_l would refuse about their common arguments, as ValueError before a device is touched.
+    Returns (C, n, G, Rmax, Lr)."""
+    if cand.dim() != 2 or cand.dtype != torch.int64:
+        raise ValueError(f"cand must be int64 (C, n), got {cand.dtype} {tuple(cand.shape)}")
+    if refs.dim() != 3 or refs.dtype != torch.int32 or not refs.is_contiguous():
+        raise ValueError(f"refs must be contiguous int32 (G, Rmax, Lr), got {refs.dtype} {tuple(refs.shape)}")
+    C_, n = cand.shape
+    G, Rmax, Lr = refs.shape
+    if G < 1 or Rmax < 1 or Lr < 1:
+        raise ValueError(f"refs must hold at least one image, reference and position, got {tuple(refs.shape)}")
+    if n > CIDER_MAX_LEN or Lr > CIDER_MAX_LEN or Rmax * Lr > CIDER_MAX_REF_TOKENS:
+        raise ValueError(f"{what} takes candidates and references of at most {CIDER_MAX_LEN} positions and at most "
+                         f"{CIDER_MAX_REF_TOKENS} reference positions per image, got n = {n}, Rmax = {Rmax}, Lr = {Lr}")
+    if (n > 1 and cand.stride(1) != 1) or (C_ > 1 and cand.stride(0) < n):
+        raise ValueError("cand rows must be dense and must not overlap")
+    if cand_group is None:
+        if C_ % G:
+            raise ValueError(f"without cand_group the {C_} candidates must be a multiple of the {G} images")
+    elif cand_group.dtype != torch.int32 or cand_group.shape != (C_,) or not cand_group.is_contiguous():
+        raise ValueError(f"cand_group must be contiguous int32 ({C_},)")
+    if ref_count is not None and (ref_count.dtype != torch.int32 or ref_count.shape != (G,) or not ref_count.is_contiguous()):
+        raise ValueError(f"ref_count must be contiguous int32 ({G},)")
+    for t in (refs, ref_count, cand_group):
+        if t is not None and t.device != cand.device:
+            raise ValueError(f"every tensor must be on the candidates' device {cand.device}, got {t.device}")
+    return C_, n, G, Rmax, Lr
+
+
+def bleu_stats(cand: torch.Tensor, refs: torch.Tensor, *, stop_token: int = 50256, count_stop: bool = False,
+               ref_count: Optional[torch.Tensor] = None, cand_group: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """BLEU-1..4 over word ids (cc_bleu_stats, one launch; nothing is read back): the reference's bleu_scorer.py with option "closest".
+    ``cand``, ``refs``, ``ref_count``, ``cand_group``, ``stop_token`` and ``count_stop`` are ``cider_score``'s, except that any id >= 0
+    is a word and ``stop_token`` has no upper limit.  Returns (stats int32 (C, 10): L, reflen, guess[1..4], correct[1..4] per candidate,
+    exact; bleu fp32 (C, 4): the sentence scores).  ``bleu_corpus(stats)`` gives the corpus score.  ValueError for anything
+    cc_bleu_stats would refuse, before a device is touched."""
+    C_, n, G, Rmax, Lr = _caption_metric_shapes("bleu_stats", cand, refs, ref_count, cand_group)
+    stats = torch.empty(C_, 10, dtype=torch.int32, device=cand.device)
+    bleu = torch.empty(C_, 4, dtype=torch.float32, device=cand.device)
+    if C_ == 0:
+        return stats, bleu
+    _require_cuda(cand, "bleu_stats")
+    ld = cand.stride(0) if C_ > 1 else max(cand.stride(0), n)
+    check(_lib.lib().cc_bleu_stats(_p(cand), C_, n, ld, int(stop_token), 1 if count_stop else 0,
+                                   _p(cand_group) if cand_group is not None else None, _p(refs), G, Rmax, Lr,
+                                   _p(ref_count) if ref_count is not None else None, _p(stats), _p(bleu), _stream(cand.device)),
+          "cc_bleu_stats")
+    return stats, bleu
+
+
+ROUGE_BETA = 1.2                                                                # the reference's rouge.py
+
+
+def rouge_l(cand: torch.Tensor, refs: torch.Tensor, *, stop_token: int = 50256, count_stop: bool = False,
+            ref_count: Optional[torch.Tensor] = None, cand_group: Optional[torch.Tensor] = None,
+            beta: float = ROUGE_BETA) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ROUGE-L over word ids (cc_rouge_l, one launch; nothing is read back): the reference's rouge.py, except that an empty candidate
+    scores 0 and an empty reference adds 0 to both maxima.  Arguments as ``bleu_stats``; ``beta`` is rounded to fp32 on its way to the
+    kernel.  Returns (score fp32 (C,), lcs int32 (C, Rmax): the exact LCS length against every reference row in use, -1 for the
+    others).  ValueError for anything cc_rouge_l would refuse, before a device is touched."""
+    import math
+    C_, n, G, Rmax, Lr = _caption_metric_shapes("rouge_l", cand, refs, ref_count, cand_group)
+    beta = float(beta)
+    if not (beta > 0.0 and math.isfinite(beta)):
+        raise ValueError(f"beta must be positive and finite, got {beta}")
+    score = torch.empty(C_, dtype=torch.float32, device=cand.device)
+    lcs = torch.empty(C_, Rmax, dtype=torch.int32, device=cand.device)
+    if C_ == 0:
+        return score, lcs
+    _require_cuda(cand, "rouge_l")
+    ld = cand.stride(0) if C_ > 1 else max(cand.stride(0), n)
+    check(_lib.lib().cc_rouge_l(_p(cand), C_, n, ld, int(stop_token), 1 if count_stop else 0,
+                                _p(cand_group) if cand_group is not None else None, _p(refs), G, Rmax, Lr,
+                                _p(ref_count) if ref_count is not None else None, beta, _p(lcs), _p(score), _stream(cand.device)),
+          "cc_rouge_l")
+    return score, lcs
+
+
+def bleu_from_counts(counts) -> List[float]:
+    """[BLEU-1 .. BLEU-4] from ten numbers L, reflen, guess[1..4], correct[1..4] — a sentence's, or a corpus's sums — in Python float64,
+    as the reference's bleu_scorer.py computes both."""
+    import math
+    L, reflen, guess, correct = counts[0], counts[1], counts[2:6], counts[6:10]
+    tiny, small = 1e-15, 1e-9
+    out, p = [], 1.0
+    for n in range(4):
+        p *= (float(correct[n]) + tiny) / (float(guess[n]) + small)
+        out.append(p ** (1.0 / (n + 1)))
+    ratio = (L + tiny) / (reflen + small)
+    if ratio < 1:
+        out = [b * math.exp(1 - 1 / ratio) for b in out]
+    return out
+
+
+def bleu_corpus(stats: torch.Tensor) -> List[float]:
+    """The corpus BLEU-1..4 of ``bleu_stats``'s ``stats`` (C, 10): the ten columns are summed on their device in int64, the ten sums read
+    back, and the formula runs in Python float64 — exact up to float64, as the integers are exact."""
+    if stats.dim() != 2 or stats.shape[1] != 10 or stats.dtype != torch.int32:
+        raise ValueError(f"stats must be int32 (C, 10), got {stats.dtype} {tuple(stats.shape)}")
+    return bleu_from_counts(stats.sum(dim=0, dtype=torch.int64).tolist())
+
+
 def contrastive_buffers(device, S: int, k: int, D: int, ctx_max: int, entry_length: int):
     """The device state of ONE contrastive-search decode of S captions with k candidates each (never shared between decodes, streams or
     threads), as a namespace: cand_tok int32 (S*k,), cand_prob fp32 (S*k,), cand_h fp32 (S*k, D) — the candidates of the step;

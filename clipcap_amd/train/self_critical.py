@@ -4,7 +4,8 @@ The REINFORCE term with the model's own greedy caption as the baseline is a cros
 carries the weight ``reward(sample) - reward(greedy)``: exactly the weighted loss of ``ClipCapModel.fused_step(token_weights=...)``.
 This module adds no device code; it decodes twice with ``sample_tokens``, asks the caller for the rewards and takes the weighted step.
 ``reward_fn`` gets token ids and may be any metric of the caller's; ``clipcap_amd.train.cider.CiderReward(...).for_batch(refs)`` is one
-that never leaves the device: CIDEr-D over token ids against token-id references, one launch for both decodes (cc_cider_score).
+that never leaves the device: CIDEr-D over token ids against token-id references, one launch for both decodes (cc_cider_score);
+``clipcap_amd.train.metrics.MetricReward`` mixes it with BLEU and ROUGE-L (cc_bleu_stats, cc_rouge_l), one launch per metric.
 """
 from typing import Callable, Optional, Tuple
 

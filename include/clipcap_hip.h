@@ -73,7 +73,7 @@ extern "C" {
  * cc_lmhead_ce_fwd_w, cc_lmhead_ce_bwd_w, the sampling truncation rules cc_logits_truncate, and stochastic beam search
  * cc_beam_gumbel_ws_bytes, cc_beam_gumbel_step with its noise test hooks cc_gumbel_noise, cc_gumbel_from_bits, the CIDEr-D reward
  * cc_cider_score with its host-only table builder cc_cider_table_build, and lexically constrained beam search cc_beam_lex_ws_bytes,
- * cc_beam_lex_step. */
+ * cc_beam_lex_step, and the caption metrics cc_bleu_stats, cc_rouge_l. */
 #define CC_ABI_VERSION 3
 int cc_abi_version(void);
 
@@ -514,6 +514,48 @@ int cc_cider_score(const int64_t* cand, int32_t C, int32_t cand_len, int64_t can
  * distinct keys with their idf into tab_keys[cap] / tab_idf[cap].  CC_ERR_ARG, the table's contents then unspecified: cap not a power
  * of two, 2 n > cap (the load factor stays at or below 0.5), a duplicate key, the all-ones key (the empty marker), NULL pointers. */
 int cc_cider_table_build(const uint64_t* keys, const float* idf, int64_t n, uint64_t* tab_keys, float* tab_idf, int64_t cap);
+/* BLEU-1..4 and ROUGE-L over word ids (since 3, added without a version bump; the metrics of the reference's
+ * eval/pycocoevalcap/bleu/bleu_scorer.py as Bleu.compute_score calls it, option "closest", and eval/pycocoevalcap/rouge/rouge.py).  Words
+ * are non-negative integers: token ids, or the word ids of clipcap_amd.eval.  Neither entry point hashes or packs anything: n-grams and
+ * words are compared exactly, so any id >= 0 is a word and a candidate id >= 2^31 simply matches no reference word.
+ * Candidates, references, ref_count and cand_group are cc_cider_score's: cand int64 [C][cand_ld], cand_len columns read; a candidate's
+ *   words run to the first of: a stop_token (excluded; included when count_stop != 0), a negative id, cand_len.  stop_token < 0: no stop
+ *   token (there is no upper limit on it here).  Candidate c belongs to image cand_group[c], or to c % G when cand_group is NULL (C must
+ *   then be a multiple of G).  refs int32 [G][Rmax][Lr]; a row ends at its first negative id; image g uses its first ref_count[g] rows
+ *   (clamped to 1..Rmax; NULL: all Rmax), the other rows are not read.
+ *
+ * cc_bleu_stats: for candidate c of L words, the references r of its image, and n = 1..4
+ *     guess[n]   = max(0, L - n + 1)
+ *     correct[n] = sum over the distinct n-grams g of c of  min(tf_c(g), max_r tf_r(g))
+ *     reflen     = the l among the references' lengths with the smallest (|l - L|, l): a tie goes to the SHORTER reference
+ *     p = 1;  for n = 1..4:  p *= (correct[n] + 1e-15) / (guess[n] + 1e-9);  bleu_n = p^(1/n)
+ *     ratio = (L + 1e-15) / (reflen + 1e-9);  if ratio < 1:  bleu_n *= exp(1 - 1/ratio)
+ *   stats[c][0..10) = L, reflen, guess[1..4], correct[1..4]: exact integers.  The corpus score is the last two lines on the SUMS of the
+ *   ten integers over all candidates (the caller's: clipcap_amd.engine.bleu_corpus).  bleu[c][0..4) = the sentence scores, fp64
+ *   arithmetic on the integers, rounded once to fp32; bleu may be NULL: only the integers are written.  A cand_group value outside [0, G)
+ *   gives an all-zero row of both.  stats[0 .. 10 C) and bleu[0 .. 4 C) are written, nothing else.
+ *
+ * cc_rouge_l: lcs(c, r) = the length of the longest common subsequence;  P = max_r lcs / L_c,  R = max_r lcs / L_r (the two maxima may
+ *   come from different references);  out[c] = (1 + beta^2) P R / (R + beta^2 P), 0 if P = 0 or R = 0 (the reference: beta = 1.2; beta
+ *   arrives as fp32 and is widened).  An empty candidate scores 0 and an empty reference adds 0 to both maxima (the reference never sees
+ *   an empty list: "".split(" ") is [""]).  P, R and the score are fp64, rounded once to fp32.  lcs, when not NULL: lcs[c][r] = the exact
+ *   LCS length for the rows in use, -1 for the rows not in use.  A cand_group value outside [0, G) gives out[c] = 0 and no row in use
+ *   (lcs[c][*] = -1).  out[0 .. C) and lcs[0 .. C Rmax) are written, nothing else.
+ *
+ * One launch each, one workgroup per candidate, candidate and references in LDS.  BLEU: wave n - 1 counts the n-grams of length n, tf and
+ * first occurrence by exact comparison.  ROUGE-L: the bit-parallel LCS recurrence on 64-bit ballots, one wave per reference at a time.
+ * Integer sums and maxima in a fixed order, nothing added in floating point, no global atomics: the same input gives the same bits on
+ * every run, and a row does not depend on the other candidates.
+ * Limits (CC_ERR_SHAPE): cand_len <= 256, Lr <= 256, Rmax * Lr <= 4096.
+ * CC_ERR_ARG: C < 0, cand_len < 0, cand_ld < cand_len, G < 1, Rmax < 1, Lr < 1, cand_group NULL with C not a multiple of G; cc_rouge_l:
+ * beta <= 0 or not finite; with C > 0, a NULL cand or refs, a NULL stats (cc_bleu_stats) or out (cc_rouge_l).  C == 0: CC_OK, nothing
+ * is launched.  All of this is decided before anything touches the device. */
+int cc_bleu_stats(const int64_t* cand, int32_t C, int32_t cand_len, int64_t cand_ld, int32_t stop_token, int32_t count_stop,
+                  const int32_t* cand_group, const int32_t* refs, int32_t G, int32_t Rmax, int32_t Lr, const int32_t* ref_count,
+                  int32_t* stats, float* bleu, void* stream);
+int cc_rouge_l(const int64_t* cand, int32_t C, int32_t cand_len, int64_t cand_ld, int32_t stop_token, int32_t count_stop,
+               const int32_t* cand_group, const int32_t* refs, int32_t G, int32_t Rmax, int32_t Lr, const int32_t* ref_count, float beta,
+               int32_t* lcs, float* out, void* stream);
 /* Contrastive search (since 3, added without a version bump; not in the reference: Su et al., 2022, "A Contrastive Framework for Neural
  * Text Generation"): at every step the k most probable tokens of a caption are run through the model as k rows of one group, and the
  * token kept is the one with the largest  (1 - alpha) p(c) - alpha max_j cos(h_c, h_j),  h_c = the candidate's final hidden state, h_j =
