@@ -55,6 +55,10 @@ class MapperCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("E", "D", "P", "L", "H", "N", "Hm", "W", "use_pos", "op_dtype")]
 
 
+class MlpCfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("E", "D", "L", "Hd", "op_dtype")]
+
+
 class Gpt2Cfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("D", "H", "NL", "V", "Vp", "NPOS", "op_dtype")]
 
@@ -65,7 +69,7 @@ class Gpt2Shape(C.Structure):
 
 
 _P, _I, _L, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-_MC, _GC, _GS = C.POINTER(MapperCfg), C.POINTER(Gpt2Cfg), C.POINTER(Gpt2Shape)
+_MC, _GC, _GS, _LC = C.POINTER(MapperCfg), C.POINTER(Gpt2Cfg), C.POINTER(Gpt2Shape), C.POINTER(MlpCfg)
 
 # name -> (restype, argtypes): one entry per symbol declared in include/clipcap_hip.h
 SIGNATURES = {
@@ -75,6 +79,15 @@ SIGNATURES = {
     "cc_mapper_ws_bytes": (_L, [_MC, _I, _I]),
     "cc_mapper_sync_weights": (_I, [_MC, _P, _P, _P]),
     "cc_mapper_transpose_weights": (_I, [_MC, _P, _P]),
+    "cc_mlp_param_count": (_L, [_LC]),
+    "cc_mlp_param_offsets": (_I, [_LC, C.POINTER(_L)]),
+    "cc_mlp_ws_bytes": (_L, [_LC, _I, _I]),
+    "cc_mlp_sync_weights": (_I, [_LC, _P, _P, _P]),
+    "cc_mlp_transpose_weights": (_I, [_LC, _P, _P]),
+    "cc_mlp_fwd": (_I, [_LC, _I, _P, _P, _P, _P, _P, _I, _P]),
+    "cc_mlp_bwd": (_I, [_LC, _I, _P, _P, _P, _P, _P, _P]),
+    "cc_mlp_bwd_part": (_I, [_LC, _I, _P, _P, _P, _P, _P, _I, _P]),
+    "cc_mlp_get": (_I, [_LC, _I, _P, _I, _P, _L, _P]),
     "cc_gpt2_sync_weights": (_I, [_GC, _P, _P, _P]),
     "cc_gpt2_transpose_weights": (_I, [_GC, _P, _P]),
     "cc_mapper_fwd": (_I, [_MC, _I, _P, _P, _P, _P, _P, _I, _P]),
@@ -153,6 +166,7 @@ SIGNATURES = {
     "cc_x3_image_bytes": (_L, [_L, _L]),
     "cc_x3_split_rows": (_I, [_I, _P, _L, _I, _I, _I, _P, _P]),
     "cc_gemm_act": (_I, [_I, _I, _I, _P, _I, _I, _P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P, _P, _L, _P]),
+    "cc_gemm_tanh": (_I, [_I, _I, _I, _P, _I, _I, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, _P, _L, _P]),
     "cc_gemm_resid": (_I, [_I, _I, _I, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _F, C.c_uint64, _I, _I, _P, _L, _P]),
     "cc_gemm_dact": (_I, [_I, _I, _I, _P, _I, _I, _P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P, _L, _P]),
     "cc_gemm_f32": (_I, [_I, _I, _I, _P, _I, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _F, _I, _P, _L, _P]),

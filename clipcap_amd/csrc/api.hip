@@ -1181,6 +1181,16 @@ int CC_API(cc_gemm_act)(int32_t al, int32_t bl, const void* A, int32_t a_img, in
                         static_cast<act_t*>(pre), cx);
 }
 
+int CC_API(cc_gemm_tanh)(int32_t al, int32_t bl, const void* A, int32_t a_img, int32_t lda, const uint16_t* B, int32_t ldb, int32_t M, int32_t N, int32_t K,
+                 void* C, int32_t c_img, int32_t ldc, const float* bias, void* pre, int32_t pre_nt, void* x3, int64_t x3_bytes, void* stream) {
+    if (!hook_operands_ok(al, bl, A, a_img, lda, B, ldb, M, N, K) || !C || !al16(C) || !al16(pre) || !al16(bias) || ldc < N || !hook_c_img_ok(c_img, N))
+        return CC_ERR_ARG;
+    Call cx{S_(stream)};
+    hook_scratch(cx, x3, x3_bytes);
+    return gemm_tanh(al, bl, ActIn(static_cast<const act_t*>(A), a_img), lda, B, ldb, M, N, K, Act(static_cast<act_t*>(C), c_img), ldc, bias,
+                     static_cast<act_t*>(pre), pre_nt != 0, cx);
+}
+
 int CC_API(cc_gemm_resid)(int32_t al, int32_t bl, const void* A, int32_t a_img, int32_t lda, const uint16_t* B, int32_t ldb, int32_t M, int32_t N, int32_t K,
                   float* out, const float* res, int32_t ld, const float* bias, float p, uint64_t seed, int32_t site, int32_t layer, void* x3,
                   int64_t x3_bytes, void* stream) {

@@ -231,6 +231,17 @@ __device__ __forceinline__ float gelu_new_grad(float x) {
     return __builtin_fmaf(x * q, __builtin_fmaf(-s, s, s), s);                            // s + x q s (1 - s)
 }
 
+// tanh on the same two units (the MLP mapping network's activation, gemm.hip.h EpiTanh): with e = exp(-2 |x|) in (0, 1],
+//   tanh |x| = (1 - e) / (1 + e),   sign restored by copysign.
+// The exponent is never positive, so nothing overflows: e underflows to 0 from |x| ~ 44 and the result is exactly +-1 (fp32 rounding of
+// 1 - e gives +-1 already from |x| ~ 9).  x = +-0 gives e = 1 and +-0; NaN goes through exp2, the product and copysign as NaN.  Near 0 the
+// subtraction 1 - e is exact (e >= 1/2) and the error is that of e: ~1 ulp of 1 absolute, not relative to tanh x.
+__device__ __forceinline__ float tanh_f(float x) {
+    constexpr float LOG2E = 1.4426950408889634f;
+    const float e = __builtin_amdgcn_exp2f(__builtin_fabsf(x) * (-2.0f * LOG2E));
+    return __builtin_copysignf((1.0f - e) * __builtin_amdgcn_rcpf(1.0f + e), x);
+}
+
 // ---- dropout (GPT-2 full finetune in train mode: embd / attention-probability / residual dropout, hf modeling_gpt2.py) --------
 // Counter-based: keep(element) is a hash of (seed, stream = site * 256 + layer, element index), so the backward pass regenerates the
 // forward's mask instead of storing it.  One 32-bit hash serves TWO neighbouring elements (idx >> 1; low / high 16 bits), so the vector

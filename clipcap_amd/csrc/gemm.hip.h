@@ -1725,6 +1725,48 @@ struct EpiBF16Plain {
     }
 };
 
+// C = h = tanh(acc + bias); `pre` (nullable) receives t = 1 - h h, taken from the fp32 h before any rounding: the multiplier the backward
+// applies with EpiDActT<3>.  The MLP mapping network's first GEMM (mlp.hip).  A functor of its own, so the kernels instantiated for the
+// other functors keep their code.
+struct EpiTanh {
+    act_t* C;
+    act_t* pre;         // nullable; plain [M][ldc] layout whatever `img` says
+    const float* bias;  // nullable
+    int ldc, M, Ns;     // Ns: columns to store (multiple of 8)
+    bool pre_nt = false; // `pre` is read only by the backward pass -> non-temporal stores
+    int img = 0;         // bf16x3: > 0 = write C as the consumer's operand image with this row width (epi_store8)
+    __device__ __forceinline__ void operator()(int row, int col, float (&v)[8]) const {
+        if (row >= M || col >= Ns) return;
+        if (bias) {
+            const float4 b0 = *reinterpret_cast<const float4*>(bias + col);
+            const float4 b1 = *reinterpret_cast<const float4*>(bias + col + 4);
+            v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w; v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
+        }
+        finish(row, col, v);
+    }
+    static constexpr bool kPre = false;
+    __device__ __forceinline__ void pre4(int, int, f32x4&) const {}
+    __device__ __forceinline__ void bias8(int col, float (&b)[8]) const { load_bias8(bias, col, Ns, b); }
+    __device__ __forceinline__ void fin(int row, int col, float (&v)[8], const float (&b)[8]) const {
+        if (row >= M || col >= Ns) return;
+#pragma unroll
+        for (int e = 0; e < 8; e++) v[e] += b[e];
+        finish(row, col, v);
+    }
+  private:
+    __device__ __forceinline__ void finish(int row, int col, float (&v)[8]) const {
+#pragma unroll
+        for (int e = 0; e < 8; e++) v[e] = tanh_f(v[e]);
+        if (pre) {
+            float t[8];
+#pragma unroll
+            for (int e = 0; e < 8; e++) t[e] = __builtin_fmaf(-v[e], v[e], 1.0f);
+            if (pre_nt) act_st8_nt(pre + (size_t)row * ldc + col, t); else act_st8(pre + (size_t)row * ldc + col, t);
+        }
+        epi_store8(C, ldc, row, col, v, img);
+    }
+};
+
 // out(fp32) = res + drop(acc + bias)   (residual stream update; out may alias res; drop = residual dropout, off unless drop.thresh)
 struct EpiResid {
     float* out;

@@ -18,6 +18,9 @@ namespace CC_NS {
 // Only al = bl = 0 is supported there.  An output C with C.img == n leaves the epilogue as the image of an n-deep A operand (epi_store8).
 int gemm_bf16out(int al, int bl, ActIn A, int lda, const op16_t* B, int ldb, int M, int N, int K, Act C, int ldc,
                  const float* bias, int act, act_t* pre, Call& cx);
+// C = h = tanh(A B^T + bias); pre (nullable, plain [M][ldc]) = 1 - h^2 from the fp32 h; pre_nt: only a backward pass reads it (gemm.hip.h EpiTanh)
+int gemm_tanh(int al, int bl, ActIn A, int lda, const op16_t* B, int ldb, int M, int N, int K, Act C, int ldc,
+              const float* bias, act_t* pre, bool pre_nt, Call& cx);
 int gemm_resid(int al, int bl, ActIn A, int lda, const op16_t* B, int ldb, int M, int N, int K, float* out, const float* res,
                int ld, const float* bias, Call& cx, Drop drop = Drop());
 // mode 0 store (+bias), 1 add, 2 atomic add (required when ksplit > 1)

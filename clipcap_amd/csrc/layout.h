@@ -102,6 +102,26 @@ inline bool mapper_cfg_ok(const cc_mapper_cfg* c) {
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// MLP mapper arena: model.0.weight [Hd][E], model.0.bias [Hd], model.2.weight [L D][Hd], model.2.bias [L D]
+// ------------------------------------------------------------------------------------------------------------
+struct MlpOff {
+    int64_t w1, b1, w2, b2, total;
+    explicit MlpOff(const cc_mlp_cfg* c) {
+        const int64_t LD = (int64_t)c->L * c->D;
+        w1 = 0;
+        b1 = w1 + (int64_t)c->Hd * c->E;
+        w2 = b1 + c->Hd;
+        b2 = w2 + LD * c->Hd;
+        total = b2 + LD;
+    }
+};
+// (Hd % 8 == 0 with Hd == L D / 2 exactly makes L D a multiple of 16; every tensor then starts on a 16-byte boundary in both arenas)
+inline bool mlp_cfg_ok(const cc_mlp_cfg* c) {
+    return c && (c->op_dtype == CC_OP) && c->E > 0 && c->D > 0 && c->L > 0 && c->Hd > 0 && (c->E % 8) == 0 && (c->D % 8) == 0 && (c->Hd % 8) == 0 &&
+           (int64_t)c->L * c->D == 2 * (int64_t)c->Hd && (int64_t)c->L * c->D <= (int64_t)1 << 24;
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // GPT-2 arena: wte [Vp, D], wpe [NPOS, D], NL uniform layers, ln_f — O(1) to build: the decode step builds one per generated position
 // ------------------------------------------------------------------------------------------------------------
 struct Gpt2Off {

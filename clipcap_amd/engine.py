@@ -459,6 +459,111 @@ class MapperEngine:
             on_layers_done(0, a.n)
 
 
+class MlpMapperEngine:
+    """The MLP mapping network of the ClipCap paper — Linear(E -> L*D/2), Tanh, Linear(L*D/2 -> L*D), reshaped to (B, L, D) — on the
+    HIP library (cc_mlp_*).  Same engine interface as MapperEngine where its callers use it (ClipCapEngine, GradReducer, the
+    checkpoint callback, EMA, the decoders); state-dict names are the original's nn.Sequential indices."""
+
+    NAMES = ("model.0.weight", "model.0.bias", "model.2.weight", "model.2.bias")
+
+    def __init__(self, E: int, D: int, prefix_length: int, device="cpu", precision=None):
+        L = prefix_length
+        if (L * D) % 2:
+            raise _lib.CCError(f"unsupported MLP mapper configuration E={E} D={D} L={L}: L*D must be even (hidden width L*D/2)")
+        self.dims = dict(E=E, D=D, L=L, Hd=(L * D) // 2, W=1)
+        self.op_dtype = op_dtype_of(precision)
+        self.cfg = _lib.MlpCfg(E=E, D=D, L=L, Hd=self.dims["Hd"], op_dtype=self.op_dtype)
+        l = _lib.lib()
+        n = l.cc_mlp_param_count(C.byref(self.cfg))
+        if n < 0:
+            raise _lib.CCError(f"unsupported MLP mapper configuration {self.dims}: E, D and L*D/2 must be multiples of 8")
+        self.arena = _Arena(n, device, self._sync, self.op_dtype)
+        offs = (C.c_int64 * 4)()
+        check(l.cc_mlp_param_offsets(C.byref(self.cfg), offs))
+        self.offsets = list(offs)
+        self._ws: Dict[Tuple[int, int], torch.Tensor] = {}
+
+    def _sync(self, w32, w16, st):
+        if w32 is None:          # the cast half is current (written by the optimizer step): transposed copy only
+            return _lib.lib().cc_mlp_transpose_weights(C.byref(self.cfg), w16, st)
+        return _lib.lib().cc_mlp_sync_weights(C.byref(self.cfg), w32, w16, st)
+
+    def shapes(self) -> List[Tuple[str, int, Tuple[int, ...]]]:
+        d = self.dims
+        E, LD, Hd = d["E"], d["L"] * d["D"], d["Hd"]
+        shp = [(Hd, E), (Hd,), (LD, Hd), (LD,)]
+        return [(nm, self.offsets[i], shp[i]) for i, nm in enumerate(self.NAMES)]
+
+    views = MapperEngine.views
+    to = MapperEngine.to
+    set_precision = MapperEngine.set_precision
+
+    def _workspace(self, B: int, save: int) -> torch.Tensor:
+        key = (B, save)
+        ws = self._ws.get(key)
+        if ws is None:
+            nbytes = _lib.lib().cc_mlp_ws_bytes(C.byref(self.cfg), B, save)
+            check(nbytes, "cc_mlp_ws_bytes")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.arena.device)
+            self._ws[key] = ws
+        return ws
+
+    def forward(self, emb: torch.Tensor, save: bool = False) -> torch.Tensor:
+        """emb fp32 (B, E) -> prefix fp32 (B, L, D)."""
+        d = self.dims
+        if emb.dim() != 2 or emb.shape[1] != d["E"]:
+            raise ValueError(f"expected embeddings of shape (B,{d['E']}), got {tuple(emb.shape)} (the MLP mapper takes no windowed embeddings)")
+        _require_cuda(self.arena.w32, "MlpMapperEngine.forward")
+        emb = emb.to(device=self.arena.device, dtype=torch.float32).contiguous()
+        B = emb.shape[0]
+        self.arena.sync_bf16()
+        out = torch.empty(B, d["L"], d["D"], dtype=torch.float32, device=self.arena.device)
+        ws = self._workspace(B, int(save))
+        check(_lib.lib().cc_mlp_fwd(C.byref(self.cfg), B, _p(self.arena.w32), _p(self.arena.w16), _p(emb), _p(ws), _p(out), int(save),
+                                   _stream(self.arena.device)), "cc_mlp_fwd")
+        self._last = (B, emb)  # keep the input alive until backward has consumed the workspace
+        if save:
+            self._saved_batch = B
+            self._fwd_serial = getattr(self, "_fwd_serial", 0) + 1
+        return out
+
+    def get(self, B: int, field: int) -> torch.Tensor:
+        """Test hook (cc_mlp_get): one saved field of the last forward(save=True) / backward with batch B, in its stored type:
+        0 x16 (B, E), 1 h (B, Hd), 2 t (B, Hd), 3 g16 (B, L*D), 4 dU (B, Hd)."""
+        ws = self._ws.get((B, 1))
+        if ws is None:
+            raise RuntimeError("MlpMapperEngine.get needs a preceding forward(save=True) with the same batch")
+        d = self.dims
+        width = (d["E"], d["Hd"], d["Hd"], d["L"] * d["D"], d["Hd"])[field]
+        dt = {OP_BF16: torch.bfloat16, OP_FP16: torch.float16, OP_X3: torch.float32}[self.op_dtype]
+        out = torch.empty(B, width, dtype=dt, device=self.arena.device)
+        check(_lib.lib().cc_mlp_get(C.byref(self.cfg), B, _p(ws), field, _p(out), out.numel() * out.element_size(), _stream(self.arena.device)),
+              "cc_mlp_get")
+        return out
+
+    def backward(self, dout: torch.Tensor, on_layers_done=None, group: int = 2):
+        """Accumulates d loss / d params into the gradient arena; needs a preceding forward(save=True).  No gradient for the input.
+        on_layers_done(lo, hi): with it the pass runs in two halves — model.2.* first (94 % of the gradient bytes at the real shape),
+        reported as [off(model.2.weight), n), then model.0.*, reported as [0, off(model.2.weight)) — so the DDP reducer has most of
+        the arena on the wire before the second half is enqueued.  `group` is accepted for MapperEngine's signature and unused."""
+        B = dout.shape[0]
+        dout = dout.to(dtype=torch.float32).contiguous()
+        ws = self._ws.get((B, 1))
+        if ws is None:
+            raise RuntimeError("MlpMapperEngine.backward without forward(save=True)")
+        l = _lib.lib()
+        a = self.arena
+        args = (C.byref(self.cfg), B, _p(a.w32), _p(a.w16), _p(ws), _p(dout), _p(a.grads()))
+        if on_layers_done is None:
+            check(l.cc_mlp_bwd(*args, _stream(a.device)), "cc_mlp_bwd")
+            return
+        cut = self.offsets[2]
+        check(l.cc_mlp_bwd_part(*args, 1, _stream(a.device)), "cc_mlp_bwd_part")
+        on_layers_done(cut, a.n)
+        check(l.cc_mlp_bwd_part(*args, 0, _stream(a.device)), "cc_mlp_bwd_part")
+        on_layers_done(0, cut)
+
+
 class Gpt2Engine:
     """HF GPT2LMHeadModel arithmetic (transformers modeling_gpt2.py) on the HIP library; arena keeps HF layouts."""
 

@@ -9,6 +9,9 @@ from typing import Optional
 from clipcap_amd.encoders.config import EncoderConfig
 
 
+MAPPING_TYPES = ("transformer", "mlp")
+
+
 @dataclass
 class TrainingConfig:
     optimizer_lr: float = 2e-5
@@ -36,12 +39,24 @@ class Config:
     use_positional_embeddings: bool = True
     encoder_config: Optional[EncoderConfig] = None
     training_config: Optional[TrainingConfig] = None
+    # "transformer" (the reference's only mapper) or "mlp" (the ClipCap paper's MLP mapping network, what the original checkpoints hold:
+    # projection_length, transformer_layers and transformer_attention_heads are then unused).  Not a CLI flag; a namespace attribute reaches
+    # from_args.  Left out of to_dict() at its default, so a transformer config keeps the reference's exact yaml schema.
+    mapping_type: str = "transformer"
+
+    def __post_init__(self):
+        if self.mapping_type not in MAPPING_TYPES:
+            raise ValueError(f"mapping_type must be one of {MAPPING_TYPES}, got {self.mapping_type!r}")
 
     def to_dict(self) -> dict:
-        return asdict(self)
+        d = asdict(self)
+        if d["mapping_type"] == "transformer":
+            del d["mapping_type"]
+        return d
 
     @classmethod
     def from_args(cls, args: Namespace) -> "Config":
         names = ("language_model", "train_language_model", "prefix_length", "projection_length", "transformer_layers",
                  "transformer_attention_heads", "use_positional_embeddings")
-        return cls(encoder_config=None, training_config=None, **{n: getattr(args, n) for n in names})
+        return cls(encoder_config=None, training_config=None, mapping_type=getattr(args, "mapping_type", "transformer"),
+                   **{n: getattr(args, n) for n in names})

@@ -8,7 +8,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from clipcap_amd.engine import MapperEngine
+from clipcap_amd.engine import MapperEngine, MlpMapperEngine
 from clipcap_amd.model.arena_module import ArenaModule
 
 
@@ -83,6 +83,31 @@ class TransformerMapper(ArenaModule):
         from the mapper: S = window * projection_length + prefix_length rows, probabilities over the key axis (dim 2)."""
         out = self.engine.forward(x, save=True)
         return out, self.engine.attention_probs(x.shape[0])
+
+
+class MLPMapper(ArenaModule):
+    """The MLP mapping network of the ClipCap paper, the `clip_project` of the original checkpoints:
+    Linear(E -> L*D/2), Tanh, Linear(L*D/2 -> L*D), reshaped to (B, L, D).  State-dict keys are the original nn.Sequential's:
+    model.0.weight, model.0.bias, model.2.weight, model.2.bias.  Autograd goes through the same bridge as TransformerMapper."""
+
+    def __init__(self, encoder_embedding_size: int, lm_embedding_size: int, prefix_length: int, *, precision=None):
+        super().__init__()
+        self.engine = MlpMapperEngine(encoder_embedding_size, lm_embedding_size, prefix_length, precision=precision)
+        self._bind_parameters()
+        self.reset_parameters()
+
+    @torch.no_grad()
+    def reset_parameters(self):
+        """nn.Linear's defaults: weight and bias ~ U(+-1/sqrt(fan_in))."""
+        for name, p in self._arena_params.items():
+            w = self._arena_params[name.rsplit(".", 1)[0] + ".weight"]
+            bound = 1.0 / w.shape[1] ** 0.5
+            p.uniform_(-bound, bound)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self._arena_params.values()):
+            return _MapperFn.apply(self, x, *self._arena_params.values())
+        return self.engine.forward(x, save=False)
 
 
 class TransformerMapperWindowed(TransformerMapper):

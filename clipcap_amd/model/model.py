@@ -23,7 +23,7 @@ import torch.nn as nn
 from clipcap_amd.engine import ClipCapEngine, check_ema_decay, check_label_smoothing, check_token_weights, ema_decay_at
 from clipcap_amd.model.config import Config, TrainingConfig
 from clipcap_amd.model.gpt2 import GPT2LM
-from clipcap_amd.model.mapper import TransformerMapper, TransformerMapperWindowed
+from clipcap_amd.model.mapper import MLPMapper, TransformerMapper, TransformerMapperWindowed
 from clipcap_amd.model.optim import ArenaAdamW, linear_warmup_decay
 
 
@@ -98,7 +98,13 @@ class ClipCapModel(nn.Module):
         common = dict(encoder_embedding_size=enc.encoder_embedding_size, lm_embedding_size=self.lm_embedding_size,
                       prefix_length=config.prefix_length, projection_length=config.projection_length,
                       num_heads=config.transformer_attention_heads, num_layers=config.transformer_layers)
-        if enc.use_windowed_embeddings:                      # model.py:22-32
+        if getattr(config, "mapping_type", "transformer") == "mlp":
+            # the MLP mapping network; the attribute keeps its name: the trainer, the checkpoint callback, the reducer and the decoders reach
+            # the mapper through it.  projection_length / transformer_layers / transformer_attention_heads are unused.
+            if enc.use_windowed_embeddings:
+                raise ValueError("mapping_type 'mlp' takes one embedding per sample: it cannot be combined with use_windowed_embeddings")
+            self.transformer_mapper = MLPMapper(enc.encoder_embedding_size, self.lm_embedding_size, config.prefix_length)
+        elif enc.use_windowed_embeddings:                    # model.py:22-32
             self.transformer_mapper = TransformerMapperWindowed(window_size=enc.window_size + 1,
                                                                 use_pos_embeddings=config.use_positional_embeddings, **common)
         else:                                                # model.py:33-41

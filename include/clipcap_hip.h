@@ -73,7 +73,9 @@ extern "C" {
  * cc_lmhead_ce_fwd_w, cc_lmhead_ce_bwd_w, the sampling truncation rules cc_logits_truncate, and stochastic beam search
  * cc_beam_gumbel_ws_bytes, cc_beam_gumbel_step with its noise test hooks cc_gumbel_noise, cc_gumbel_from_bits, the CIDEr-D reward
  * cc_cider_score with its host-only table builder cc_cider_table_build, and lexically constrained beam search cc_beam_lex_ws_bytes,
- * cc_beam_lex_step, and the caption metrics cc_bleu_stats, cc_rouge_l. */
+ * cc_beam_lex_step, and the caption metrics cc_bleu_stats, cc_rouge_l, and the MLP mapping network cc_mlp_param_count,
+ * cc_mlp_param_offsets, cc_mlp_ws_bytes, cc_mlp_sync_weights, cc_mlp_transpose_weights, cc_mlp_fwd, cc_mlp_bwd, cc_mlp_bwd_part with
+ * its test hooks cc_mlp_get, cc_gemm_tanh. */
 #define CC_ABI_VERSION 3
 int cc_abi_version(void);
 
@@ -778,6 +780,8 @@ int cc_gemm_wgrad(int32_t op_dtype, const uint16_t* X, int32_t ldx, const uint16
  *                      hi = bf16(x), lo = bf16(x - hi).
  *   cc_gemm_act:   C = act(A B^T + bias); act 0 none, 1 relu, 2 gelu_new, 3 gelu_new with pre receiving gelu_new'(u); pre (nullable)
  *                  otherwise receives u = A B^T + bias.
+ *   cc_gemm_tanh:  C = h = tanh(A B^T + bias); pre (nullable, always the plain [M][ldc] layout) receives 1 - h h computed from the fp32 h
+ *                  (the multiplier of cc_gemm_dact act 3); pre_nt != 0 stores it with non-temporal stores (same values).
  *   cc_gemm_resid: out = res + drop(A B^T + bias), fp32 rows of stride ld, out may alias res.  drop: residual dropout with probability p
  *                  on the mask stream (seed, site, layer) of cc_dropout_mask, element index row * ld + col; p = 0: off.
  *   cc_gemm_dact:  C = (A B^T) * act'(aux); act 1 relu (aux = post-activation), 2 gelu_new (aux = pre-activation), 3 multiply by aux.
@@ -789,6 +793,8 @@ int64_t cc_x3_image_bytes(int64_t rows, int64_t depth);
 int cc_x3_split_rows(int32_t op_dtype, const float* src, int64_t ld, int32_t rows, int32_t width, int32_t form, uint16_t* dst, void* stream);
 int cc_gemm_act(int32_t op_dtype, int32_t al, int32_t bl, const void* A, int32_t a_img, int32_t lda, const uint16_t* B, int32_t ldb, int32_t M, int32_t N,
                 int32_t K, void* C, int32_t c_img, int32_t ldc, const float* bias, int32_t act, void* pre, void* x3, int64_t x3_bytes, void* stream);
+int cc_gemm_tanh(int32_t op_dtype, int32_t al, int32_t bl, const void* A, int32_t a_img, int32_t lda, const uint16_t* B, int32_t ldb, int32_t M, int32_t N,
+                 int32_t K, void* C, int32_t c_img, int32_t ldc, const float* bias, void* pre, int32_t pre_nt, void* x3, int64_t x3_bytes, void* stream);
 int cc_gemm_resid(int32_t op_dtype, int32_t al, int32_t bl, const void* A, int32_t a_img, int32_t lda, const uint16_t* B, int32_t ldb, int32_t M, int32_t N,
                   int32_t K, float* out, const float* res, int32_t ld, const float* bias, float p, uint64_t seed, int32_t site, int32_t layer,
                   void* x3, int64_t x3_bytes, void* stream);
@@ -885,6 +891,51 @@ int cc_colsum_multi(int32_t op_dtype, const uint16_t* const* X_host, float* cons
                     float* red_ws, void* stream);
 /* dst[i] += sum over b < B of src[b * src_stride + i], i < len  (fp32) */
 int cc_batch_sum(const float* src, int64_t src_stride, float* dst, int32_t len, int32_t B, float* red_ws, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * MLP mapping network (the ClipCap paper's other mapper; the `clip_project` of the original checkpoints):
+ *   prefix = reshape(Linear(Hd -> L D)(tanh(Linear(E -> Hd)(emb))), [B][L][D]),   Hd = L D / 2.
+ * Two GEMMs whose cost is weight bytes.  Arena order (state-dict names of the original's nn.Sequential): model.0.weight [Hd][E],
+ * model.0.bias [Hd], model.2.weight [L D][Hd], model.2.bias [L D].  The w16 arena follows the conventions above: [0, n) the cast,
+ * [n, 2n) the transposed copy of model.2.weight at its own offset (model.0.weight has none: no gradient flows to emb); CC_OP_BF16X3:
+ * 6n elements, the [hi | lo | hi] images of both weights at 3 off and of model.2.weight's transpose at 3 (n + off).
+ * E, D and Hd must be multiples of 8, Hd == L D / 2 exactly (so L D is a multiple of 16) and L D <= 2^24: CC_ERR_SHAPE from the count / offset / size
+ * calls, CC_ERR_ARG from the passes, before anything is launched.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t E;        /* encoder_embedding_size */
+    int32_t D;        /* lm_embedding_size */
+    int32_t L;        /* prefix_length */
+    int32_t Hd;       /* hidden width = (L * D) / 2 */
+    int32_t op_dtype; /* CC_OP_BF16 / CC_OP_FP16 / CC_OP_BF16X3 */
+} cc_mlp_cfg;
+#define CC_MLP_TENSORS 4
+int64_t cc_mlp_param_count(const cc_mlp_cfg* cfg);
+int cc_mlp_param_offsets(const cc_mlp_cfg* cfg, int64_t* offsets /* [CC_MLP_TENSORS] */);
+/* save != 0: the workspace also carries what cc_mlp_bwd needs (t, the backward's buffers and scratch).  B <= 0: CC_ERR_SHAPE */
+int64_t cc_mlp_ws_bytes(const cc_mlp_cfg* cfg, int32_t B, int32_t save);
+int cc_mlp_sync_weights(const cc_mlp_cfg* cfg, const float* w32, uint16_t* w16, void* stream);
+int cc_mlp_transpose_weights(const cc_mlp_cfg* cfg, uint16_t* w16, void* stream);      /* the [n, 2n) half only (CC_OP_BF16X3: CC_ERR_ARG) */
+/* x16 = cast(emb [B][E]); h = tanh(x16 W1^T + b1) (and, save != 0, t = 1 - h h from the fp32 h); out [B][L D] fp32 = h W2^T + b2 */
+int cc_mlp_fwd(const cc_mlp_cfg* cfg, int32_t B, const float* w32, const uint16_t* w16, const float* emb, void* ws, float* out, int32_t save,
+               void* stream);
+/* After cc_mlp_fwd(save = 1) on the same workspace.  g32 is ACCUMULATED into.  g16 = cast(dout [B][L D]); db2 += sum_b dout (fp32);
+ * dW2 += g16^T h; dU = (g16 W2) * t; dW1 += dU^T x16; db1 += column sums of dU.  No gradient for emb.  Every cross-block sum folds in a
+ * fixed order through the workspace's reduction scratch (no atomics): the same bits from run to run.
+ * cc_mlp_bwd_part: part 1 = g16, db2, dW2, dU (the gradients of model.2.*, 94 % of the arena at E = 512, D = 768, L = 10); part 0 = dW1,
+ * db1 (model.0.*), which reads the dU part 1 left: call part 1 first.  cc_mlp_bwd = part 1 then part 0.  Any other part: CC_ERR_ARG. */
+int cc_mlp_bwd(const cc_mlp_cfg* cfg, int32_t B, const float* w32, const uint16_t* w16, void* ws, const float* dout, float* g32, void* stream);
+int cc_mlp_bwd_part(const cc_mlp_cfg* cfg, int32_t B, const float* w32, const uint16_t* w16, void* ws, const float* dout, float* g32, int32_t part,
+                    void* stream);
+/* Test hook: a raw copy (hipMemcpyAsync on the call's stream, no kernel) of one field of the save = 1 workspace of (cfg, B) into dst;
+ * dst_bytes = the field's exact byte count (CC_ERR_SHAPE otherwise; CC_ERR_ARG for NULL pointers or an unknown field).  Every field is
+ * plain row-major in the stored type: the operand type's 16-bit element, fp32 in CC_OP_BF16X3 (where the GEMMs split it at their boundary). */
+#define CC_MLP_X16 0      /* [B][E]    cast of emb */
+#define CC_MLP_H 1        /* [B][Hd]   tanh output */
+#define CC_MLP_T 2        /* [B][Hd]   1 - h h */
+#define CC_MLP_G16 3      /* [B][L D]  cast of dout (after cc_mlp_bwd_part 1) */
+#define CC_MLP_DU 4       /* [B][Hd]   gradient of the pre-activation (after cc_mlp_bwd_part 1) */
+int cc_mlp_get(const cc_mlp_cfg* cfg, int32_t B, void* ws, int32_t field, void* dst, int64_t dst_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Measurement aid for bench.py's roofline line: brackets every launch of ONE GEMM call site — or, with CC_SITE_ALL_GEMMS, every
